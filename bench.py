@@ -364,6 +364,36 @@ class DeviceBatches:
         return dt / steps * 1e3
 
 
+DUMP_MAX_BYTES = 64_000_000   # --dump-outputs: files on disk, .npy headers included
+
+
+def dump_outputs(directory, ops, extra, n_extra, counts, seed=SEED, max_bytes=DUMP_MAX_BYTES):
+    """Write what smx_batch_run_device handed its caller in the last timed step as DIR/<name>.npy, so that two builds can be
+    compared output for output: ops_<field> (the primary records, one per read in read order), extra_<field> (the stored
+    extra records, sorted by read: the kernel emits them in any order between reads, in emission order within a read),
+    n_extra, and counts (accumulated over the timed steps).  Record fields are integers below 2**24, exact in float32;
+    counts are float64.  Records beyond the byte budget are cut to a fixed seeded sample of rows (each row keeps its `read`)."""
+    fields = [(f, ops.dtype[f].shape) for f in ops.dtype.names]
+    row_bytes = 4 * sum(int(np.prod(s)) for _f, s in fields)
+    extra = extra[np.argsort(extra["read"], kind="stable")]
+    cap_rows = (max_bytes - 8 * (len(counts) + 1) - 256 * (2 * len(fields) + 2)) // row_bytes   # 256: room for a header
+    n_ops_rows = len(ops) if len(ops) + len(extra) <= cap_rows else cap_rows * len(ops) // (len(ops) + len(extra))
+    os.makedirs(directory, exist_ok=True)
+
+    def save(name, a, dtype):
+        v = a.astype(dtype)
+        assert np.array_equal(v, a), f"{name} is not exact in {np.dtype(dtype).name}"
+        np.save(os.path.join(directory, f"{name}.npy"), v)
+
+    for prefix, recs, m, stream in (("ops", ops, n_ops_rows, 0), ("extra", extra, cap_rows - n_ops_rows, 1)):
+        if len(recs) > m:
+            recs = recs[np.sort(np.random.default_rng([seed, stream]).choice(len(recs), m, replace=False))]
+        for f, _s in fields:
+            save(f"{prefix}_{f}", recs[f], np.float32)
+    save("n_extra", np.array([n_extra], dtype=np.uint64), np.float64)
+    save("counts", counts, np.float64)
+
+
 def step_kernel_list(k_t, k_d, k_b, demux_name):
     return [{"kernel": "smx::prescan_transpose_kernel", "ms": k_t}, {"kernel": "smx::prescan_dp_kernel", "ms": k_d},
             {"kernel": demux_name, "ms": k_b}]
@@ -451,7 +481,11 @@ def main():
     ap.add_argument("--trim", default=None, help=argparse.SUPPRESS)   # e.g. tails: not the headline flags, DESIGN.md side numbers
     ap.add_argument("--cli-args", default="", help=argparse.SUPPRESS)  # extra specimux flags for side measurements, e.g. "-e 4"
     ap.add_argument("--config", default="c2", choices=["c2", "c3", "c5"], help=argparse.SUPPRESS)   # c3: 3072 specimens / 4 pools; c5: + 160-nt windows, 15 % errors
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the records and counts of the last timed step as DIR/<name>.npy (rank 0, at most 64 MB)")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
     if "WORLD_SIZE" not in os.environ and a.gpus > 1:
         self_launch(a, sys.argv[1:])
     rank = int(os.environ.get("RANK", "0"))
@@ -550,6 +584,12 @@ def main():
     total_reads = world * n * a.steps
     assert counts[_lib.CNT_TOTAL] == total_reads, (counts[:8], total_reads)
     assert counts[_lib.CNT_OVERFLOW] == 0 and db.max_extra() <= db.extra_cap
+    if a.dump_outputs and rank == 0:
+        # before anything below relaunches the kernels into these buffers; step i ran on stream i % len(db.streams)
+        o = db.out[(a.steps - 1) % len(db.streams)]
+        n_extra = int(o["nextra"][0].item())
+        dump_outputs(a.dump_outputs, o["ops"].cpu().numpy().view(_lib.OP_DTYPE),
+                     o["extra"][:n_extra * 32].cpu().numpy().view(_lib.OP_DTYPE), n_extra, counts)
     n_rccl_ranks = world if (world > 1 and reducer.backend == "rccl") else (1 if world == 1 else 0)
     reducer.close()
     if world > 1:

@@ -71,11 +71,21 @@ def test_two_rank_counts_reduce_equals_single_process(tmp_path):
 
 
 # ------------------------------------------------------------------ the FILE path: shard by byte range, per-rank trees, merge
+def _cpu_only_rank():
+    """No GPU in this tier, on any host: a rank sees what torch reports on a host without one.  Otherwise every rank opens
+    the GPU of a GPU host (run_sharded asks torch.cuda.is_available(); torch.distributed.barrier() asks
+    torch._C._get_accelerator(), which initialises the HIP runtime even under gloo), and an 8-rank run holds it in 8
+    processes at once."""
+    torch.cuda.is_available = lambda: False
+    torch._C._get_accelerator = lambda: torch.device("cpu")
+
+
 def _file_worker(rank, world, port, tmp, seqfile, pf, sf):
     sys.path.insert(0, REPO)
     sys.path.insert(0, os.path.join(REPO, "tests"))
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world),
                       LOCAL_RANK=str(rank), SMX_DIST_BACKEND="gloo")
+    _cpu_only_rank()
     from oracle import specimux_oracle as O
     from parity_utils import Both
     from specimux_amd import _lib
@@ -202,6 +212,7 @@ def _failing_worker(rank, world, port, tmp, seqfile):
     sys.path.insert(0, REPO)
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world),
                       LOCAL_RANK=str(rank), SMX_DIST_BACKEND="gloo")
+    _cpu_only_rank()
     from specimux_amd.distributed import run_sharded
 
     def shard_runner(path, out_dir, byte_range, stride):

@@ -238,3 +238,42 @@ def test_oracle_trace_on_golden_reads():
         assert all(ev in it for ev in streams[lo]), f"level {lo} is not a subsequence of level {hi}"
     assert not any(r[1] in ("PRIMER_SEARCH", "BARCODE_SEARCH") for r in streams[1])
     assert any(r[1] == "BARCODE_SEARCH" for r in streams[3])
+
+
+def test_bench_dump_outputs(tmp_path):
+    """bench.py --dump-outputs: float copies equal to the records, extras in read order (emission order within a read),
+    and over the byte budget a sample that is the same from run to run."""
+    import bench
+    from specimux_amd import _lib
+    rng = np.random.default_rng(5)
+    ops = np.zeros(1000, dtype=_lib.OP_DTYPE)
+    ops["read"] = np.arange(1000)
+    ops["sample"] = rng.integers(-1, 768, 1000)
+    ops["trim_end"] = rng.integers(0, 1500, 1000)
+    ops["dist"] = rng.integers(-1, 8, (1000, 4))
+    extra = np.zeros(300, dtype=_lib.OP_DTYPE)
+    extra["read"] = rng.integers(0, 1000, 300)
+    extra["trim_start"] = np.arange(300)   # emission order
+    counts = rng.integers(0, 1 << 40, 776).astype(np.uint64)
+
+    full = tmp_path / "full"
+    bench.dump_outputs(str(full), ops, extra, 300, counts)
+    assert {np.load(p).dtype for p in full.iterdir()} <= {np.dtype(np.float32), np.dtype(np.float64)}
+    for f in _lib.OP_DTYPE.names:
+        assert np.array_equal(np.load(full / f"ops_{f}.npy"), ops[f]), f
+    order = np.lexsort((extra["trim_start"], extra["read"]))
+    for f in _lib.OP_DTYPE.names:
+        assert np.array_equal(np.load(full / f"extra_{f}.npy"), extra[order][f]), f
+    assert np.array_equal(np.load(full / "counts.npy"), counts) and np.load(full / "n_extra.npy").tolist() == [300]
+
+    budget = 40_000
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), ops, extra, 300, counts, max_bytes=budget)
+    files = sorted(p.name for p in (tmp_path / "a").iterdir())
+    assert files == sorted(p.name for p in full.iterdir())
+    assert sum((tmp_path / "a" / f).stat().st_size for f in files) <= budget
+    for f in files:
+        assert np.array_equal(np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)), f
+    rows = np.load(tmp_path / "a" / "ops_read.npy").astype(np.int64)
+    assert 0 < len(rows) < len(ops) and np.all(np.diff(rows) > 0)
+    assert np.array_equal(np.load(tmp_path / "a" / "ops_sample.npy"), ops["sample"][rows])
