@@ -19,6 +19,8 @@
  *   smx_align         <- align_seq's edlib.align call (alignment.py:42), one alignment, for unit parity.
  *   smx_pack_windows  <- the two `search_len` end slices match_one_end / determine_orientation take
  *           (demultiplex.py:757-766, :612-624): the only bases the hot path ever reads.
+ *   smx_mine_*        <- specimine.py's mine_sequences (the separate specimine tool, :197-257): batched long-read
+ *           HW distances and the per-partial-read best identity.
  *   smx_counts_*      <- the parent summing (batch_total, batch_matched) (orchestration.py:203-207).
  *
  * Conventions: plain pointers and sizes only; the caller owns every buffer; no callbacks; every
@@ -270,6 +272,34 @@ int smx_align(const char *query, int qlen, const char *target, int tlen, int k, 
 int smx_align_batch(const char *queries, const uint32_t *qoff, uint32_t n_queries, const char *targets,
                     const uint64_t *toff, const uint32_t *qidx, const int32_t *k, const uint8_t *mode, uint32_t n,
                     int32_t *dist, int32_t *nloc, int32_t *starts, int32_t *ends, uint32_t cap);
+
+/*
+ * specimine: HW (infix) edit distances of long reads in batches -- query = a specimen's full read, target = one of its
+ * partial reads (reference specimine.py:197-257, edlib.align(full, partial, mode="HW", k)).  Exact byte equality, no
+ * IUPAC equalities.  Distance only.
+ *   queries / qoff     n_queries queries (concatenated, n_queries + 1 offsets), each >= 1 byte; a query's Peq table,
+ *                      (distinct bytes + 1) x ceil(len / 64) words, must fit the LDS (any DNA read up to ~250 kb)
+ *   k                  per query: max distance, < 0 = none (-1 is returned for a distance above k)
+ *   targets / toff     n_targets targets (concatenated, n_targets + 1 offsets), any length (empty: distance = query
+ *                      length whatever k is, as edlib)
+ *   jobs               each job pairs queries [q0, q0 + nq) with targets [t0, t0 + nt)
+ * smx_mine_distances writes job j's nq x nt distances row-major (one row per query) at dist[sum over earlier jobs of
+ * nq * nt].  smx_mine_best_identity reduces on the device instead: per target of job j, at best[sum over earlier jobs
+ * of nt], the largest identity = 1 - d / len(query) (IEEE double) over the job's queries with d != -1,
+ * identity >= min_identity and identity > 0; 0 when there is none.
+ * kernel_ms (may be NULL) receives the device time of the distance kernels (HIP events).
+ */
+typedef struct smx_mine_job {
+    uint32_t q0, nq, t0, nt;
+    double min_identity;      /* smx_mine_best_identity only */
+} smx_mine_job;
+
+int smx_mine_distances(const char *queries, const uint64_t *qoff, uint32_t n_queries, const int32_t *k, const char *targets,
+                       const uint64_t *toff, uint32_t n_targets, const smx_mine_job *jobs, uint32_t n_jobs, int32_t *dist,
+                       float *kernel_ms);
+int smx_mine_best_identity(const char *queries, const uint64_t *qoff, uint32_t n_queries, const int32_t *k,
+                           const char *targets, const uint64_t *toff, uint32_t n_targets, const smx_mine_job *jobs,
+                           uint32_t n_jobs, double *best, float *kernel_ms);
 
 /*
  * RCCL reduction of the per-specimen counts over xGMI (one communicator per process/GPU).

@@ -24,7 +24,8 @@ OP_DTYPE = np.dtype([("sample", "<i4"), ("trim_start", "<i4"), ("trim_end", "<i4
                      ("flags", "u1"), ("n_ops", "<u2"), ("read", "<u4")])
 HIT_DTYPE = np.dtype([("first_start", "<i4"), ("first_end", "<i4"), ("tail_end", "<i4"), ("pdist", "<i2"),
                       ("nloc", "<i2"), ("bbest", "<i2"), ("ntied", "<i2"), ("first_tied", "<i2"), ("flags", "<i2")])
-assert OP_DTYPE.itemsize == 32 and HIT_DTYPE.itemsize == 24
+MINE_JOB_DTYPE = np.dtype([("q0", "<u4"), ("nq", "<u4"), ("t0", "<u4"), ("nt", "<u4"), ("min_identity", "<f8")])
+assert OP_DTYPE.itemsize == 32 and HIT_DTYPE.itemsize == 24 and MINE_JOB_DTYPE.itemsize == 24
 
 
 class PanelDesc(C.Structure):
@@ -74,6 +75,10 @@ SYMBOLS = [
     ("smx_align", C.c_int, [C.c_char_p, C.c_int, C.c_char_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int),
                             C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_int)]),
     ("smx_align_batch", C.c_int, [_P, _P, C.c_uint32, _P, _P, _P, _P, _P, C.c_uint32, _P, _P, _P, _P, C.c_uint32]),
+    ("smx_mine_distances", C.c_int, [C.c_char_p, _P, C.c_uint32, _P, C.c_char_p, _P, C.c_uint32, _P, C.c_uint32, _P,
+                                     C.POINTER(C.c_float)]),
+    ("smx_mine_best_identity", C.c_int, [C.c_char_p, _P, C.c_uint32, _P, C.c_char_p, _P, C.c_uint32, _P, C.c_uint32, _P,
+                                         C.POINTER(C.c_float)]),
     ("smx_comm_unique_id", C.c_int, [_P]),
     ("smx_comm_init", C.c_int, [_P, C.c_int, C.c_int, C.POINTER(_P)]),
     ("smx_counts_allreduce", C.c_int, [_P, C.c_size_t, _P, _P]),

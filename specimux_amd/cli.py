@@ -109,5 +109,11 @@ def main(argv=None):
         orchestration.specimux(args)
 
 
+def specimine_main(argv=None):
+    """Entry point of the specimine tool (reference cli.py:113-116); also `python -m specimux_amd.specimine`."""
+    from . import specimine
+    specimine.main(argv)
+
+
 if __name__ == "__main__":
     main()

@@ -946,6 +946,167 @@ int smx_align_batch(const char *queries, const uint32_t *qoff, uint32_t n_querie
     return SMX_OK;
 }
 
+// ---- specimine: batched long-read HW distances (smx_mine.hip); grow-only device workspace, calls serialised
+namespace {
+std::mutex g_mine_mutex;
+DevBuf g_mine_ws[9];
+
+// the work of one smx_mine_* call up to the distances, left on the device in g_mine_ws[6]
+int mine_run(const char *queries, const uint64_t *qoff, uint32_t n_queries, const int32_t *k, const char *targets,
+             const uint64_t *toff, uint32_t n_targets, const smx_mine_job *jobs, uint32_t n_jobs,
+             std::vector<smx::MineJobDev> *djobs, uint64_t *n_pairs, float *kernel_ms) {
+    if (!queries || !qoff || !k || !targets || !toff || (n_jobs && !jobs)) return fail(SMX_ERR_ARG, "null argument");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(SMX_ERR_DEVICE, "libsmx has no CPU path: no HIP device");
+    // per query: words, distinct bytes -> LDS bytes of its Peq table; register class of its per-lane state
+    std::vector<size_t> qlds(n_queries);
+    std::vector<int> qclass(n_queries);
+    for (uint32_t q = 0; q < n_queries; q++) {
+        if (qoff[q + 1] <= qoff[q]) return fail(SMX_ERR_ARG, "query %u is empty", q);
+        const uint64_t m = qoff[q + 1] - qoff[q];
+        if (m > (uint64_t)INT32_MAX) return fail(SMX_ERR_UNSUPPORTED, "query %u: length %llu", q, (unsigned long long)m);
+        bool seen[256] = {false};
+        int rows = 0;
+        for (uint64_t i = qoff[q]; i < qoff[q + 1]; i++) {
+            const unsigned char c = (unsigned char)queries[i];
+            if (!seen[c]) { seen[c] = true; rows++; }
+        }
+        const size_t W = (size_t)((m + 63) / 64), Wp = W | 1;
+        qlds[q] = (MINE_LDS_HEAD + (size_t)(rows + 1) * Wp) * 8;
+        if (qlds[q] > SMX_LDS_POOL)
+            return fail(SMX_ERR_UNSUPPORTED, "query %u: %d distinct bytes x %zu words do not fit the LDS (%zu > %zu bytes)", q,
+                        rows, W, qlds[q], (size_t)SMX_LDS_POOL);
+        qclass[q] = W <= 1 ? 1 : W <= 2 ? 2 : W <= 4 ? 3 : W <= 8 ? 4 : W <= 16 ? 5 : 0;
+    }
+    // targets: 16-byte aligned copies, 16 bytes of slack at the end (the kernel loads 16 bytes at a time)
+    std::vector<uint64_t> tdoff(n_targets);
+    std::vector<int32_t> tlen(n_targets);
+    uint64_t tbytes = 0;
+    for (uint32_t t = 0; t < n_targets; t++) {
+        if (toff[t + 1] < toff[t] || toff[t + 1] - toff[t] > (uint64_t)INT32_MAX) return fail(SMX_ERR_ARG, "target %u: bad offsets", t);
+        tdoff[t] = tbytes;
+        tlen[t] = (int32_t)(toff[t + 1] - toff[t]);
+        tbytes += ((uint64_t)tlen[t] + 15) & ~(uint64_t)15;
+    }
+    tbytes += 16;
+    std::vector<unsigned char> tpad(tbytes, 0);
+    for (uint32_t t = 0; t < n_targets; t++) memcpy(&tpad[tdoff[t]], targets + toff[t], (size_t)tlen[t]);
+    // jobs -> work items (one query x up to MINE_THREADS targets), grouped by register class
+    std::vector<smx::MineItem> items[6];
+    size_t lds_max[6] = {0, 0, 0, 0, 0, 0};
+    int words_max0 = 0;
+    djobs->resize(n_jobs);
+    uint64_t dist_off = 0, best_off = 0;
+    for (uint32_t j = 0; j < n_jobs; j++) {
+        const smx_mine_job &J = jobs[j];
+        if ((uint64_t)J.q0 + J.nq > n_queries || (uint64_t)J.t0 + J.nt > n_targets)
+            return fail(SMX_ERR_ARG, "job %u: query or target range out of bounds", j);
+        (*djobs)[j] = smx::MineJobDev{J.q0, J.nq, J.t0, J.nt, dist_off, best_off, J.min_identity};
+        for (uint32_t i = 0; i < J.nq; i++) {
+            const uint32_t q = J.q0 + i;
+            const int c = qclass[q];
+            lds_max[c] = std::max(lds_max[c], qlds[q]);
+            if (c == 0) words_max0 = std::max(words_max0, (int)((qoff[q + 1] - qoff[q] + 63) / 64));
+            for (uint32_t t = 0; t < J.nt; t += MINE_THREADS)
+                items[c].push_back(smx::MineItem{q, J.t0 + t, std::min<uint32_t>(MINE_THREADS, J.nt - t), k[q],
+                                                 dist_off + (uint64_t)i * J.nt + t});
+        }
+        dist_off += (uint64_t)J.nq * J.nt;
+        best_off += J.nt;
+    }
+    *n_pairs = dist_off;
+    // the generic class keeps its per-lane state in a global slice per workgroup: bound the grid to ~256 MiB of it
+    const size_t slice = (size_t)3 * words_max0 * MINE_THREADS * 8;
+    const int grid0 = (int)std::min<size_t>(std::max<size_t>(items[0].size(), 1),
+                                            std::max<size_t>(1, ((size_t)256 << 20) / std::max<size_t>(slice, 1)));
+    size_t nitems = 0;
+    for (int c = 0; c < 6; c++) nitems += items[c].size();
+    DevBuf *B = g_mine_ws;
+    const size_t sz[8] = {(size_t)qoff[n_queries], ((size_t)n_queries + 1) * 8, (size_t)tbytes, (size_t)n_targets * 8,
+                          (size_t)n_targets * 4, nitems * sizeof(smx::MineItem), (size_t)dist_off * 4,
+                          items[0].empty() ? 0 : (size_t)grid0 * slice};
+    for (int b = 0; b < 8; b++) HIP_TRY(B[b].ensure(std::max<size_t>(sz[b], 16)));
+    HIP_TRY(hipMemcpy(B[0].p, queries, sz[0], hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(B[1].p, qoff, sz[1], hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(B[2].p, tpad.data(), sz[2], hipMemcpyHostToDevice));
+    if (n_targets) {
+        HIP_TRY(hipMemcpy(B[3].p, tdoff.data(), sz[3], hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(B[4].p, tlen.data(), sz[4], hipMemcpyHostToDevice));
+    }
+    size_t at = 0;
+    for (int c = 0; c < 6; c++) {
+        if (!items[c].empty())
+            HIP_TRY(hipMemcpy((char *)B[5].p + at * sizeof(smx::MineItem), items[c].data(), items[c].size() * sizeof(smx::MineItem),
+                              hipMemcpyHostToDevice));
+        at += items[c].size();
+    }
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    if (kernel_ms) {
+        HIP_TRY(hipEventCreate(&ev[0]));
+        HIP_TRY(hipEventCreate(&ev[1]));
+        HIP_TRY(hipEventRecord(ev[0], nullptr));
+    }
+    static const int kWords[6] = {0, 1, 2, 4, 8, 16};
+    at = 0;
+    int e = 0;
+    for (int c = 0; c < 6 && e == 0; c++) {
+        const uint32_t n = (uint32_t)items[c].size();
+        if (n)
+            e = smx_launch_mine(nullptr, kWords[c], (const unsigned char *)B[0].p, (const uint64_t *)B[1].p,
+                                (const unsigned char *)B[2].p, (const uint64_t *)B[3].p, (const int32_t *)B[4].p,
+                                (const char *)B[5].p + at * sizeof(smx::MineItem), n, c == 0 ? grid0 : (int)n, lds_max[c],
+                                (int32_t *)B[6].p, (unsigned long long *)B[7].p, words_max0);
+        at += n;
+    }
+    if (e != 0) return fail(SMX_ERR_DEVICE, "mining kernel launch failed: %s", hipGetErrorString((hipError_t)e));
+    if (kernel_ms) {
+        HIP_TRY(hipEventRecord(ev[1], nullptr));
+        HIP_TRY(hipEventSynchronize(ev[1]));
+        HIP_TRY(hipEventElapsedTime(kernel_ms, ev[0], ev[1]));
+        (void)hipEventDestroy(ev[0]);
+        (void)hipEventDestroy(ev[1]);
+    }
+    HIP_TRY(hipDeviceSynchronize());
+    return SMX_OK;
+}
+}  // namespace
+
+int smx_mine_distances(const char *queries, const uint64_t *qoff, uint32_t n_queries, const int32_t *k, const char *targets,
+                       const uint64_t *toff, uint32_t n_targets, const smx_mine_job *jobs, uint32_t n_jobs, int32_t *dist,
+                       float *kernel_ms) {
+    if (!dist && n_jobs) return fail(SMX_ERR_ARG, "null argument");
+    std::lock_guard<std::mutex> guard(g_mine_mutex);
+    std::vector<smx::MineJobDev> djobs;
+    uint64_t n_pairs = 0;
+    int rc = mine_run(queries, qoff, n_queries, k, targets, toff, n_targets, jobs, n_jobs, &djobs, &n_pairs, kernel_ms);
+    if (rc != SMX_OK) return rc;
+    if (n_pairs) HIP_TRY(hipMemcpy(dist, g_mine_ws[6].p, n_pairs * 4, hipMemcpyDeviceToHost));
+    return SMX_OK;
+}
+
+int smx_mine_best_identity(const char *queries, const uint64_t *qoff, uint32_t n_queries, const int32_t *k,
+                           const char *targets, const uint64_t *toff, uint32_t n_targets, const smx_mine_job *jobs,
+                           uint32_t n_jobs, double *best, float *kernel_ms) {
+    if (!best && n_jobs) return fail(SMX_ERR_ARG, "null argument");
+    std::lock_guard<std::mutex> guard(g_mine_mutex);
+    std::vector<smx::MineJobDev> djobs;
+    uint64_t n_pairs = 0;
+    int rc = mine_run(queries, qoff, n_queries, k, targets, toff, n_targets, jobs, n_jobs, &djobs, &n_pairs, kernel_ms);
+    if (rc != SMX_OK) return rc;
+    uint64_t n_out = 0;
+    for (uint32_t j = 0; j < n_jobs; j++) n_out += jobs[j].nt;
+    if (n_out == 0) return SMX_OK;
+    DevBuf *B = g_mine_ws;
+    HIP_TRY(B[8].ensure(n_jobs * sizeof(smx::MineJobDev) + n_out * 8));
+    HIP_TRY(hipMemcpy(B[8].p, djobs.data(), n_jobs * sizeof(smx::MineJobDev), hipMemcpyHostToDevice));
+    double *d_best = (double *)((char *)B[8].p + n_jobs * sizeof(smx::MineJobDev));
+    int e = smx_launch_mine_best(nullptr, B[8].p, n_jobs, (const uint64_t *)B[1].p, (const int32_t *)B[6].p, d_best, n_out);
+    if (e != 0) return fail(SMX_ERR_DEVICE, "identity reduction launch failed: %s", hipGetErrorString((hipError_t)e));
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(best, d_best, n_out * 8, hipMemcpyDeviceToHost));
+    return SMX_OK;
+}
+
 // ---- lanes: asynchronous host-buffer path (pinned staging, one stream per lane)
 struct smx_lane {
     smx_panel *P = nullptr;

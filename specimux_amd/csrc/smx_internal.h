@@ -67,6 +67,24 @@ struct DemuxAux {
     const uint8_t *naflag;   // prescan: per read, 1 = a window holds something other than upper-case ACGT (ASCII path for that read)
 };
 
+// specimine (smx_mine.hip): one query x up to MINE_THREADS targets per work item, one target per lane
+#define MINE_THREADS 128
+#define MINE_LDS_HEAD 192   // u64 words before the Peq table: byte -> row map (512 B) + byte presence flags (1 KiB)
+
+struct MineItem {
+    uint32_t q;       // query index
+    uint32_t t0;      // first target index
+    uint32_t nt;      // targets (lanes) of this item, 1..MINE_THREADS
+    int32_t k;        // max distance (< 0: none)
+    uint64_t out;     // dist index of (q, t0); lane i writes out + i
+};
+
+struct MineJobDev {   // one smx_mine_job with its output offsets
+    uint32_t q0, nq, t0, nt;
+    uint64_t dist_off, best_off;
+    double min_identity;
+};
+
 }  // namespace smx
 
 extern "C" {
@@ -95,5 +113,11 @@ int smx_launch_align_batch(void *stream, const unsigned long long *d_qpeq, const
                            const unsigned char *d_tcodes, const unsigned long long *d_toff, const int *d_k,
                            const unsigned char *d_modes, unsigned n, unsigned char *d_ws, int *d_dist, int *d_nloc,
                            int *d_starts, int *d_ends, unsigned cap);
+// specimine (smx_mine.hip); wr = register words per lane (1, 2, 4, 8, 16) or 0 = state in d_scratch
+int smx_launch_mine(void *stream, int wr, const unsigned char *d_q, const uint64_t *d_qoff, const unsigned char *d_t,
+                    const uint64_t *d_toff, const int32_t *d_tlen, const void *d_items, uint32_t n_items, int grid,
+                    size_t lds_bytes, int32_t *d_dist, unsigned long long *d_scratch, int scratch_words);
+int smx_launch_mine_best(void *stream, const void *d_jobs, uint32_t n_jobs, const uint64_t *d_qoff, const int32_t *d_dist,
+                         double *d_best, uint64_t n_out);
 }
 #endif

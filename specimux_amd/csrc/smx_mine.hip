@@ -1,0 +1,246 @@
+// smx_mine.hip -- the specimine hot path: batched HW (infix) edit distances of long reads, distance only.
+//
+// One work item = one query (a full read) x up to MINE_THREADS targets (partial reads), one target per lane.
+// The workgroup builds the query's Peq once in LDS from a byte -> row map (row 0 = bytes absent from the query,
+// all zero), then every lane runs the multi-word Myers/Hyyro bit-vector over its own target, one column per
+// target byte, with an edlib-style block band ("specimine"):
+//   * blocks 0..L hold the column's state; a block is dropped from the bottom once its bottom score is >= k + 64
+//     (every cell of it is then > k), and block L+1 joins a column only if the bottom cell of L was <= k one column
+//     earlier (diagonals never decrease, so no cell deeper than that can reach <= k).  A block that joins starts
+//     from the +1-per-row column, an upper bound of the true one; cells <= k are still exact.
+//   * once a column's last-row score v <= k is found, k tightens to v (only the minimum is wanted).
+// Matching is exact byte equality: no IUPAC equalities here (unlike the demux kernels).
+//
+// The per-lane state of a query of W <= WR words lives in registers (fully unrolled over WR, every index static);
+// longer queries keep it in a global scratch slice per workgroup ([word][lane], coalesced).
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "smx_internal.h"
+
+namespace smx {
+
+typedef unsigned long long u64;
+
+// Hyyro's block step with a horizontal carry in and out (hin, hout in {-1, 0, +1}).
+__device__ __forceinline__ int mine_step(u64 Eq, u64 &Pv, u64 &Mv, int hin) {
+    const u64 hneg = hin < 0 ? 1ull : 0ull, hpos = hin > 0 ? 1ull : 0ull;
+    const u64 Xv = Eq | Mv;
+    Eq |= hneg;
+    const u64 Xh = (((Eq & Pv) + Pv) ^ Pv) | Eq;
+    u64 Ph = Mv | ~(Xh | Pv);
+    u64 Mh = Pv & Xh;
+    const int hout = (int)(Ph >> 63) - (int)(Mh >> 63);
+    Ph = (Ph << 1) | hpos;
+    Mh = (Mh << 1) | hneg;
+    Pv = Mh | ~(Xv | Ph);
+    Mv = Ph & Xv;
+    return hout;
+}
+
+// score of the last real row (local row r of the last block) from the block's bottom score
+__device__ __forceinline__ int mine_last_row(u64 Pv, u64 Mv, int bottom, int r) {
+    if (r == 63) return bottom;
+    return bottom - (__popcll(Pv >> (r + 1)) - __popcll(Mv >> (r + 1)));
+}
+
+template <int WR> struct RegState {
+    u64 P[WR > 0 ? WR : 1], M[WR > 0 ? WR : 1];
+    int S[WR > 0 ? WR : 1];
+    __device__ __forceinline__ u64 &p(int w) { return P[w]; }
+    __device__ __forceinline__ u64 &m(int w) { return M[w]; }
+    __device__ __forceinline__ int &s(int w) { return S[w]; }
+};
+
+struct GlobalState {   // pointers already offset to this lane; element w at [w * MINE_THREADS]
+    u64 *P, *M;
+    int *S;
+    __device__ __forceinline__ u64 &p(int w) { return P[(size_t)w * MINE_THREADS]; }
+    __device__ __forceinline__ u64 &m(int w) { return M[(size_t)w * MINE_THREADS]; }
+    __device__ __forceinline__ int &s(int w) { return S[(size_t)w * MINE_THREADS]; }
+};
+
+// One pair: HW distance of the query (Peq in LDS, W words, padded row stride Wp) in target t[0..n).
+// Returns -1 if the distance exceeds k (k < 0: no limit).
+template <int WR, typename State>
+__device__ int mine_pair(State &st, const u64 *peq, const unsigned short *rowmap, int m, int W, int Wp, int k,
+                         const unsigned char *t, int n) {
+    if (n == 0) return m;                          // edlib: an empty target costs the whole query, whatever k is
+    if (k >= 0 && n < m - k) return -1;            // an infix needs at least m - k target bytes
+    int kk = (k < 0 || k > m) ? m : k;
+    const int last = W - 1, rlast = (m - 1) - 64 * last;
+    int L = min(last, kk / 64);
+    const int wend = WR > 0 ? WR : W;
+    constexpr int kUnroll = WR > 0 ? WR : 1;     // the register variants unroll fully (static indices)
+#pragma unroll kUnroll
+    for (int w = 0; w < wend; w++) {               // column 0: D[i][0] = i
+        st.p(w) = ~0ull;
+        st.m(w) = 0ull;
+        st.s(w) = 64 * (w + 1);
+    }
+    int best = -1;
+    const uint4 *t16 = reinterpret_cast<const uint4 *>(t);
+    uint4 chunk = make_uint4(0, 0, 0, 0);
+    for (int j = 0; j < n; j++) {
+        if ((j & 15) == 0) chunk = t16[j >> 4];    // 16 target bytes per load (targets are 16-byte aligned, padded)
+        const int jj = j & 15;
+        const unsigned word = jj < 4 ? chunk.x : jj < 8 ? chunk.y : jj < 12 ? chunk.z : chunk.w;
+        const u64 *eqrow = peq + (size_t)rowmap[(word >> (8 * (jj & 3))) & 0xffu] * Wp;
+        int h = 0, nl = 0, sprev = 0;
+        bool ext = false;
+#pragma unroll kUnroll
+        for (int w = 0; w < wend; w++) {
+            if (w > L + 1 || w > last) break;
+            if (w == L + 1) {                       // band extension: only if the bottom of L was <= k last column
+                if (!ext) break;
+                st.p(w) = ~0ull;
+                st.m(w) = 0ull;
+                st.s(w) = sprev + 64;
+            }
+            u64 Pv = st.p(w), Mv = st.m(w);
+            const int sp = st.s(w);
+            h = mine_step(eqrow[w], Pv, Mv, h);
+            st.p(w) = Pv;
+            st.m(w) = Mv;
+            st.s(w) = sp + h;
+            if (w == L) { sprev = sp; ext = sp <= kk; }
+            if (sp + h < kk + 64) nl = w;          // the deepest block that may hold a cell <= k
+            if (w == last) {
+                const int v = mine_last_row(Pv, Mv, sp + h, rlast);
+                if (v <= kk) { best = v; kk = v; }
+            }
+        }
+        L = nl;
+    }
+    return best;
+}
+
+// Peq of query q into LDS: rowmap[256] (byte -> row, 0 = absent), peq[(nrows + 1) * Wp] words.
+__device__ void mine_build_peq(const unsigned char *qs, int m, int W, int Wp, u64 *peq, unsigned short *rowmap,
+                               unsigned *present) {
+    const int tid = threadIdx.x;
+    for (int c = tid; c < 256; c += MINE_THREADS) present[c] = 0;
+    __syncthreads();
+    for (int i = tid; i < m; i += MINE_THREADS) present[qs[i]] = 1;
+    __syncthreads();
+    // rows 1..nrows in byte order; every wave computes the same prefix, wave 0 writes it
+    const int lane = tid & 63;
+    int base = 1;
+    for (int c0 = 0; c0 < 256; c0 += 64) {
+        const unsigned pr = present[c0 + lane];
+        const u64 bal = __ballot(pr != 0);
+        const int rank = __popcll(bal & ((1ull << lane) - 1ull));
+        if (tid < 64) rowmap[c0 + lane] = pr ? (unsigned short)(base + rank) : (unsigned short)0;
+        base += __popcll(bal);
+    }
+    const int words = base * Wp;                   // base = nrows + 1
+    for (int i = tid; i < words; i += MINE_THREADS) peq[i] = 0ull;
+    __syncthreads();
+    for (int i = tid; i < m; i += MINE_THREADS) atomicOr(&peq[(size_t)rowmap[qs[i]] * Wp + (i >> 6)], 1ull << (i & 63));
+    __syncthreads();
+}
+
+template <int WR>
+__global__ __launch_bounds__(MINE_THREADS) void mine_kernel(const unsigned char *__restrict__ qbytes,
+                                                            const uint64_t *__restrict__ qoff,
+                                                            const unsigned char *__restrict__ tbytes,
+                                                            const uint64_t *__restrict__ toff,
+                                                            const int32_t *__restrict__ tlen,
+                                                            const MineItem *__restrict__ items, uint32_t n_items,
+                                                            int32_t *__restrict__ dist, u64 *scratch, int scratch_words) {
+    extern __shared__ u64 lds[];
+    unsigned short *rowmap = reinterpret_cast<unsigned short *>(lds);     // 512 B
+    unsigned *present = reinterpret_cast<unsigned *>(lds + 64);           // 1 KiB
+    u64 *peq = lds + MINE_LDS_HEAD;
+    for (uint32_t it = blockIdx.x; it < n_items; it += gridDim.x) {
+        const MineItem I = items[it];
+        const uint64_t q0 = qoff[I.q];
+        const int m = (int)(qoff[I.q + 1] - q0);
+        const int W = (m + 63) >> 6, Wp = W | 1;
+        __syncthreads();                           // the previous item's lanes are done with the table
+        mine_build_peq(qbytes + q0, m, W, Wp, peq, rowmap, present);
+        const unsigned lane = threadIdx.x;
+        if (lane < I.nt) {
+            const uint32_t ti = I.t0 + lane;
+            int d;
+            if constexpr (WR > 0) {
+                RegState<WR> st;
+                d = mine_pair<WR>(st, peq, rowmap, m, W, Wp, I.k, tbytes + toff[ti], tlen[ti]);
+            } else {
+                u64 *base = scratch + (size_t)blockIdx.x * 3 * scratch_words * MINE_THREADS;
+                GlobalState st{base + lane, base + (size_t)scratch_words * MINE_THREADS + lane,
+                               reinterpret_cast<int *>(base + (size_t)2 * scratch_words * MINE_THREADS) + lane};
+                d = mine_pair<0>(st, peq, rowmap, m, W, Wp, I.k, tbytes + toff[ti], tlen[ti]);
+            }
+            dist[I.out + lane] = d;
+        }
+    }
+}
+
+// best identity per (job, target): max over the job's queries of 1 - d / m among d != -1, identity >= min_identity
+// and identity > 0 (the reference's loop: best starts at 0 and only grows), in IEEE double.
+__global__ void mine_best_kernel(const MineJobDev *__restrict__ jobs, uint32_t n_jobs, const uint64_t *__restrict__ qoff,
+                                 const int32_t *__restrict__ dist, double *__restrict__ best, uint64_t n_out) {
+    const uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= n_out) return;
+    uint32_t lo = 0, hi = n_jobs;                  // the job whose [best_off, best_off + nt) holds g
+    while (hi - lo > 1) {
+        const uint32_t mid = (lo + hi) / 2;
+        if (jobs[mid].best_off <= g) lo = mid; else hi = mid;
+    }
+    const MineJobDev J = jobs[lo];
+    const uint32_t t = (uint32_t)(g - J.best_off);
+    double b = 0.0;
+    for (uint32_t i = 0; i < J.nq; i++) {
+        const int d = dist[J.dist_off + (uint64_t)i * J.nt + t];
+        if (d == -1) continue;
+        const double m = (double)(qoff[J.q0 + i + 1] - qoff[J.q0 + i]);
+        const double identity = 1.0 - (double)d / m;
+        if (identity >= J.min_identity && identity > b) b = identity;
+    }
+    best[g] = b;
+}
+
+}  // namespace smx
+
+extern "C" int smx_launch_mine(void *stream, int wr, const unsigned char *d_q, const uint64_t *d_qoff,
+                               const unsigned char *d_t, const uint64_t *d_toff, const int32_t *d_tlen,
+                               const void *d_items, uint32_t n_items, int grid, size_t lds_bytes, int32_t *d_dist,
+                               unsigned long long *d_scratch, int scratch_words) {
+    using namespace smx;
+    const void *fn;
+    switch (wr) {
+        case 1: fn = (const void *)mine_kernel<1>; break;
+        case 2: fn = (const void *)mine_kernel<2>; break;
+        case 4: fn = (const void *)mine_kernel<4>; break;
+        case 8: fn = (const void *)mine_kernel<8>; break;
+        case 16: fn = (const void *)mine_kernel<16>; break;
+        case 0: fn = (const void *)mine_kernel<0>; break;
+        default: return (int)hipErrorInvalidValue;
+    }
+    if (lds_bytes > 65536) {
+        hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+        if (e != hipSuccess) return (int)e;
+    }
+    const MineItem *items = (const MineItem *)d_items;
+    hipStream_t s = (hipStream_t)stream;
+    switch (wr) {
+        case 1: hipLaunchKernelGGL(mine_kernel<1>, dim3(grid), dim3(MINE_THREADS), lds_bytes, s, d_q, d_qoff, d_t, d_toff, d_tlen, items, n_items, d_dist, d_scratch, scratch_words); break;
+        case 2: hipLaunchKernelGGL(mine_kernel<2>, dim3(grid), dim3(MINE_THREADS), lds_bytes, s, d_q, d_qoff, d_t, d_toff, d_tlen, items, n_items, d_dist, d_scratch, scratch_words); break;
+        case 4: hipLaunchKernelGGL(mine_kernel<4>, dim3(grid), dim3(MINE_THREADS), lds_bytes, s, d_q, d_qoff, d_t, d_toff, d_tlen, items, n_items, d_dist, d_scratch, scratch_words); break;
+        case 8: hipLaunchKernelGGL(mine_kernel<8>, dim3(grid), dim3(MINE_THREADS), lds_bytes, s, d_q, d_qoff, d_t, d_toff, d_tlen, items, n_items, d_dist, d_scratch, scratch_words); break;
+        case 16: hipLaunchKernelGGL(mine_kernel<16>, dim3(grid), dim3(MINE_THREADS), lds_bytes, s, d_q, d_qoff, d_t, d_toff, d_tlen, items, n_items, d_dist, d_scratch, scratch_words); break;
+        default: hipLaunchKernelGGL(mine_kernel<0>, dim3(grid), dim3(MINE_THREADS), lds_bytes, s, d_q, d_qoff, d_t, d_toff, d_tlen, items, n_items, d_dist, d_scratch, scratch_words); break;
+    }
+    return (int)hipGetLastError();
+}
+
+extern "C" int smx_launch_mine_best(void *stream, const void *d_jobs, uint32_t n_jobs, const uint64_t *d_qoff,
+                                    const int32_t *d_dist, double *d_best, uint64_t n_out) {
+    if (n_out == 0) return 0;
+    const unsigned threads = 256;
+    const unsigned grid = (unsigned)((n_out + threads - 1) / threads);
+    hipLaunchKernelGGL(smx::mine_best_kernel, dim3(grid), dim3(threads), 0, (hipStream_t)stream,
+                       (const smx::MineJobDev *)d_jobs, n_jobs, d_qoff, d_dist, d_best, n_out);
+    return (int)hipGetLastError();
+}

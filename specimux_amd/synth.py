@@ -357,3 +357,59 @@ def _make_chunk(panel: Panel, n, rng, search_len=80, error_rate=0.06, insert_mea
             quals.append((rng.integers(3, 41, len(s)) + 33).astype(np.uint8).tobytes().decode())
         rs.reads, rs.quals = reads, quals
     return rs
+
+
+# ---- specimine workloads: a demultiplexed output tree (full/ and partial/) of synthetic specimens
+def _mutate(rng, s, rate):
+    out = []
+    for ch in s:
+        r = rng.random()
+        if r < rate * 0.4:
+            out.append("ACGT"[rng.integers(4)])          # substitution
+        elif r < rate * 0.7:
+            out.append(ch + "ACGT"[rng.integers(4)])     # insertion
+        elif r < rate:
+            continue                                     # deletion
+        else:
+            out.append(ch)
+    return "".join(out)
+
+
+def write_mine_tree(root, n_specimens=4, n_full=6, n_partial=10, length=650, seed=0, pairs=("P1-P2",),
+                    pool="POOL", partial_error=(0.0, 0.25), decoy_fraction=0.3):
+    """A specimux output tree under `root` for specimine: specimens.txt, full/<pool>/<specimen>.fastq (and the same at
+    full/<pool>/<pair>/), partial/<pool>/<pair>/barcode_{fwd,rev}_<barcode>.fastq.  Per specimen one random insert of
+    ~`length` nt; full reads are copies with 2 % errors, partial reads copies with a per-read error rate drawn from
+    `partial_error` or unrelated decoys; lengths vary by about +-10 %.  Returns the specimen ids."""
+    rng = np.random.default_rng(seed)
+    fwd, rev = make_barcodes(n_specimens, n_specimens, seed=seed)
+    ids = [f"S{i:03d}" for i in range(n_specimens)]
+
+    def fastq(path, seqs, tag):
+        os.makedirs(os.path.dirname(path), exist_ok=True)
+        with open(path, "w") as fh:
+            for j, s in enumerate(seqs):
+                fh.write(f"@{tag}_{j} some description {j}\n{s}\n+\n{'I' * len(s)}\n")
+
+    with open(os.path.join(root, "specimens.txt"), "w") as fh:
+        fh.write("SampleID\tPrimerPool\tFwIndex\tFwPrimer\tRvIndex\tRvPrimer\n")
+        for i, sid in enumerate(ids):
+            fh.write(f"{sid}\t{pool}\t{fwd[i]}\tP1\t{rev[i]}\tP2\n")
+    for i, sid in enumerate(ids):
+        n = max(1, int(rng.normal(length, length * 0.05)))
+        insert = "".join("ACGT"[c] for c in rng.integers(0, 4, n))
+        fulls = [_mutate(rng, insert, 0.02) for _ in range(n_full)]
+        fastq(os.path.join(root, "full", pool, f"{sid}.fastq"), fulls, f"{sid}_full")
+        for pair in pairs:
+            fastq(os.path.join(root, "full", pool, pair, f"{sid}.fastq"), fulls, f"{sid}_full")
+            for kind, bc in (("fwd", fwd[i]), ("rev", rev[i])):
+                parts = []
+                for _ in range(n_partial):
+                    if rng.random() < decoy_fraction:
+                        m = max(1, int(rng.normal(length, length * 0.1)))
+                        parts.append("".join("ACGT"[c] for c in rng.integers(0, 4, m)))
+                    else:
+                        lo, hi = partial_error
+                        parts.append(_mutate(rng, insert, rng.uniform(lo, hi)))
+                fastq(os.path.join(root, "partial", pool, pair, f"barcode_{kind}_{bc}.fastq"), parts, f"{sid}_{pair}_{kind}")
+    return ids
