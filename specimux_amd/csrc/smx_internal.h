@@ -5,6 +5,7 @@
 #include <stdint.h>
 #include "smx.h"
 #include "smx_prescan_core.h"
+#include "smx_mine_core.h"
 
 // LDS a CU of gfx950 gives to workgroups (in 512-byte granules): measured, tools/ubench/lds_residency.hip
 #define SMX_LDS_POOL ((size_t)159744)
@@ -67,8 +68,7 @@ struct DemuxAux {
     const uint8_t *naflag;   // prescan: per read, 1 = a window holds something other than upper-case ACGT (ASCII path for that read)
 };
 
-// specimine (smx_mine.hip): one query x up to MINE_THREADS targets per work item, one target per lane
-#define MINE_THREADS 128
+// specimine (smx_mine.hip): one query x up to MINE_THREADS (smx_mine_core.h) targets per work item, one target per lane
 #define MINE_LDS_HEAD 192   // u64 words before the Peq table: byte -> row map (512 B) + byte presence flags (1 KiB)
 
 struct MineItem {

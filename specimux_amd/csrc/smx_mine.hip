@@ -2,13 +2,8 @@
 //
 // One work item = one query (a full read) x up to MINE_THREADS targets (partial reads), one target per lane.
 // The workgroup builds the query's Peq once in LDS from a byte -> row map (row 0 = bytes absent from the query,
-// all zero), then every lane runs the multi-word Myers/Hyyro bit-vector over its own target, one column per
-// target byte, with an edlib-style block band ("specimine"):
-//   * blocks 0..L hold the column's state; a block is dropped from the bottom once its bottom score is >= k + 64
-//     (every cell of it is then > k), and block L+1 joins a column only if the bottom cell of L was <= k one column
-//     earlier (diagonals never decrease, so no cell deeper than that can reach <= k).  A block that joins starts
-//     from the +1-per-row column, an upper bound of the true one; cells <= k are still exact.
-//   * once a column's last-row score v <= k is found, k tightens to v (only the minimum is wanted).
+// all zero), then every lane runs mine_pair (smx_mine_core.h: the multi-word Myers/Hyyro bit-vector with an
+// edlib-style block band, host/device code shared with the CPU unit test) over its own target.
 // Matching is exact byte equality: no IUPAC equalities here (unlike the demux kernels).
 //
 // The per-lane state of a query of W <= WR words lives in registers (fully unrolled over WR, every index static);
@@ -17,103 +12,9 @@
 #include <stdint.h>
 
 #include "smx_internal.h"
+#include "smx_mine_core.h"
 
 namespace smx {
-
-typedef unsigned long long u64;
-
-// Hyyro's block step with a horizontal carry in and out (hin, hout in {-1, 0, +1}).
-__device__ __forceinline__ int mine_step(u64 Eq, u64 &Pv, u64 &Mv, int hin) {
-    const u64 hneg = hin < 0 ? 1ull : 0ull, hpos = hin > 0 ? 1ull : 0ull;
-    const u64 Xv = Eq | Mv;
-    Eq |= hneg;
-    const u64 Xh = (((Eq & Pv) + Pv) ^ Pv) | Eq;
-    u64 Ph = Mv | ~(Xh | Pv);
-    u64 Mh = Pv & Xh;
-    const int hout = (int)(Ph >> 63) - (int)(Mh >> 63);
-    Ph = (Ph << 1) | hpos;
-    Mh = (Mh << 1) | hneg;
-    Pv = Mh | ~(Xv | Ph);
-    Mv = Ph & Xv;
-    return hout;
-}
-
-// score of the last real row (local row r of the last block) from the block's bottom score
-__device__ __forceinline__ int mine_last_row(u64 Pv, u64 Mv, int bottom, int r) {
-    if (r == 63) return bottom;
-    return bottom - (__popcll(Pv >> (r + 1)) - __popcll(Mv >> (r + 1)));
-}
-
-template <int WR> struct RegState {
-    u64 P[WR > 0 ? WR : 1], M[WR > 0 ? WR : 1];
-    int S[WR > 0 ? WR : 1];
-    __device__ __forceinline__ u64 &p(int w) { return P[w]; }
-    __device__ __forceinline__ u64 &m(int w) { return M[w]; }
-    __device__ __forceinline__ int &s(int w) { return S[w]; }
-};
-
-struct GlobalState {   // pointers already offset to this lane; element w at [w * MINE_THREADS]
-    u64 *P, *M;
-    int *S;
-    __device__ __forceinline__ u64 &p(int w) { return P[(size_t)w * MINE_THREADS]; }
-    __device__ __forceinline__ u64 &m(int w) { return M[(size_t)w * MINE_THREADS]; }
-    __device__ __forceinline__ int &s(int w) { return S[(size_t)w * MINE_THREADS]; }
-};
-
-// One pair: HW distance of the query (Peq in LDS, W words, padded row stride Wp) in target t[0..n).
-// Returns -1 if the distance exceeds k (k < 0: no limit).
-template <int WR, typename State>
-__device__ int mine_pair(State &st, const u64 *peq, const unsigned short *rowmap, int m, int W, int Wp, int k,
-                         const unsigned char *t, int n) {
-    if (n == 0) return m;                          // edlib: an empty target costs the whole query, whatever k is
-    if (k >= 0 && n < m - k) return -1;            // an infix needs at least m - k target bytes
-    int kk = (k < 0 || k > m) ? m : k;
-    const int last = W - 1, rlast = (m - 1) - 64 * last;
-    int L = min(last, kk / 64);
-    const int wend = WR > 0 ? WR : W;
-    constexpr int kUnroll = WR > 0 ? WR : 1;     // the register variants unroll fully (static indices)
-#pragma unroll kUnroll
-    for (int w = 0; w < wend; w++) {               // column 0: D[i][0] = i
-        st.p(w) = ~0ull;
-        st.m(w) = 0ull;
-        st.s(w) = 64 * (w + 1);
-    }
-    int best = -1;
-    const uint4 *t16 = reinterpret_cast<const uint4 *>(t);
-    uint4 chunk = make_uint4(0, 0, 0, 0);
-    for (int j = 0; j < n; j++) {
-        if ((j & 15) == 0) chunk = t16[j >> 4];    // 16 target bytes per load (targets are 16-byte aligned, padded)
-        const int jj = j & 15;
-        const unsigned word = jj < 4 ? chunk.x : jj < 8 ? chunk.y : jj < 12 ? chunk.z : chunk.w;
-        const u64 *eqrow = peq + (size_t)rowmap[(word >> (8 * (jj & 3))) & 0xffu] * Wp;
-        int h = 0, nl = 0, sprev = 0;
-        bool ext = false;
-#pragma unroll kUnroll
-        for (int w = 0; w < wend; w++) {
-            if (w > L + 1 || w > last) break;
-            if (w == L + 1) {                       // band extension: only if the bottom of L was <= k last column
-                if (!ext) break;
-                st.p(w) = ~0ull;
-                st.m(w) = 0ull;
-                st.s(w) = sprev + 64;
-            }
-            u64 Pv = st.p(w), Mv = st.m(w);
-            const int sp = st.s(w);
-            h = mine_step(eqrow[w], Pv, Mv, h);
-            st.p(w) = Pv;
-            st.m(w) = Mv;
-            st.s(w) = sp + h;
-            if (w == L) { sprev = sp; ext = sp <= kk; }
-            if (sp + h < kk + 64) nl = w;          // the deepest block that may hold a cell <= k
-            if (w == last) {
-                const int v = mine_last_row(Pv, Mv, sp + h, rlast);
-                if (v <= kk) { best = v; kk = v; }
-            }
-        }
-        L = nl;
-    }
-    return best;
-}
 
 // Peq of query q into LDS: rowmap[256] (byte -> row, 0 = absent), peq[(nrows + 1) * Wp] words.
 __device__ void mine_build_peq(const unsigned char *qs, int m, int W, int Wp, u64 *peq, unsigned short *rowmap,
