@@ -16,6 +16,7 @@
 #include "smx.h"
 #include "smx_internal.h"
 #include "smx_prescan_core.h"
+#include "smx_barcode_core.h"
 
 namespace {
 
@@ -287,11 +288,8 @@ int smx_panel_create(const smx_panel_desc *d, smx_panel **out) {
     if (bs_ok)
         for (int p = 0; p < NP; p++)
             for (int li = pbc_off[p]; li < pbc_off[p + 1]; li++) {
-                int gb = pbc[li], bi = li - pbc_off[p];
-                for (int row = 0; row < 16; row++)   // rows past the barcode are wildcards (bitsliced_shw_pad)
-                    for (int c = 0; c < 16; c++)
-                        if (row >= bm[gb] || ((bpeq[gb * 16 + c] >> row) & 1u))
-                            bsre[((((size_t)p * MBWh + (bi >> 5)) * 16 + row) * 16 + c)] |= 1u << (bi & 31);   // [primer][word][row][code]
+                int gb = pbc[li], bi = li - pbc_off[p];   // [primer][word][row][code]; rows past the barcode are wildcards
+                smx::bs_table_add(&bsre[((size_t)p * MBWh + (bi >> 5)) * 256], bi & 31, &bpeq[gb * 16], bm[gb]);
             }
     // primers with the same barcode list (the same kit in every pool) share one table: the 8-primer panel keeps 2 of 8 in LDS
     std::vector<int> bs_tab(NP, 0);
