@@ -4,25 +4,30 @@
 One "step" = one pass of the hot path (libsmx: primer prescan kernels + demux kernel = primer scan, barcode scan,
 scorer) over one whole 765 000-read batch of configs[1], end windows already resident in HBM.  The timed loop ROTATES
 over three distinct resident batches (3 x 122 MB of windows: more than the 256 MiB Infinity Cache), so no step finds
-its input in the last-level cache; the rate on one batch relaunched in place is reported beside it (`single_buffer`).
+its input in the last-level cache; --full reports the rate on one batch relaunched in place beside it (`single_buffer`).
 `--gpus N` runs one process per GPU: under torch.distributed.run (RANK / WORLD_SIZE set) this process is one rank;
 started plainly with --gpus N > 1 it launches its own N ranks (python -m torch.distributed.run, before anything here
 touches a GPU), relays rank 0's line and exits with the ranks' status.  Every rank owns its own 765k-read shards
 (seed + rank, weak scaling, no data-path collective) and the per-specimen counts are summed once at the end with RCCL
 (smx_counts_allreduce, C ABI).  Rank 0 prints ONE JSON line.
 
-`value` is the kernel-resident rate the contract asks for.  The same line carries the wider scopes, so that no
-ratio has to mix scopes (N = 1 only, after the timed region):
-  step_kernels    device time of every kernel of a step (HIP events on the launch stream, smx_debug_kernel_times)
+`value` is the kernel-resident rate the contract asks for.  A plain run does only what it needs: it sets up, warms up,
+times the steps, writes --dump-outputs and prints the line with `value`, `ms_per_step` and the figures derived from them
+without further runs:
   roofline        vs the 8 TB/s HBM3E peak, ALGORITHMIC bytes = 196 B/read (2*search_len window bytes + 4 length +
-                  32 result record, SURVEY.md 8(d)) over ALL kernels of a step -- the same scope as `value`;
-                  `dominant_kernel` = the same bytes over the demux kernel alone.  `traffic` = HBM bytes per step from
-                  the committed rocprofv3 PMC passes of this workload (profiles/, replayed: not measured in this run).
+                  32 result record) over ALL kernels of a step -- the same scope as `value`.  `traffic` =
+                  HBM bytes per step from the committed rocprofv3 PMC passes of this workload (profiles/, replayed: not
+                  measured in this run).
+  valu_roofline   the bound that binds (integer VALU issue): wave64 VALU instructions per step (committed PMC summary,
+                  replayed) over the measured time per step, against the guide's peak (one wave64 VALU per SIMD-32 every
+                  2 cycles) and against the measured-mix bound of tools/ubench/issue_rate.hip (2.75 cycles).
+With --full the same line also carries the wider scopes, so that no ratio has to mix scopes (measured after the timed
+region; rank 0, and the last four with N = 1 only):
+  step_kernels    device time of every kernel of a step (HIP events on the launch stream, smx_debug_kernel_times);
+                  `roofline.dominant_kernel` = the algorithmic bytes over the demux kernel alone
+  one_stream      the same rotation with one batch in flight at a time; `single_buffer`: one batch relaunched in place
   other_configs   the configs[2]- and configs[4]-shaped workloads (3072 specimens / 8 primers; + -l 160, 15 % errors),
                   1 M reads per step, timed here after the headline region: value, per-kernel ms, path roofline
-  valu_roofline   the bound that binds (integer VALU issue): wave64 VALU instructions per step (committed PMC summary,
-                  replayed) over the measured kernel time, against the guide's peak (one wave64 VALU per SIMD-32 every
-                  2 cycles) and against the measured-mix bound of tools/ubench/issue_rate.hip (2.75 cycles).
   pcie_inclusive  host windows in, records out through the pinned, asynchronous lanes (smx_lane_*), three lanes in flight
   end_to_end      FASTQ file in /dev/shm -> output tree through the CLI pipeline (native reader, lanes, native writer):
                   reads/s, input GB/s, stage seconds, share of the wall time the main thread was not waiting for the GPU
@@ -472,9 +477,12 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the wider scopes after the timed region: per-kernel times, one stream, one buffer, "
+                         "other configs, PCIe-inclusive, end to end, CPU baseline (see the module docstring)")
     ap.add_argument("--reads", type=int, default=N_READS, help=argparse.SUPPRESS)
-    ap.add_argument("--no-cpu-baseline", action="store_true", help=argparse.SUPPRESS)
-    ap.add_argument("--no-extras", action="store_true", help=argparse.SUPPRESS)   # skip other_configs / pcie_inclusive / end_to_end (profiling runs)
+    ap.add_argument("--no-cpu-baseline", action="store_true", help=argparse.SUPPRESS)   # with --full: skip cpu_baseline
+    ap.add_argument("--no-extras", action="store_true", help=argparse.SUPPRESS)   # with --full: skip other_configs / pcie_inclusive / end_to_end (profiling runs)
     ap.add_argument("--e2e-reads", type=int, default=N_READS, help=argparse.SUPPRESS)
     ap.add_argument("--rotate", type=int, default=N_ROTATE, help=argparse.SUPPRESS)   # resident input batches (1: relaunch in place)
     ap.add_argument("--streams", type=int, default=None, help=argparse.SUPPRESS)      # batches in flight (default: 3 on configs[1], else 1)
@@ -496,7 +504,8 @@ def main():
     from specimux_amd import synth
     pan = synth.panel_c2(SEED) if a.config == "c2" else synth.panel_c3(SEED)
     tmp = tempfile.mkdtemp(prefix="smx_bench_")
-    e2e_dir = tempfile.mkdtemp(prefix="smx_bench_e2e_", dir="/dev/shm" if os.path.isdir("/dev/shm") else None)
+    e2e_dir = (tempfile.mkdtemp(prefix="smx_bench_e2e_", dir="/dev/shm" if os.path.isdir("/dev/shm") else None)
+               if a.full else None)
     pf, sf = pan.write(tmp)
     from specimux_amd.distributed import shard_seed
     gen_kw = dict(search_len=160, error_rate=0.15) if a.config == "c5" else {}
@@ -508,7 +517,7 @@ def main():
 
     solo = rank == 0 and a.gpus == 1
     cpu = None
-    if solo and not a.no_cpu_baseline and a.config == "c2":
+    if a.full and solo and not a.no_cpu_baseline and a.config == "c2":
         cpu = cpu_baseline(pf, sf, rs, e2e_dir)
 
     import torch
@@ -597,21 +606,9 @@ def main():
     if rank != 0:
         return
 
-    # ---- after the timed region (rank 0): the same launches on ONE batch relaunched in place (Infinity-Cache assisted),
-    # per-kernel device times (HIP events on the launch stream)
-    one_stream_ms = db.event_timed(a.steps, rotate=True, n_streams=1)
-    single_ms = db.event_timed(a.steps, rotate=False, n_streams=1) if len(sets) > 1 else None
-    k_t, k_d, k_b = db.kernel_times()
-    bsv = 1 if parameters.max_dist_index < 4 and (a.trim or "") != "tails" else (3 if parameters.max_dist_index < 4 else 2)
-    # (template arguments after the scan variant -- compact / redo mode, default-flags specialisation -- are chosen by the
-    # launch glue from the panel; panels with compact tiles launch the kernel twice per step, both are in this time)
-    demux_name = f"smx::demux_kernel<unsigned int, 256, {bsv}, ...>"
-    kernels_ms = k_t + k_d + k_b
-
     bytes_per_read = (2 * 160 + 4 + 32) if a.config == "c5" else BYTES_PER_READ
     step_ms_value = elapsed / a.steps * 1e3 / 1.0                       # per step of THIS rank: the scope of `value`
     achieved = bytes_per_read * n / (step_ms_value * 1e-3) / 1e9        # algorithmic bytes over the measured time per step
-    dom_achieved = bytes_per_read * n / (k_b * 1e-3) / 1e9              # the demux kernel alone, launched by itself
     traffic = None
     valu = None
     prof_name = "r03_pmc_summary.json" if os.path.exists(os.path.join(REPO, "profiles", "r03_pmc_summary.json")) else "r02_pmc_summary.json"
@@ -646,41 +643,54 @@ def main():
                    "scope": f"kernel-resident: end windows already in HBM, records left in HBM; the timed loop rotates over "
                             f"{len(sets)} distinct resident batches ({len(sets) * n * cp.window_stride / 1e6:.0f} MB of windows) and hands "
                             f"the steps round robin to {n_streams} HIP stream(s)"},
-        "step_kernels": step_kernel_list(k_t, k_d, k_b, demux_name),
-        "step_kernels_note": "each kernel launched by itself at full size on one stream (HIP events on that stream)",
-        "one_stream": {"value": n / (one_stream_ms * 1e-3), "unit": "reads/s", "ms_per_step": one_stream_ms,
-                       "note": "the same rotation with one batch in flight at a time"},
-        "single_buffer": ({"value": n / (single_ms * 1e-3), "unit": "reads/s", "ms_per_step": single_ms,
-                           "note": "one stream, one resident batch relaunched in place (inputs + intermediates fit the 256 MiB "
-                                   "Infinity Cache): NOT the headline"} if single_ms else None),
-        "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
-                     "frac": achieved / HBM_PEAK_GBPS, "traffic": traffic,
-                     "traffic_source": (f"profiles/{prof_name} (rocprofv3 FETCH_SIZE x2 + WRITE_SIZE over the three kernels "
-                                        "of a step; replayed, not measured in this run)") if traffic else None,
-                     "kernels": "all three kernels of a step, batches overlapped as in the timed loop (the scope of `value`)",
-                     "ms_per_step_this_rank": step_ms_value, "kernels_ms_one_at_a_time": kernels_ms,
-                     "algorithmic_bytes_per_read": bytes_per_read,
-                     "dominant_kernel": {"kernel": demux_name, "kernel_ms_avg": k_b, "achieved": dom_achieved,
-                                         "frac": dom_achieved / HBM_PEAK_GBPS},
-                     "note": "integer-VALU / latency bound, not HBM bound: see DESIGN.md sections 4-5"},
-        "cpu_baseline": cpu,
     }
+    roofline = {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBPS, "unit": "GB/s",
+                "frac": achieved / HBM_PEAK_GBPS, "traffic": traffic,
+                "traffic_source": (f"profiles/{prof_name} (rocprofv3 FETCH_SIZE x2 + WRITE_SIZE over the three kernels "
+                                   "of a step; replayed, not measured in this run)") if traffic else None,
+                "kernels": "all three kernels of a step, batches overlapped as in the timed loop (the scope of `value`)",
+                "ms_per_step_this_rank": step_ms_value, "algorithmic_bytes_per_read": bytes_per_read,
+                "note": "integer-VALU / latency bound, not HBM bound: see DESIGN.md sections 4-5"}
+    if a.full:
+        # ---- after the timed region (rank 0): the same launches with one batch in flight, on ONE batch relaunched in
+        # place (Infinity-Cache assisted), per-kernel device times (HIP events on the launch stream)
+        one_stream_ms = db.event_timed(a.steps, rotate=True, n_streams=1)
+        single_ms = db.event_timed(a.steps, rotate=False, n_streams=1) if len(sets) > 1 else None
+        k_t, k_d, k_b = db.kernel_times()
+        bsv = 1 if parameters.max_dist_index < 4 and (a.trim or "") != "tails" else (3 if parameters.max_dist_index < 4 else 2)
+        # (template arguments after the scan variant -- compact / redo mode, default-flags specialisation -- are chosen by the
+        # launch glue from the panel; panels with compact tiles launch the kernel twice per step, both are in this time)
+        demux_name = f"smx::demux_kernel<unsigned int, 256, {bsv}, ...>"
+        dom_achieved = bytes_per_read * n / (k_b * 1e-3) / 1e9              # the demux kernel alone, launched by itself
+        out["step_kernels"] = step_kernel_list(k_t, k_d, k_b, demux_name)
+        out["step_kernels_note"] = "each kernel launched by itself at full size on one stream (HIP events on that stream)"
+        out["one_stream"] = {"value": n / (one_stream_ms * 1e-3), "unit": "reads/s", "ms_per_step": one_stream_ms,
+                             "note": "the same rotation with one batch in flight at a time"}
+        out["single_buffer"] = ({"value": n / (single_ms * 1e-3), "unit": "reads/s", "ms_per_step": single_ms,
+                                 "note": "one stream, one resident batch relaunched in place (inputs + intermediates fit the "
+                                         "256 MiB Infinity Cache): NOT the headline"} if single_ms else None)
+        roofline["kernels_ms_one_at_a_time"] = k_t + k_d + k_b
+        roofline["dominant_kernel"] = {"kernel": demux_name, "kernel_ms_avg": k_b, "achieved": dom_achieved,
+                                       "frac": dom_achieved / HBM_PEAK_GBPS}
+    out["roofline"] = roofline
     if valu:
         out["valu_roofline"] = valu
-    cp.set_streams(1)
-    if solo and not a.no_extras and a.config == "c2":
-        del db
-        torch.cuda.empty_cache()
-        out["other_configs"] = {c: side_config(lib, c, dev, stream, tmp) for c in ("c3", "c5")}
-        out["pcie_inclusive"] = pcie_inclusive(cp, rs)
-        out["end_to_end"] = end_to_end(pan, pf, sf, a.e2e_reads, e2e_dir)
-    if cpu:
-        out["gpu_over_cpu"] = out["value"] / cpu["value"]   # kernel-resident rate over the oracle's in-memory rate, same reads
-        out["gpu_over_cpu_scopes"] = {"kernel_resident_over_cpu_in_memory": out["gpu_over_cpu"],
-                                      "note": "like-for-like scopes only; both CPU legs are the Python-loop oracle, not a tuned CPU code"}
-        if out.get("end_to_end"):
-            out["gpu_over_cpu_scopes"]["end_to_end_over_cpu_end_to_end"] = out["end_to_end"]["value"] / cpu["end_to_end"]["value"]
-    shutil.rmtree(e2e_dir, ignore_errors=True)
+    if a.full:
+        out["cpu_baseline"] = cpu
+        cp.set_streams(1)
+        if solo and not a.no_extras and a.config == "c2":
+            del db
+            torch.cuda.empty_cache()
+            out["other_configs"] = {c: side_config(lib, c, dev, stream, tmp) for c in ("c3", "c5")}
+            out["pcie_inclusive"] = pcie_inclusive(cp, rs)
+            out["end_to_end"] = end_to_end(pan, pf, sf, a.e2e_reads, e2e_dir)
+        if cpu:
+            out["gpu_over_cpu"] = out["value"] / cpu["value"]   # kernel-resident rate over the oracle's in-memory rate, same reads
+            out["gpu_over_cpu_scopes"] = {"kernel_resident_over_cpu_in_memory": out["gpu_over_cpu"],
+                                          "note": "like-for-like scopes only; both CPU legs are the Python-loop oracle, not a tuned CPU code"}
+            if out.get("end_to_end"):
+                out["gpu_over_cpu_scopes"]["end_to_end_over_cpu_end_to_end"] = out["end_to_end"]["value"] / cpu["end_to_end"]["value"]
+        shutil.rmtree(e2e_dir, ignore_errors=True)
     shutil.rmtree(tmp, ignore_errors=True)
     print(json.dumps(out))
 

@@ -5,7 +5,7 @@
 set -e
 TAG=${1:-r01}
 OUT=gpurun_out/prof_$TAG
-BENCH="python3 bench.py --no-cpu-baseline --no-extras --steps 5 --warmup 2 ${BENCH_ARGS:-}"
+BENCH="python3 bench.py --full --no-cpu-baseline --no-extras --steps 5 --warmup 2 ${BENCH_ARGS:-}"
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 mkdir -p "$OUT"
 case "${BENCH_ARGS:-}" in *c5*) export PROF_BYTES_PER_READ=356;; esac   # -l 160: 2 * 160 + 4 + 32 algorithmic bytes per read
