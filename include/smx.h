@@ -300,6 +300,15 @@ int smx_mine_distances(const char *queries, const uint64_t *qoff, uint32_t n_que
 int smx_mine_best_identity(const char *queries, const uint64_t *qoff, uint32_t n_queries, const int32_t *k,
                            const char *targets, const uint64_t *toff, uint32_t n_targets, const smx_mine_job *jobs,
                            uint32_t n_jobs, double *best, float *kernel_ms);
+/*
+ * smx_mine_best_identity_fused: the same arguments and the same best[] bit for bit as smx_mine_best_identity, without
+ * a distance matrix: each pair's identity goes straight into its target's best with a 64-bit atomic max.  Device and
+ * host memory are bounded by the queries, the targets, sum(nq) and sum(nt); nothing grows with sum(nq * nt).  Job
+ * target ranges may overlap (many jobs over one uploaded target set).  kernel_ms: device time of the mining kernels.
+ */
+int smx_mine_best_identity_fused(const char *queries, const uint64_t *qoff, uint32_t n_queries, const int32_t *k,
+                                 const char *targets, const uint64_t *toff, uint32_t n_targets, const smx_mine_job *jobs,
+                                 uint32_t n_jobs, double *best, float *kernel_ms);
 
 /*
  * RCCL reduction of the per-specimen counts over xGMI (one communicator per process/GPU).

@@ -79,6 +79,8 @@ SYMBOLS = [
                                      C.POINTER(C.c_float)]),
     ("smx_mine_best_identity", C.c_int, [C.c_char_p, _P, C.c_uint32, _P, C.c_char_p, _P, C.c_uint32, _P, C.c_uint32, _P,
                                          C.POINTER(C.c_float)]),
+    ("smx_mine_best_identity_fused", C.c_int, [C.c_char_p, _P, C.c_uint32, _P, C.c_char_p, _P, C.c_uint32, _P, C.c_uint32,
+                                               _P, C.POINTER(C.c_float)]),
     ("smx_comm_unique_id", C.c_int, [_P]),
     ("smx_comm_init", C.c_int, [_P, C.c_int, C.c_int, C.POINTER(_P)]),
     ("smx_counts_allreduce", C.c_int, [_P, C.c_size_t, _P, _P]),

@@ -947,18 +947,15 @@ int smx_align_batch(const char *queries, const uint32_t *qoff, uint32_t n_querie
 // ---- specimine: batched long-read HW distances (smx_mine.hip); grow-only device workspace, calls serialised
 namespace {
 std::mutex g_mine_mutex;
-DevBuf g_mine_ws[9];
+DevBuf g_mine_ws[11];   // [9], [10]: smx_mine_best_identity_fused's pair list and chunk starts
 
-// the work of one smx_mine_* call up to the distances, left on the device in g_mine_ws[6]
-int mine_run(const char *queries, const uint64_t *qoff, uint32_t n_queries, const int32_t *k, const char *targets,
-             const uint64_t *toff, uint32_t n_targets, const smx_mine_job *jobs, uint32_t n_jobs,
-             std::vector<smx::MineJobDev> *djobs, uint64_t *n_pairs, float *kernel_ms) {
-    if (!queries || !qoff || !k || !targets || !toff || (n_jobs && !jobs)) return fail(SMX_ERR_ARG, "null argument");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(SMX_ERR_DEVICE, "libsmx has no CPU path: no HIP device");
-    // per query: words, distinct bytes -> LDS bytes of its Peq table; register class of its per-lane state
-    std::vector<size_t> qlds(n_queries);
-    std::vector<int> qclass(n_queries);
+// per query: LDS bytes of its Peq table ((distinct bytes + 1) x padded words) and the register class of its per-lane state
+int mine_queries(const char *queries, const uint64_t *qoff, uint32_t n_queries, std::vector<size_t> *qlds_out,
+                 std::vector<int> *qclass_out) {
+    std::vector<size_t> &qlds = *qlds_out;
+    std::vector<int> &qclass = *qclass_out;
+    qlds.assign(n_queries, 0);
+    qclass.assign(n_queries, 0);
     for (uint32_t q = 0; q < n_queries; q++) {
         if (qoff[q + 1] <= qoff[q]) return fail(SMX_ERR_ARG, "query %u is empty", q);
         const uint64_t m = qoff[q + 1] - qoff[q];
@@ -976,9 +973,16 @@ int mine_run(const char *queries, const uint64_t *qoff, uint32_t n_queries, cons
                         rows, W, qlds[q], (size_t)SMX_LDS_POOL);
         qclass[q] = W <= 1 ? 1 : W <= 2 ? 2 : W <= 4 ? 3 : W <= 8 ? 4 : W <= 16 ? 5 : 0;
     }
-    // targets: 16-byte aligned copies, 16 bytes of slack at the end (the kernel loads 16 bytes at a time)
-    std::vector<uint64_t> tdoff(n_targets);
-    std::vector<int32_t> tlen(n_targets);
+    return SMX_OK;
+}
+
+// targets: 16-byte aligned copies, 16 bytes of slack at the end (the kernel loads 16 bytes at a time)
+int mine_targets(const char *targets, const uint64_t *toff, uint32_t n_targets, std::vector<uint64_t> *tdoff_out,
+                 std::vector<int32_t> *tlen_out, std::vector<unsigned char> *tpad) {
+    std::vector<uint64_t> &tdoff = *tdoff_out;
+    std::vector<int32_t> &tlen = *tlen_out;
+    tdoff.assign(n_targets, 0);
+    tlen.assign(n_targets, 0);
     uint64_t tbytes = 0;
     for (uint32_t t = 0; t < n_targets; t++) {
         if (toff[t + 1] < toff[t] || toff[t + 1] - toff[t] > (uint64_t)INT32_MAX) return fail(SMX_ERR_ARG, "target %u: bad offsets", t);
@@ -987,8 +991,28 @@ int mine_run(const char *queries, const uint64_t *qoff, uint32_t n_queries, cons
         tbytes += ((uint64_t)tlen[t] + 15) & ~(uint64_t)15;
     }
     tbytes += 16;
-    std::vector<unsigned char> tpad(tbytes, 0);
-    for (uint32_t t = 0; t < n_targets; t++) memcpy(&tpad[tdoff[t]], targets + toff[t], (size_t)tlen[t]);
+    tpad->assign(tbytes, 0);
+    for (uint32_t t = 0; t < n_targets; t++) memcpy(tpad->data() + tdoff[t], targets + toff[t], (size_t)tlen[t]);
+    return SMX_OK;
+}
+
+// the work of one smx_mine_* call up to the distances, left on the device in g_mine_ws[6]
+int mine_run(const char *queries, const uint64_t *qoff, uint32_t n_queries, const int32_t *k, const char *targets,
+             const uint64_t *toff, uint32_t n_targets, const smx_mine_job *jobs, uint32_t n_jobs,
+             std::vector<smx::MineJobDev> *djobs, uint64_t *n_pairs, float *kernel_ms) {
+    if (!queries || !qoff || !k || !targets || !toff || (n_jobs && !jobs)) return fail(SMX_ERR_ARG, "null argument");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(SMX_ERR_DEVICE, "libsmx has no CPU path: no HIP device");
+    std::vector<size_t> qlds;
+    std::vector<int> qclass;
+    int rc = mine_queries(queries, qoff, n_queries, &qlds, &qclass);
+    if (rc != SMX_OK) return rc;
+    std::vector<uint64_t> tdoff;
+    std::vector<int32_t> tlen;
+    std::vector<unsigned char> tpad;
+    rc = mine_targets(targets, toff, n_targets, &tdoff, &tlen, &tpad);
+    if (rc != SMX_OK) return rc;
+    const uint64_t tbytes = tpad.size();
     // jobs -> work items (one query x up to MINE_THREADS targets), grouped by register class
     std::vector<smx::MineItem> items[6];
     size_t lds_max[6] = {0, 0, 0, 0, 0, 0};
@@ -1100,6 +1124,129 @@ int smx_mine_best_identity(const char *queries, const uint64_t *qoff, uint32_t n
     double *d_best = (double *)((char *)B[8].p + n_jobs * sizeof(smx::MineJobDev));
     int e = smx_launch_mine_best(nullptr, B[8].p, n_jobs, (const uint64_t *)B[1].p, (const int32_t *)B[6].p, d_best, n_out);
     if (e != 0) return fail(SMX_ERR_DEVICE, "identity reduction launch failed: %s", hipGetErrorString((hipError_t)e));
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(best, d_best, n_out * 8, hipMemcpyDeviceToHost));
+    return SMX_OK;
+}
+
+// Fused: the best identities without a distance matrix.  Device and host memory are bounded by the queries, the targets,
+// sum(nq) (job, query) pairs and sum(nt) outputs; nothing is sized by sum(nq * nt).
+int smx_mine_best_identity_fused(const char *queries, const uint64_t *qoff, uint32_t n_queries, const int32_t *k,
+                                 const char *targets, const uint64_t *toff, uint32_t n_targets, const smx_mine_job *jobs,
+                                 uint32_t n_jobs, double *best, float *kernel_ms) {
+    if (!best && n_jobs) return fail(SMX_ERR_ARG, "null argument");
+    if (!queries || !qoff || !k || !targets || !toff || (n_jobs && !jobs)) return fail(SMX_ERR_ARG, "null argument");
+    std::lock_guard<std::mutex> guard(g_mine_mutex);
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(SMX_ERR_DEVICE, "libsmx has no CPU path: no HIP device");
+    std::vector<size_t> qlds;
+    std::vector<int> qclass;
+    int rc = mine_queries(queries, qoff, n_queries, &qlds, &qclass);
+    if (rc != SMX_OK) return rc;
+    std::vector<uint64_t> tdoff;
+    std::vector<int32_t> tlen;
+    std::vector<unsigned char> tpad;
+    rc = mine_targets(targets, toff, n_targets, &tdoff, &tlen, &tpad);
+    if (rc != SMX_OK) return rc;
+    // jobs -> (job, query) pairs with at least one target, grouped by register class, in query order within a class
+    // (a workgroup rebuilds the Peq table only when the query changes)
+    std::vector<smx::MineJobDev> djobs(n_jobs);
+    std::vector<smx::MineFusedPair> pairs[6];
+    size_t lds_max[6] = {0, 0, 0, 0, 0, 0};
+    int words_max0 = 0;
+    uint64_t n_out = 0;
+    for (uint32_t j = 0; j < n_jobs; j++) {
+        const smx_mine_job &J = jobs[j];
+        if ((uint64_t)J.q0 + J.nq > n_queries || (uint64_t)J.t0 + J.nt > n_targets)
+            return fail(SMX_ERR_ARG, "job %u: query or target range out of bounds", j);
+        djobs[j] = smx::MineJobDev{J.q0, J.nq, J.t0, J.nt, 0, n_out, J.min_identity};
+        n_out += J.nt;
+        if (J.nt == 0) continue;
+        for (uint32_t i = 0; i < J.nq; i++) {
+            const uint32_t q = J.q0 + i;
+            const int c = qclass[q];
+            lds_max[c] = std::max(lds_max[c], qlds[q]);
+            if (c == 0) words_max0 = std::max(words_max0, (int)((qoff[q + 1] - qoff[q] + 63) / 64));
+            pairs[c].push_back(smx::MineFusedPair{j, q, k[q], 0});
+        }
+    }
+    if (n_out == 0) return SMX_OK;
+    size_t npairs = 0;
+    std::vector<uint64_t> chunk_start;            // per class: n + 1 prefix entries, one after the other
+    uint64_t chunks[6] = {0, 0, 0, 0, 0, 0};
+    for (int c = 0; c < 6; c++) {
+        std::stable_sort(pairs[c].begin(), pairs[c].end(),
+                         [](const smx::MineFusedPair &a, const smx::MineFusedPair &b) { return a.q < b.q; });
+        if (pairs[c].empty()) continue;
+        chunk_start.push_back(0);
+        for (const smx::MineFusedPair &P : pairs[c]) {
+            chunks[c] += (djobs[P.job].nt + MINE_THREADS - 1) / MINE_THREADS;
+            chunk_start.push_back(chunks[c]);
+        }
+        npairs += pairs[c].size();
+    }
+    // a workgroup takes MINE_FUSED_CHUNKS chunks in a row (more where the grid is capped): the pair search and the
+    // Peq build of a query's run of chunks are paid once.  Measured on MI355X: one chunk per
+    // workgroup loses 1.5x on runs of cheap (decoy) chunks, runs of 8 lose ~11 % to balance on costly chunks
+    constexpr uint64_t MINE_FUSED_CHUNKS = 8;
+    const uint64_t grid_cap = (uint64_t)INT32_MAX;
+    // the generic class keeps its per-lane state in a global slice per workgroup: bound its grid to ~256 MiB of it
+    const size_t slice = (size_t)3 * words_max0 * MINE_THREADS * 8;
+    const uint64_t grid0_cap = std::max<size_t>(1, ((size_t)256 << 20) / std::max<size_t>(slice, 1));
+    DevBuf *B = g_mine_ws;
+    const size_t sz[5] = {(size_t)qoff[n_queries], ((size_t)n_queries + 1) * 8, tpad.size(), (size_t)n_targets * 8,
+                          (size_t)n_targets * 4};
+    for (int b = 0; b < 5; b++) HIP_TRY(B[b].ensure(std::max<size_t>(sz[b], 16)));
+    HIP_TRY(B[9].ensure(npairs * sizeof(smx::MineFusedPair)));
+    HIP_TRY(B[10].ensure(chunk_start.size() * 8));
+    if (!pairs[0].empty()) HIP_TRY(B[7].ensure((size_t)std::min(chunks[0], grid0_cap) * slice));
+    HIP_TRY(B[8].ensure(n_jobs * sizeof(smx::MineJobDev) + n_out * 8));
+    HIP_TRY(hipMemcpy(B[0].p, queries, sz[0], hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(B[1].p, qoff, sz[1], hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(B[2].p, tpad.data(), sz[2], hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(B[3].p, tdoff.data(), sz[3], hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(B[4].p, tlen.data(), sz[4], hipMemcpyHostToDevice));
+    size_t at = 0;
+    for (int c = 0; c < 6; c++) {
+        if (!pairs[c].empty())
+            HIP_TRY(hipMemcpy((char *)B[9].p + at * sizeof(smx::MineFusedPair), pairs[c].data(),
+                              pairs[c].size() * sizeof(smx::MineFusedPair), hipMemcpyHostToDevice));
+        at += pairs[c].size();
+    }
+    HIP_TRY(hipMemcpy(B[10].p, chunk_start.data(), chunk_start.size() * 8, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(B[8].p, djobs.data(), n_jobs * sizeof(smx::MineJobDev), hipMemcpyHostToDevice));
+    unsigned long long *d_best = (unsigned long long *)((char *)B[8].p + n_jobs * sizeof(smx::MineJobDev));
+    HIP_TRY(hipMemset(d_best, 0, n_out * 8));       // +0.0: "no pair counts"
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    if (kernel_ms) {
+        HIP_TRY(hipEventCreate(&ev[0]));
+        HIP_TRY(hipEventCreate(&ev[1]));
+        HIP_TRY(hipEventRecord(ev[0], nullptr));
+    }
+    static const int kWords[6] = {0, 1, 2, 4, 8, 16};
+    size_t pat = 0, cat = 0;
+    int e = 0;
+    for (int c = 0; c < 6 && e == 0; c++) {
+        const uint32_t n = (uint32_t)pairs[c].size();
+        if (!n) continue;
+        const uint64_t cap = c == 0 ? std::min(grid_cap, grid0_cap) : grid_cap;
+        const uint64_t per_block = std::max(MINE_FUSED_CHUNKS, (chunks[c] + cap - 1) / cap);
+        const uint64_t grid = (chunks[c] + per_block - 1) / per_block;
+        e = smx_launch_mine_fused(nullptr, kWords[c], (const unsigned char *)B[0].p, (const uint64_t *)B[1].p,
+                                  (const unsigned char *)B[2].p, (const uint64_t *)B[3].p, (const int32_t *)B[4].p,
+                                  (const char *)B[9].p + pat * sizeof(smx::MineFusedPair), (const uint64_t *)B[10].p + cat, n,
+                                  B[8].p, (int)grid, per_block, lds_max[c], d_best, (unsigned long long *)B[7].p, words_max0);
+        pat += n;
+        cat += (size_t)n + 1;
+    }
+    if (e != 0) return fail(SMX_ERR_DEVICE, "fused mining kernel launch failed: %s", hipGetErrorString((hipError_t)e));
+    if (kernel_ms) {
+        HIP_TRY(hipEventRecord(ev[1], nullptr));
+        HIP_TRY(hipEventSynchronize(ev[1]));
+        HIP_TRY(hipEventElapsedTime(kernel_ms, ev[0], ev[1]));
+        (void)hipEventDestroy(ev[0]);
+        (void)hipEventDestroy(ev[1]);
+    }
     HIP_TRY(hipDeviceSynchronize());
     HIP_TRY(hipMemcpy(best, d_best, n_out * 8, hipMemcpyDeviceToHost));
     return SMX_OK;

@@ -85,6 +85,13 @@ struct MineJobDev {   // one smx_mine_job with its output offsets
     double min_identity;
 };
 
+struct MineFusedPair { // smx_mine_best_identity_fused: one (job, query) pair, ceil(nt / MINE_THREADS) target chunks
+    uint32_t job;     // index into the MineJobDev array
+    uint32_t q;       // query index
+    int32_t k;        // max distance of the query (< 0: none)
+    uint32_t pad;
+};
+
 }  // namespace smx
 
 extern "C" {
@@ -117,6 +124,14 @@ int smx_launch_align_batch(void *stream, const unsigned long long *d_qpeq, const
 int smx_launch_mine(void *stream, int wr, const unsigned char *d_q, const uint64_t *d_qoff, const unsigned char *d_t,
                     const uint64_t *d_toff, const int32_t *d_tlen, const void *d_items, uint32_t n_items, int grid,
                     size_t lds_bytes, int32_t *d_dist, unsigned long long *d_scratch, int scratch_words);
+// wr as smx_launch_mine; pairs[0..n_pairs) with chunk_start[0..n_pairs] (prefix sum of their target chunks, nonzero
+// each); workgroup b takes chunks [b * per_block, (b + 1) * per_block), grid * per_block >= the chunk count; d_best
+// holds the 64-bit patterns of the non-negative best identities (zeroed by the caller)
+int smx_launch_mine_fused(void *stream, int wr, const unsigned char *d_q, const uint64_t *d_qoff, const unsigned char *d_t,
+                          const uint64_t *d_toff, const int32_t *d_tlen, const void *d_pairs, const uint64_t *d_chunk_start,
+                          uint32_t n_pairs, const void *d_jobs, int grid, uint64_t per_block, size_t lds_bytes,
+                          unsigned long long *d_best,
+                          unsigned long long *d_scratch, int scratch_words);
 int smx_launch_mine_best(void *stream, const void *d_jobs, uint32_t n_jobs, const uint64_t *d_qoff, const int32_t *d_dist,
                          double *d_best, uint64_t n_out);
 }

@@ -78,6 +78,75 @@ __global__ __launch_bounds__(MINE_THREADS) void mine_kernel(const unsigned char 
     }
 }
 
+// Best identity without a distance matrix (smx_mine_best_identity_fused).  The work is the chunk list of (job, query)
+// pairs, pair p owning chunks [chunk_start[p], chunk_start[p + 1]) = MINE_THREADS targets each.  Workgroup b takes
+// the contiguous chunks [b * per_block, (b + 1) * per_block): one pair search per workgroup, the Peq table rebuilt
+// only when the query changes, and workgroups short enough that the hardware balances their uneven cost.  Each lane
+// turns its distance
+// into the pair's identity contribution (mine_identity) and, if that is > 0, raises best[job.best_off + t] with a
+// 64-bit atomic max on the bit pattern (non-negative doubles order like their patterns; best starts at +0.0).
+template <int WR>
+__global__ __launch_bounds__(MINE_THREADS) void mine_fused_kernel(const unsigned char *__restrict__ qbytes,
+                                                                  const uint64_t *__restrict__ qoff,
+                                                                  const unsigned char *__restrict__ tbytes,
+                                                                  const uint64_t *__restrict__ toff,
+                                                                  const int32_t *__restrict__ tlen,
+                                                                  const MineFusedPair *__restrict__ pairs,
+                                                                  const uint64_t *__restrict__ chunk_start, uint32_t n_pairs,
+                                                                  const MineJobDev *__restrict__ jobs,
+                                                                  uint64_t per_block, unsigned long long *best, u64 *scratch,
+                                                                  int scratch_words) {
+    extern __shared__ u64 lds[];
+    unsigned short *rowmap = reinterpret_cast<unsigned short *>(lds);     // 512 B
+    unsigned *present = reinterpret_cast<unsigned *>(lds + 64);           // 1 KiB
+    u64 *peq = lds + MINE_LDS_HEAD;
+    const uint64_t n_chunks = chunk_start[n_pairs];
+    const uint64_t lo = (uint64_t)blockIdx.x * per_block;
+    const uint64_t hi = lo + per_block < n_chunks ? lo + per_block : n_chunks;
+    // the pair whose chunk range holds lo: a 64-way search, one load per lane and round (3 rounds up to 262 144
+    // pairs); each wave finds the same pair on its own
+    uint32_t p = 0, n = n_pairs;                   // the pair is in [p, p + n)
+    while (n > 1) {
+        const uint32_t step = (n + 63) / 64, idx = p + (threadIdx.x & 63) * step;
+        const bool le = idx < p + n && chunk_start[idx] <= lo;    // true on a prefix of the lanes (lane 0 always)
+        const uint32_t below = (uint32_t)__popcll(__ballot(le)) - 1;
+        const uint32_t end = p + n;
+        p += below * step;
+        n = min(step, end - p);
+    }
+    uint32_t cur_q = 0xffffffffu;
+    const unsigned lane = threadIdx.x;
+    for (uint64_t v = lo; v < hi; v++) {
+        while (chunk_start[p + 1] <= v) p++;
+        const MineFusedPair P = pairs[p];
+        const MineJobDev J = jobs[P.job];
+        const uint32_t c0 = (uint32_t)(v - chunk_start[p]) * MINE_THREADS;   // first target of the chunk in the job
+        const uint64_t q0 = qoff[P.q];
+        const int m = (int)(qoff[P.q + 1] - q0);
+        const int W = (m + 63) >> 6, Wp = W | 1;
+        if (P.q != cur_q) {
+            __syncthreads();                       // the previous query's lanes are done with the table
+            mine_build_peq(qbytes + q0, m, W, Wp, peq, rowmap, present);
+            cur_q = P.q;
+        }
+        if ((uint64_t)c0 + lane < J.nt) {
+            const uint32_t ti = J.t0 + c0 + lane;
+            int d;
+            if constexpr (WR > 0) {
+                RegState<WR> st;
+                d = mine_pair<WR>(st, peq, rowmap, m, W, Wp, P.k, tbytes + toff[ti], tlen[ti]);
+            } else {
+                u64 *sbase = scratch + (size_t)blockIdx.x * 3 * scratch_words * MINE_THREADS;
+                GlobalState st{sbase + lane, sbase + (size_t)scratch_words * MINE_THREADS + lane,
+                               reinterpret_cast<int *>(sbase + (size_t)2 * scratch_words * MINE_THREADS) + lane};
+                d = mine_pair<0>(st, peq, rowmap, m, W, Wp, P.k, tbytes + toff[ti], tlen[ti]);
+            }
+            const double identity = mine_identity(d, m, J.min_identity);
+            if (identity > 0.0) atomicMax(&best[J.best_off + c0 + lane], (unsigned long long)__double_as_longlong(identity));
+        }
+    }
+}
+
 // best identity per (job, target): max over the job's queries of 1 - d / m among d != -1, identity >= min_identity
 // and identity > 0 (the reference's loop: best starts at 0 and only grows), in IEEE double.
 __global__ void mine_best_kernel(const MineJobDev *__restrict__ jobs, uint32_t n_jobs, const uint64_t *__restrict__ qoff,
@@ -133,6 +202,46 @@ extern "C" int smx_launch_mine(void *stream, int wr, const unsigned char *d_q, c
         case 16: hipLaunchKernelGGL(mine_kernel<16>, dim3(grid), dim3(MINE_THREADS), lds_bytes, s, d_q, d_qoff, d_t, d_toff, d_tlen, items, n_items, d_dist, d_scratch, scratch_words); break;
         default: hipLaunchKernelGGL(mine_kernel<0>, dim3(grid), dim3(MINE_THREADS), lds_bytes, s, d_q, d_qoff, d_t, d_toff, d_tlen, items, n_items, d_dist, d_scratch, scratch_words); break;
     }
+    return (int)hipGetLastError();
+}
+
+extern "C" int smx_launch_mine_fused(void *stream, int wr, const unsigned char *d_q, const uint64_t *d_qoff,
+                                     const unsigned char *d_t, const uint64_t *d_toff, const int32_t *d_tlen,
+                                     const void *d_pairs, const uint64_t *d_chunk_start, uint32_t n_pairs,
+                                     const void *d_jobs, int grid, uint64_t per_block, size_t lds_bytes,
+                                     unsigned long long *d_best,
+                                     unsigned long long *d_scratch, int scratch_words) {
+    using namespace smx;
+    const void *fn;
+    switch (wr) {
+        case 1: fn = (const void *)mine_fused_kernel<1>; break;
+        case 2: fn = (const void *)mine_fused_kernel<2>; break;
+        case 4: fn = (const void *)mine_fused_kernel<4>; break;
+        case 8: fn = (const void *)mine_fused_kernel<8>; break;
+        case 16: fn = (const void *)mine_fused_kernel<16>; break;
+        case 0: fn = (const void *)mine_fused_kernel<0>; break;
+        default: return (int)hipErrorInvalidValue;
+    }
+    if (n_pairs == 0 || grid < 1 || per_block < 1) return (int)hipErrorInvalidValue;
+    if (lds_bytes > 65536) {
+        hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+        if (e != hipSuccess) return (int)e;
+    }
+    const MineFusedPair *pairs = (const MineFusedPair *)d_pairs;
+    const MineJobDev *jobs = (const MineJobDev *)d_jobs;
+    hipStream_t s = (hipStream_t)stream;
+#define SMX_MINE_FUSED(WR) hipLaunchKernelGGL(mine_fused_kernel<WR>, dim3(grid), dim3(MINE_THREADS), lds_bytes, s, d_q, d_qoff, \
+                                              d_t, d_toff, d_tlen, pairs, d_chunk_start, n_pairs, jobs, per_block, d_best, \
+                                              d_scratch, scratch_words)
+    switch (wr) {
+        case 1: SMX_MINE_FUSED(1); break;
+        case 2: SMX_MINE_FUSED(2); break;
+        case 4: SMX_MINE_FUSED(4); break;
+        case 8: SMX_MINE_FUSED(8); break;
+        case 16: SMX_MINE_FUSED(16); break;
+        default: SMX_MINE_FUSED(0); break;
+    }
+#undef SMX_MINE_FUSED
     return (int)hipGetLastError();
 }
 

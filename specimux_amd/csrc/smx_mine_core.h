@@ -155,6 +155,15 @@ SMX_MINE_HD int mine_pair(State &st, const u64 *peq, const unsigned short *rowma
     return best;
 }
 
+// What one pair contributes to its target's best identity: 1 - d / m in IEEE double (the reference's expression), or 0
+// where the pair does not count (d = -1, identity below min_identity, identity 0).  The best of a target is the
+// largest contribution over its queries; a non-negative double orders like its 64-bit pattern.
+SMX_HD double mine_identity(int d, int m, double min_identity) {
+    if (d == -1) return 0.0;
+    const double identity = 1.0 - (double)d / (double)m;
+    return (identity >= min_identity && identity > 0.0) ? identity : 0.0;
+}
+
 }  // namespace smx
 
 #endif  // SMX_MINE_CORE_H

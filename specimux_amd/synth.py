@@ -376,14 +376,19 @@ def _mutate(rng, s, rate):
 
 
 def write_mine_tree(root, n_specimens=4, n_full=6, n_partial=10, length=650, seed=0, pairs=("P1-P2",),
-                    pool="POOL", partial_error=(0.0, 0.25), decoy_fraction=0.3):
+                    pool="POOL", partial_error=(0.0, 0.25), decoy_fraction=0.3, fwd_groups=0):
     """A specimux output tree under `root` for specimine: specimens.txt, full/<pool>/<specimen>.fastq (and the same at
     full/<pool>/<pair>/), partial/<pool>/<pair>/barcode_{fwd,rev}_<barcode>.fastq.  Per specimen one random insert of
     ~`length` nt; full reads are copies with 2 % errors, partial reads copies with a per-read error rate drawn from
-    `partial_error` or unrelated decoys; lengths vary by about +-10 %.  Returns the specimen ids."""
+    `partial_error` or unrelated decoys; lengths vary by about +-10 %.  fwd_groups > 0: specimen i takes forward
+    barcode i % fwd_groups, so that specimens share one forward partial file (a plate grid); 0: one barcode each.
+    Returns the specimen ids."""
     rng = np.random.default_rng(seed)
     fwd, rev = make_barcodes(n_specimens, n_specimens, seed=seed)
+    if fwd_groups > 0:
+        fwd = [fwd[i % fwd_groups] for i in range(n_specimens)]
     ids = [f"S{i:03d}" for i in range(n_specimens)]
+    shared = {}                                    # partial file -> its records' sequences and tags, in specimen order
 
     def fastq(path, seqs, tag):
         os.makedirs(os.path.dirname(path), exist_ok=True)
@@ -411,5 +416,12 @@ def write_mine_tree(root, n_specimens=4, n_full=6, n_partial=10, length=650, see
                     else:
                         lo, hi = partial_error
                         parts.append(_mutate(rng, insert, rng.uniform(lo, hi)))
-                fastq(os.path.join(root, "partial", pool, pair, f"barcode_{kind}_{bc}.fastq"), parts, f"{sid}_{pair}_{kind}")
+                shared.setdefault(os.path.join(root, "partial", pool, pair, f"barcode_{kind}_{bc}.fastq"), []).append(
+                    (parts, f"{sid}_{pair}_{kind}"))
+    for path, chunks in shared.items():
+        os.makedirs(os.path.dirname(path), exist_ok=True)
+        with open(path, "w") as fh:
+            for parts, tag in chunks:
+                for j, s in enumerate(parts):
+                    fh.write(f"@{tag}_{j} some description {j}\n{s}\n+\n{'I' * len(s)}\n")
     return ids

@@ -5,7 +5,12 @@ line: pairs/s and cell updates/s (sum of len(full) * len(partial) over kernel ti
 (file reading, device work, writing), and a CPU comparator -- a sampled subset through the O(m*n) oracle DP,
 extrapolated.  The comparator is that DP, not edlib (edlib is not installed), so no speed-up over edlib is measured.
 
-    python tools/specimine_bench.py [--specimens 96 --full 300 --partial 300 --length 650 --min-identity 0.85]"""
+    python tools/specimine_bench.py [--specimens 96 --full 300 --partial 300 --length 650 --min-identity 0.85]
+
+--run: the whole-run mode.  A plate-grid tree (specimens share forward barcodes, --fwd-groups of them) is mined with
+`specimine.mine_run` (what `--run-dir` runs); one JSON line: end-to-end seconds of mine_run, the fused kernel's
+pairs/s next to the two-step path (distance matrix + reduction) on the same device jobs, and the device memory each
+path takes, measured in a fresh child process per path (device free bytes before / after, workspaces are grow-only)."""
 import argparse
 import json
 import os
@@ -30,7 +35,14 @@ def main():
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--cpu-sample", type=int, default=300)
     ap.add_argument("--workdir", default=None)
+    ap.add_argument("--run", action="store_true", help="whole-run mode (see the module doc)")
+    ap.add_argument("--fwd-groups", type=int, default=8, help="--run: forward barcodes shared by the specimens")
+    ap.add_argument("--peak", choices=("fused", "two-step"), default=None, help=argparse.SUPPRESS)
     a = ap.parse_args()
+    if a.peak:
+        return peak_child(a)
+    if a.run:
+        return run_mode(a)
     import ctypes as C
     lib = _lib.load()
     _lib.check(lib.smx_device_init(0, C.byref(C.c_int(0))))
@@ -82,6 +94,67 @@ def main():
         "cpu_comparator": "O(mn) DP, not edlib (oracle/align_oracle.c, one core, sampled)",
         "cpu_sample_pairs": len(sample), "cpu_pairs_per_s": round(cpu_rate, 1),
         "cpu_extrapolated_s": round(pairs / cpu_rate, 1),
+    }))
+
+
+def run_jobs(root, min_identity):
+    index = os.path.join(root, "specimens.txt")
+    return [specimine.plan_job(index, f, True, False, min_identity) for f in specimine.discover_specimens(root, "pool")]
+
+
+def peak_child(a):
+    """One path over every job of the tree in one call, in a fresh process: device bytes it took."""
+    import ctypes as C
+    import torch
+    lib = _lib.load()
+    _lib.check(lib.smx_device_init(0, C.byref(C.c_int(0))))
+    jobs = run_jobs(a.workdir, a.min_identity)
+    free0, _ = torch.cuda.mem_get_info(0)
+    specimine._mine_call(jobs, fused=a.peak == "fused")
+    free1, _ = torch.cuda.mem_get_info(0)
+    print(json.dumps({"peak_device_bytes": free0 - free1}))
+
+
+def run_mode(a):
+    import ctypes as C
+    import subprocess
+    lib = _lib.load()
+    _lib.check(lib.smx_device_init(0, C.byref(C.c_int(0))))
+    root = a.workdir or tempfile.mkdtemp(prefix="specimine_run_bench_")
+    ids = synth.write_mine_tree(root, a.specimens, a.full, a.partial, a.length, seed=1, fwd_groups=a.fwd_groups)
+    index = os.path.join(root, "specimens.txt")
+    jobs = run_jobs(root, a.min_identity)
+    pairs = 0
+    for job in jobs:
+        nf = len(specimine.read_fastq(job.fastq))
+        pairs += nf * sum(len(specimine.read_fastq(f)) for f in specimine.job_partials(job))
+    specimine._mine_call(jobs[:1])                             # warm-up: code objects, workspace
+    specimine._mine_call(jobs[:1], fused=False)
+    e2e, kms = [], {"fused": [], "two-step": []}
+    for _ in range(a.repeats):
+        ms = []
+        t0 = time.perf_counter()
+        res = specimine.mine_run(root, index, "pool", True, False, a.min_identity, kernel_ms=ms)
+        e2e.append(time.perf_counter() - t0)
+        for name, fused in (("fused", True), ("two-step", False)):
+            ms = []
+            specimine._mine_call(jobs, kernel_ms=ms, fused=fused)
+            kms[name].append(sum(ms))
+    peak = {}
+    for name in ("fused", "two-step"):
+        r = subprocess.run([sys.executable, os.path.abspath(__file__), "--peak", name, "--workdir", root,
+                            "--min-identity", repr(a.min_identity)], capture_output=True, text=True, timeout=900)
+        peak[name] = json.loads(r.stdout.strip().splitlines()[-1])["peak_device_bytes"] if r.returncode == 0 else None
+    fused_ms, two_ms = min(kms["fused"]), min(kms["two-step"])
+    print(json.dumps({
+        "bench": "specimine_run", "specimens": len(ids), "fwd_groups": a.fwd_groups, "full_per_specimen": a.full,
+        "partial_per_file": a.partial, "read_length": a.length, "min_identity": a.min_identity,
+        "pairs": pairs, "mined_specimens": res["mined"], "mined_records": res["reads"],
+        "run_dir_e2e_s": round(min(e2e), 3),
+        "fused_kernel_ms": round(fused_ms, 3), "fused_pairs_per_s": round(pairs / (fused_ms / 1e3), 1),
+        "two_step_kernel_ms": round(two_ms, 3), "two_step_pairs_per_s": round(pairs / (two_ms / 1e3), 1),
+        "fused_peak_device_bytes": peak["fused"], "two_step_peak_device_bytes": peak["two-step"],
+        "distance_matrix_bytes": 4 * pairs,
     }))
 
 
