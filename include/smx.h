@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define SMX_ABI_VERSION 4
+#define SMX_ABI_VERSION 5
 
 typedef enum {
     SMX_OK = 0,
@@ -283,11 +283,14 @@ int smx_align_batch(const char *queries, const uint32_t *qoff, uint32_t n_querie
  *   targets / toff     n_targets targets (concatenated, n_targets + 1 offsets), any length (empty: distance = query
  *                      length whatever k is, as edlib)
  *   jobs               each job pairs queries [q0, q0 + nq) with targets [t0, t0 + nt)
- * smx_mine_distances writes job j's nq x nt distances row-major (one row per query) at dist[sum over earlier jobs of
- * nq * nt].  smx_mine_best_identity reduces on the device instead: per target of job j, at best[sum over earlier jobs
- * of nt], the largest identity = 1 - d / len(query) (IEEE double) over the job's queries with d != -1,
- * identity >= min_identity and identity > 0; 0 when there is none.
- * kernel_ms (may be NULL) receives the device time of the distance kernels (HIP events).
+ * smx_mine_best_identity: per target of job j, at best[sum over earlier jobs of nt], the largest identity
+ * = 1 - d / len(query) (IEEE double) over the job's queries with d != -1, identity >= min_identity and identity > 0;
+ * 0 when there is none.  Each pair's identity goes straight into its target's best with a 64-bit atomic max, without a
+ * distance matrix: device and host memory are bounded by the queries, the targets, sum(nq) and sum(nt); nothing grows
+ * with sum(nq * nt).  Job target ranges may overlap (many jobs over one uploaded target set).
+ * smx_mine_distances, kept for tests and inspection, writes job j's nq x nt distances row-major (one row per query) at
+ * dist[sum over earlier jobs of nq * nt].
+ * kernel_ms (may be NULL) receives the device time of the mining kernels (HIP events).
  */
 typedef struct smx_mine_job {
     uint32_t q0, nq, t0, nt;
@@ -300,15 +303,6 @@ int smx_mine_distances(const char *queries, const uint64_t *qoff, uint32_t n_que
 int smx_mine_best_identity(const char *queries, const uint64_t *qoff, uint32_t n_queries, const int32_t *k,
                            const char *targets, const uint64_t *toff, uint32_t n_targets, const smx_mine_job *jobs,
                            uint32_t n_jobs, double *best, float *kernel_ms);
-/*
- * smx_mine_best_identity_fused: the same arguments and the same best[] bit for bit as smx_mine_best_identity, without
- * a distance matrix: each pair's identity goes straight into its target's best with a 64-bit atomic max.  Device and
- * host memory are bounded by the queries, the targets, sum(nq) and sum(nt); nothing grows with sum(nq * nt).  Job
- * target ranges may overlap (many jobs over one uploaded target set).  kernel_ms: device time of the mining kernels.
- */
-int smx_mine_best_identity_fused(const char *queries, const uint64_t *qoff, uint32_t n_queries, const int32_t *k,
-                                 const char *targets, const uint64_t *toff, uint32_t n_targets, const smx_mine_job *jobs,
-                                 uint32_t n_jobs, double *best, float *kernel_ms);
 
 /*
  * RCCL reduction of the per-specimen counts over xGMI (one communicator per process/GPU).

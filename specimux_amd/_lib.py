@@ -9,7 +9,7 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SMX_LIB") or os.path.join(_HERE, "libsmx.so")   # SMX_LIB: A/B builds (tools/tune.sh)
 
-ABI_VERSION = 4
+ABI_VERSION = 5
 OK, ERR_ARG, ERR_UNSUPPORTED, ERR_DEVICE, ERR_OVERFLOW = 0, -1, -2, -3, -4
 TRIM = {"none": 0, "tails": 1, "barcodes": 2, "primers": 3}
 DEREP = {"none": 0, "best": 1}
@@ -79,8 +79,6 @@ SYMBOLS = [
                                      C.POINTER(C.c_float)]),
     ("smx_mine_best_identity", C.c_int, [C.c_char_p, _P, C.c_uint32, _P, C.c_char_p, _P, C.c_uint32, _P, C.c_uint32, _P,
                                          C.POINTER(C.c_float)]),
-    ("smx_mine_best_identity_fused", C.c_int, [C.c_char_p, _P, C.c_uint32, _P, C.c_char_p, _P, C.c_uint32, _P, C.c_uint32,
-                                               _P, C.POINTER(C.c_float)]),
     ("smx_comm_unique_id", C.c_int, [_P]),
     ("smx_comm_init", C.c_int, [_P, C.c_int, C.c_int, C.POINTER(_P)]),
     ("smx_counts_allreduce", C.c_int, [_P, C.c_size_t, _P, _P]),

@@ -947,7 +947,7 @@ int smx_align_batch(const char *queries, const uint32_t *qoff, uint32_t n_querie
 // ---- specimine: batched long-read HW distances (smx_mine.hip); grow-only device workspace, calls serialised
 namespace {
 std::mutex g_mine_mutex;
-DevBuf g_mine_ws[11];   // [9], [10]: smx_mine_best_identity_fused's pair list and chunk starts
+DevBuf g_mine_ws[9];    // queries, qoff, targets, target offsets, lengths, pairs, chunk starts, scratch, jobs + output
 
 // per query: LDS bytes of its Peq table ((distinct bytes + 1) x padded words) and the register class of its per-lane state
 int mine_queries(const char *queries, const uint64_t *qoff, uint32_t n_queries, std::vector<size_t> *qlds_out,
@@ -996,145 +996,13 @@ int mine_targets(const char *targets, const uint64_t *toff, uint32_t n_targets, 
     return SMX_OK;
 }
 
-// the work of one smx_mine_* call up to the distances, left on the device in g_mine_ws[6]
-int mine_run(const char *queries, const uint64_t *qoff, uint32_t n_queries, const int32_t *k, const char *targets,
-             const uint64_t *toff, uint32_t n_targets, const smx_mine_job *jobs, uint32_t n_jobs,
-             std::vector<smx::MineJobDev> *djobs, uint64_t *n_pairs, float *kernel_ms) {
-    if (!queries || !qoff || !k || !targets || !toff || (n_jobs && !jobs)) return fail(SMX_ERR_ARG, "null argument");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(SMX_ERR_DEVICE, "libsmx has no CPU path: no HIP device");
-    std::vector<size_t> qlds;
-    std::vector<int> qclass;
-    int rc = mine_queries(queries, qoff, n_queries, &qlds, &qclass);
-    if (rc != SMX_OK) return rc;
-    std::vector<uint64_t> tdoff;
-    std::vector<int32_t> tlen;
-    std::vector<unsigned char> tpad;
-    rc = mine_targets(targets, toff, n_targets, &tdoff, &tlen, &tpad);
-    if (rc != SMX_OK) return rc;
-    const uint64_t tbytes = tpad.size();
-    // jobs -> work items (one query x up to MINE_THREADS targets), grouped by register class
-    std::vector<smx::MineItem> items[6];
-    size_t lds_max[6] = {0, 0, 0, 0, 0, 0};
-    int words_max0 = 0;
-    djobs->resize(n_jobs);
-    uint64_t dist_off = 0, best_off = 0;
-    for (uint32_t j = 0; j < n_jobs; j++) {
-        const smx_mine_job &J = jobs[j];
-        if ((uint64_t)J.q0 + J.nq > n_queries || (uint64_t)J.t0 + J.nt > n_targets)
-            return fail(SMX_ERR_ARG, "job %u: query or target range out of bounds", j);
-        (*djobs)[j] = smx::MineJobDev{J.q0, J.nq, J.t0, J.nt, dist_off, best_off, J.min_identity};
-        for (uint32_t i = 0; i < J.nq; i++) {
-            const uint32_t q = J.q0 + i;
-            const int c = qclass[q];
-            lds_max[c] = std::max(lds_max[c], qlds[q]);
-            if (c == 0) words_max0 = std::max(words_max0, (int)((qoff[q + 1] - qoff[q] + 63) / 64));
-            for (uint32_t t = 0; t < J.nt; t += MINE_THREADS)
-                items[c].push_back(smx::MineItem{q, J.t0 + t, std::min<uint32_t>(MINE_THREADS, J.nt - t), k[q],
-                                                 dist_off + (uint64_t)i * J.nt + t});
-        }
-        dist_off += (uint64_t)J.nq * J.nt;
-        best_off += J.nt;
-    }
-    *n_pairs = dist_off;
-    // the generic class keeps its per-lane state in a global slice per workgroup: bound the grid to ~256 MiB of it
-    const size_t slice = (size_t)3 * words_max0 * MINE_THREADS * 8;
-    const int grid0 = (int)std::min<size_t>(std::max<size_t>(items[0].size(), 1),
-                                            std::max<size_t>(1, ((size_t)256 << 20) / std::max<size_t>(slice, 1)));
-    size_t nitems = 0;
-    for (int c = 0; c < 6; c++) nitems += items[c].size();
-    DevBuf *B = g_mine_ws;
-    const size_t sz[8] = {(size_t)qoff[n_queries], ((size_t)n_queries + 1) * 8, (size_t)tbytes, (size_t)n_targets * 8,
-                          (size_t)n_targets * 4, nitems * sizeof(smx::MineItem), (size_t)dist_off * 4,
-                          items[0].empty() ? 0 : (size_t)grid0 * slice};
-    for (int b = 0; b < 8; b++) HIP_TRY(B[b].ensure(std::max<size_t>(sz[b], 16)));
-    HIP_TRY(hipMemcpy(B[0].p, queries, sz[0], hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(B[1].p, qoff, sz[1], hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(B[2].p, tpad.data(), sz[2], hipMemcpyHostToDevice));
-    if (n_targets) {
-        HIP_TRY(hipMemcpy(B[3].p, tdoff.data(), sz[3], hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(B[4].p, tlen.data(), sz[4], hipMemcpyHostToDevice));
-    }
-    size_t at = 0;
-    for (int c = 0; c < 6; c++) {
-        if (!items[c].empty())
-            HIP_TRY(hipMemcpy((char *)B[5].p + at * sizeof(smx::MineItem), items[c].data(), items[c].size() * sizeof(smx::MineItem),
-                              hipMemcpyHostToDevice));
-        at += items[c].size();
-    }
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    if (kernel_ms) {
-        HIP_TRY(hipEventCreate(&ev[0]));
-        HIP_TRY(hipEventCreate(&ev[1]));
-        HIP_TRY(hipEventRecord(ev[0], nullptr));
-    }
-    static const int kWords[6] = {0, 1, 2, 4, 8, 16};
-    at = 0;
-    int e = 0;
-    for (int c = 0; c < 6 && e == 0; c++) {
-        const uint32_t n = (uint32_t)items[c].size();
-        if (n)
-            e = smx_launch_mine(nullptr, kWords[c], (const unsigned char *)B[0].p, (const uint64_t *)B[1].p,
-                                (const unsigned char *)B[2].p, (const uint64_t *)B[3].p, (const int32_t *)B[4].p,
-                                (const char *)B[5].p + at * sizeof(smx::MineItem), n, c == 0 ? grid0 : (int)n, lds_max[c],
-                                (int32_t *)B[6].p, (unsigned long long *)B[7].p, words_max0);
-        at += n;
-    }
-    if (e != 0) return fail(SMX_ERR_DEVICE, "mining kernel launch failed: %s", hipGetErrorString((hipError_t)e));
-    if (kernel_ms) {
-        HIP_TRY(hipEventRecord(ev[1], nullptr));
-        HIP_TRY(hipEventSynchronize(ev[1]));
-        HIP_TRY(hipEventElapsedTime(kernel_ms, ev[0], ev[1]));
-        (void)hipEventDestroy(ev[0]);
-        (void)hipEventDestroy(ev[1]);
-    }
-    HIP_TRY(hipDeviceSynchronize());
-    return SMX_OK;
-}
-}  // namespace
-
-int smx_mine_distances(const char *queries, const uint64_t *qoff, uint32_t n_queries, const int32_t *k, const char *targets,
-                       const uint64_t *toff, uint32_t n_targets, const smx_mine_job *jobs, uint32_t n_jobs, int32_t *dist,
-                       float *kernel_ms) {
-    if (!dist && n_jobs) return fail(SMX_ERR_ARG, "null argument");
-    std::lock_guard<std::mutex> guard(g_mine_mutex);
-    std::vector<smx::MineJobDev> djobs;
-    uint64_t n_pairs = 0;
-    int rc = mine_run(queries, qoff, n_queries, k, targets, toff, n_targets, jobs, n_jobs, &djobs, &n_pairs, kernel_ms);
-    if (rc != SMX_OK) return rc;
-    if (n_pairs) HIP_TRY(hipMemcpy(dist, g_mine_ws[6].p, n_pairs * 4, hipMemcpyDeviceToHost));
-    return SMX_OK;
-}
-
-int smx_mine_best_identity(const char *queries, const uint64_t *qoff, uint32_t n_queries, const int32_t *k,
-                           const char *targets, const uint64_t *toff, uint32_t n_targets, const smx_mine_job *jobs,
-                           uint32_t n_jobs, double *best, float *kernel_ms) {
-    if (!best && n_jobs) return fail(SMX_ERR_ARG, "null argument");
-    std::lock_guard<std::mutex> guard(g_mine_mutex);
-    std::vector<smx::MineJobDev> djobs;
-    uint64_t n_pairs = 0;
-    int rc = mine_run(queries, qoff, n_queries, k, targets, toff, n_targets, jobs, n_jobs, &djobs, &n_pairs, kernel_ms);
-    if (rc != SMX_OK) return rc;
-    uint64_t n_out = 0;
-    for (uint32_t j = 0; j < n_jobs; j++) n_out += jobs[j].nt;
-    if (n_out == 0) return SMX_OK;
-    DevBuf *B = g_mine_ws;
-    HIP_TRY(B[8].ensure(n_jobs * sizeof(smx::MineJobDev) + n_out * 8));
-    HIP_TRY(hipMemcpy(B[8].p, djobs.data(), n_jobs * sizeof(smx::MineJobDev), hipMemcpyHostToDevice));
-    double *d_best = (double *)((char *)B[8].p + n_jobs * sizeof(smx::MineJobDev));
-    int e = smx_launch_mine_best(nullptr, B[8].p, n_jobs, (const uint64_t *)B[1].p, (const int32_t *)B[6].p, d_best, n_out);
-    if (e != 0) return fail(SMX_ERR_DEVICE, "identity reduction launch failed: %s", hipGetErrorString((hipError_t)e));
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(best, d_best, n_out * 8, hipMemcpyDeviceToHost));
-    return SMX_OK;
-}
-
-// Fused: the best identities without a distance matrix.  Device and host memory are bounded by the queries, the targets,
-// sum(nq) (job, query) pairs and sum(nt) outputs; nothing is sized by sum(nq * nt).
-int smx_mine_best_identity_fused(const char *queries, const uint64_t *qoff, uint32_t n_queries, const int32_t *k,
-                                 const char *targets, const uint64_t *toff, uint32_t n_targets, const smx_mine_job *jobs,
-                                 uint32_t n_jobs, double *best, float *kernel_ms) {
-    if (!best && n_jobs) return fail(SMX_ERR_ARG, "null argument");
+// One smx_mine_* call.  distances: job j's nq x nt distances at out[sum over earlier jobs of nq * nt] (int32); else
+// the best identities at out[sum over earlier jobs of nt] (double).  Device and host memory hold the queries, the
+// targets, sum(nq) (job, query) pairs and the output: only the distance output grows with sum(nq * nt).
+int mine_call(bool distances, const char *queries, const uint64_t *qoff, uint32_t n_queries, const int32_t *k,
+              const char *targets, const uint64_t *toff, uint32_t n_targets, const smx_mine_job *jobs, uint32_t n_jobs,
+              void *out, float *kernel_ms) {
+    if (!out && n_jobs) return fail(SMX_ERR_ARG, "null argument");
     if (!queries || !qoff || !k || !targets || !toff || (n_jobs && !jobs)) return fail(SMX_ERR_ARG, "null argument");
     std::lock_guard<std::mutex> guard(g_mine_mutex);
     int ndev = 0;
@@ -1151,44 +1019,50 @@ int smx_mine_best_identity_fused(const char *queries, const uint64_t *qoff, uint
     // jobs -> (job, query) pairs with at least one target, grouped by register class, in query order within a class
     // (a workgroup rebuilds the Peq table only when the query changes)
     std::vector<smx::MineJobDev> djobs(n_jobs);
-    std::vector<smx::MineFusedPair> pairs[6];
+    std::vector<smx::MinePair> pairs[6];
     size_t lds_max[6] = {0, 0, 0, 0, 0, 0};
     int words_max0 = 0;
-    uint64_t n_out = 0;
+    uint64_t dist_off = 0, best_off = 0;
     for (uint32_t j = 0; j < n_jobs; j++) {
         const smx_mine_job &J = jobs[j];
         if ((uint64_t)J.q0 + J.nq > n_queries || (uint64_t)J.t0 + J.nt > n_targets)
             return fail(SMX_ERR_ARG, "job %u: query or target range out of bounds", j);
-        djobs[j] = smx::MineJobDev{J.q0, J.nq, J.t0, J.nt, 0, n_out, J.min_identity};
-        n_out += J.nt;
+        djobs[j] = smx::MineJobDev{J.q0, J.nq, J.t0, J.nt, dist_off, best_off, J.min_identity};
+        dist_off += (uint64_t)J.nq * J.nt;
+        best_off += J.nt;
         if (J.nt == 0) continue;
         for (uint32_t i = 0; i < J.nq; i++) {
             const uint32_t q = J.q0 + i;
             const int c = qclass[q];
             lds_max[c] = std::max(lds_max[c], qlds[q]);
             if (c == 0) words_max0 = std::max(words_max0, (int)((qoff[q + 1] - qoff[q] + 63) / 64));
-            pairs[c].push_back(smx::MineFusedPair{j, q, k[q], 0});
+            pairs[c].push_back(smx::MinePair{j, q, k[q], 0});
         }
     }
-    if (n_out == 0) return SMX_OK;
+    const uint64_t n_out = distances ? dist_off : best_off;
+    if (n_out == 0) {
+        if (kernel_ms) *kernel_ms = 0.0f;
+        return SMX_OK;
+    }
+    const size_t out_bytes = n_out * (distances ? sizeof(int32_t) : sizeof(double));
     size_t npairs = 0;
     std::vector<uint64_t> chunk_start;            // per class: n + 1 prefix entries, one after the other
     uint64_t chunks[6] = {0, 0, 0, 0, 0, 0};
     for (int c = 0; c < 6; c++) {
         std::stable_sort(pairs[c].begin(), pairs[c].end(),
-                         [](const smx::MineFusedPair &a, const smx::MineFusedPair &b) { return a.q < b.q; });
+                         [](const smx::MinePair &a, const smx::MinePair &b) { return a.q < b.q; });
         if (pairs[c].empty()) continue;
         chunk_start.push_back(0);
-        for (const smx::MineFusedPair &P : pairs[c]) {
+        for (const smx::MinePair &P : pairs[c]) {
             chunks[c] += (djobs[P.job].nt + MINE_THREADS - 1) / MINE_THREADS;
             chunk_start.push_back(chunks[c]);
         }
         npairs += pairs[c].size();
     }
-    // a workgroup takes MINE_FUSED_CHUNKS chunks in a row (more where the grid is capped): the pair search and the
+    // a workgroup takes MINE_BLOCK_CHUNKS chunks in a row (more where the grid is capped): the pair search and the
     // Peq build of a query's run of chunks are paid once.  Measured on MI355X: one chunk per
     // workgroup loses 1.5x on runs of cheap (decoy) chunks, runs of 8 lose ~11 % to balance on costly chunks
-    constexpr uint64_t MINE_FUSED_CHUNKS = 8;
+    constexpr uint64_t MINE_BLOCK_CHUNKS = 8;
     const uint64_t grid_cap = (uint64_t)INT32_MAX;
     // the generic class keeps its per-lane state in a global slice per workgroup: bound its grid to ~256 MiB of it
     const size_t slice = (size_t)3 * words_max0 * MINE_THREADS * 8;
@@ -1197,10 +1071,10 @@ int smx_mine_best_identity_fused(const char *queries, const uint64_t *qoff, uint
     const size_t sz[5] = {(size_t)qoff[n_queries], ((size_t)n_queries + 1) * 8, tpad.size(), (size_t)n_targets * 8,
                           (size_t)n_targets * 4};
     for (int b = 0; b < 5; b++) HIP_TRY(B[b].ensure(std::max<size_t>(sz[b], 16)));
-    HIP_TRY(B[9].ensure(npairs * sizeof(smx::MineFusedPair)));
-    HIP_TRY(B[10].ensure(chunk_start.size() * 8));
+    HIP_TRY(B[5].ensure(npairs * sizeof(smx::MinePair)));
+    HIP_TRY(B[6].ensure(chunk_start.size() * 8));
     if (!pairs[0].empty()) HIP_TRY(B[7].ensure((size_t)std::min(chunks[0], grid0_cap) * slice));
-    HIP_TRY(B[8].ensure(n_jobs * sizeof(smx::MineJobDev) + n_out * 8));
+    HIP_TRY(B[8].ensure(n_jobs * sizeof(smx::MineJobDev) + out_bytes));
     HIP_TRY(hipMemcpy(B[0].p, queries, sz[0], hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(B[1].p, qoff, sz[1], hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(B[2].p, tpad.data(), sz[2], hipMemcpyHostToDevice));
@@ -1209,14 +1083,14 @@ int smx_mine_best_identity_fused(const char *queries, const uint64_t *qoff, uint
     size_t at = 0;
     for (int c = 0; c < 6; c++) {
         if (!pairs[c].empty())
-            HIP_TRY(hipMemcpy((char *)B[9].p + at * sizeof(smx::MineFusedPair), pairs[c].data(),
-                              pairs[c].size() * sizeof(smx::MineFusedPair), hipMemcpyHostToDevice));
+            HIP_TRY(hipMemcpy((char *)B[5].p + at * sizeof(smx::MinePair), pairs[c].data(),
+                              pairs[c].size() * sizeof(smx::MinePair), hipMemcpyHostToDevice));
         at += pairs[c].size();
     }
-    HIP_TRY(hipMemcpy(B[10].p, chunk_start.data(), chunk_start.size() * 8, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(B[6].p, chunk_start.data(), chunk_start.size() * 8, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(B[8].p, djobs.data(), n_jobs * sizeof(smx::MineJobDev), hipMemcpyHostToDevice));
-    unsigned long long *d_best = (unsigned long long *)((char *)B[8].p + n_jobs * sizeof(smx::MineJobDev));
-    HIP_TRY(hipMemset(d_best, 0, n_out * 8));       // +0.0: "no pair counts"
+    void *d_out = (char *)B[8].p + n_jobs * sizeof(smx::MineJobDev);
+    if (!distances) HIP_TRY(hipMemset(d_out, 0, out_bytes));       // +0.0: "no pair counts"
     hipEvent_t ev[2] = {nullptr, nullptr};
     if (kernel_ms) {
         HIP_TRY(hipEventCreate(&ev[0]));
@@ -1230,16 +1104,16 @@ int smx_mine_best_identity_fused(const char *queries, const uint64_t *qoff, uint
         const uint32_t n = (uint32_t)pairs[c].size();
         if (!n) continue;
         const uint64_t cap = c == 0 ? std::min(grid_cap, grid0_cap) : grid_cap;
-        const uint64_t per_block = std::max(MINE_FUSED_CHUNKS, (chunks[c] + cap - 1) / cap);
+        const uint64_t per_block = std::max(MINE_BLOCK_CHUNKS, (chunks[c] + cap - 1) / cap);
         const uint64_t grid = (chunks[c] + per_block - 1) / per_block;
-        e = smx_launch_mine_fused(nullptr, kWords[c], (const unsigned char *)B[0].p, (const uint64_t *)B[1].p,
-                                  (const unsigned char *)B[2].p, (const uint64_t *)B[3].p, (const int32_t *)B[4].p,
-                                  (const char *)B[9].p + pat * sizeof(smx::MineFusedPair), (const uint64_t *)B[10].p + cat, n,
-                                  B[8].p, (int)grid, per_block, lds_max[c], d_best, (unsigned long long *)B[7].p, words_max0);
+        e = smx_launch_mine(nullptr, kWords[c], distances, (const unsigned char *)B[0].p, (const uint64_t *)B[1].p,
+                            (const unsigned char *)B[2].p, (const uint64_t *)B[3].p, (const int32_t *)B[4].p,
+                            (const char *)B[5].p + pat * sizeof(smx::MinePair), (const uint64_t *)B[6].p + cat, n,
+                            B[8].p, (int)grid, per_block, lds_max[c], d_out, (unsigned long long *)B[7].p, words_max0);
         pat += n;
         cat += (size_t)n + 1;
     }
-    if (e != 0) return fail(SMX_ERR_DEVICE, "fused mining kernel launch failed: %s", hipGetErrorString((hipError_t)e));
+    if (e != 0) return fail(SMX_ERR_DEVICE, "mining kernel launch failed: %s", hipGetErrorString((hipError_t)e));
     if (kernel_ms) {
         HIP_TRY(hipEventRecord(ev[1], nullptr));
         HIP_TRY(hipEventSynchronize(ev[1]));
@@ -1248,8 +1122,21 @@ int smx_mine_best_identity_fused(const char *queries, const uint64_t *qoff, uint
         (void)hipEventDestroy(ev[1]);
     }
     HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(best, d_best, n_out * 8, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(out, d_out, out_bytes, hipMemcpyDeviceToHost));
     return SMX_OK;
+}
+}  // namespace
+
+int smx_mine_distances(const char *queries, const uint64_t *qoff, uint32_t n_queries, const int32_t *k, const char *targets,
+                       const uint64_t *toff, uint32_t n_targets, const smx_mine_job *jobs, uint32_t n_jobs, int32_t *dist,
+                       float *kernel_ms) {
+    return mine_call(true, queries, qoff, n_queries, k, targets, toff, n_targets, jobs, n_jobs, dist, kernel_ms);
+}
+
+int smx_mine_best_identity(const char *queries, const uint64_t *qoff, uint32_t n_queries, const int32_t *k,
+                           const char *targets, const uint64_t *toff, uint32_t n_targets, const smx_mine_job *jobs,
+                           uint32_t n_jobs, double *best, float *kernel_ms) {
+    return mine_call(false, queries, qoff, n_queries, k, targets, toff, n_targets, jobs, n_jobs, best, kernel_ms);
 }
 
 // ---- lanes: asynchronous host-buffer path (pinned staging, one stream per lane)

@@ -68,16 +68,8 @@ struct DemuxAux {
     const uint8_t *naflag;   // prescan: per read, 1 = a window holds something other than upper-case ACGT (ASCII path for that read)
 };
 
-// specimine (smx_mine.hip): one query x up to MINE_THREADS (smx_mine_core.h) targets per work item, one target per lane
+// specimine (smx_mine.hip): chunks of one query x up to MINE_THREADS (smx_mine_core.h) targets, one target per lane
 #define MINE_LDS_HEAD 192   // u64 words before the Peq table: byte -> row map (512 B) + byte presence flags (1 KiB)
-
-struct MineItem {
-    uint32_t q;       // query index
-    uint32_t t0;      // first target index
-    uint32_t nt;      // targets (lanes) of this item, 1..MINE_THREADS
-    int32_t k;        // max distance (< 0: none)
-    uint64_t out;     // dist index of (q, t0); lane i writes out + i
-};
 
 struct MineJobDev {   // one smx_mine_job with its output offsets
     uint32_t q0, nq, t0, nt;
@@ -85,7 +77,7 @@ struct MineJobDev {   // one smx_mine_job with its output offsets
     double min_identity;
 };
 
-struct MineFusedPair { // smx_mine_best_identity_fused: one (job, query) pair, ceil(nt / MINE_THREADS) target chunks
+struct MinePair {     // one (job, query) pair, ceil(nt / MINE_THREADS) target chunks
     uint32_t job;     // index into the MineJobDev array
     uint32_t q;       // query index
     int32_t k;        // max distance of the query (< 0: none)
@@ -120,19 +112,14 @@ int smx_launch_align_batch(void *stream, const unsigned long long *d_qpeq, const
                            const unsigned char *d_tcodes, const unsigned long long *d_toff, const int *d_k,
                            const unsigned char *d_modes, unsigned n, unsigned char *d_ws, int *d_dist, int *d_nloc,
                            int *d_starts, int *d_ends, unsigned cap);
-// specimine (smx_mine.hip); wr = register words per lane (1, 2, 4, 8, 16) or 0 = state in d_scratch
-int smx_launch_mine(void *stream, int wr, const unsigned char *d_q, const uint64_t *d_qoff, const unsigned char *d_t,
-                    const uint64_t *d_toff, const int32_t *d_tlen, const void *d_items, uint32_t n_items, int grid,
-                    size_t lds_bytes, int32_t *d_dist, unsigned long long *d_scratch, int scratch_words);
-// wr as smx_launch_mine; pairs[0..n_pairs) with chunk_start[0..n_pairs] (prefix sum of their target chunks, nonzero
-// each); workgroup b takes chunks [b * per_block, (b + 1) * per_block), grid * per_block >= the chunk count; d_best
-// holds the 64-bit patterns of the non-negative best identities (zeroed by the caller)
-int smx_launch_mine_fused(void *stream, int wr, const unsigned char *d_q, const uint64_t *d_qoff, const unsigned char *d_t,
-                          const uint64_t *d_toff, const int32_t *d_tlen, const void *d_pairs, const uint64_t *d_chunk_start,
-                          uint32_t n_pairs, const void *d_jobs, int grid, uint64_t per_block, size_t lds_bytes,
-                          unsigned long long *d_best,
-                          unsigned long long *d_scratch, int scratch_words);
-int smx_launch_mine_best(void *stream, const void *d_jobs, uint32_t n_jobs, const uint64_t *d_qoff, const int32_t *d_dist,
-                         double *d_best, uint64_t n_out);
+// specimine (smx_mine.hip); wr = register words per lane (1, 2, 4, 8, 16) or 0 = state in d_scratch; pairs[0..n_pairs)
+// with chunk_start[0..n_pairs] (prefix sum of their target chunks, nonzero each); workgroup b takes chunks
+// [b * per_block, (b + 1) * per_block), grid * per_block >= the chunk count.  dist = 0: d_out holds the 64-bit patterns
+// of the non-negative best identities (zeroed by the caller); dist = 1: d_out holds the int32 distances, job j's
+// nq x nt row-major at its dist_off
+int smx_launch_mine(void *stream, int wr, int dist, const unsigned char *d_q, const uint64_t *d_qoff, const unsigned char *d_t,
+                    const uint64_t *d_toff, const int32_t *d_tlen, const void *d_pairs, const uint64_t *d_chunk_start,
+                    uint32_t n_pairs, const void *d_jobs, int grid, uint64_t per_block, size_t lds_bytes, void *d_out,
+                    unsigned long long *d_scratch, int scratch_words);
 }
 #endif

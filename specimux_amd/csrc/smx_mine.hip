@@ -1,7 +1,7 @@
 // smx_mine.hip -- the specimine hot path: batched HW (infix) edit distances of long reads, distance only.
 //
-// One work item = one query (a full read) x up to MINE_THREADS targets (partial reads), one target per lane.
-// The workgroup builds the query's Peq once in LDS from a byte -> row map (row 0 = bytes absent from the query,
+// One chunk = one query (a full read) x up to MINE_THREADS targets (partial reads), one target per lane.
+// The workgroup builds the query's Peq in LDS from a byte -> row map (row 0 = bytes absent from the query,
 // all zero), then every lane runs mine_pair (smx_mine_core.h: the multi-word Myers/Hyyro bit-vector with an
 // edlib-style block band, host/device code shared with the CPU unit test) over its own target.
 // Matching is exact byte equality: no IUPAC equalities here (unlike the demux kernels).
@@ -10,6 +10,7 @@
 // longer queries keep it in a global scratch slice per workgroup ([word][lane], coalesced).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 
 #include "smx_internal.h"
 #include "smx_mine_core.h"
@@ -41,61 +42,27 @@ __device__ void mine_build_peq(const unsigned char *qs, int m, int W, int Wp, u6
     __syncthreads();
 }
 
-template <int WR>
+// The work is the chunk list of (job, query) pairs, pair p owning chunks [chunk_start[p], chunk_start[p + 1]) =
+// MINE_THREADS targets each.  Workgroup b takes the contiguous chunks [b * per_block, (b + 1) * per_block): one pair
+// search per workgroup, the Peq table rebuilt only when the query changes, and workgroups short enough that the
+// hardware balances their uneven cost.  What a lane does with its distance d is the output mode:
+//   DIST = false (best identity): it turns d into the pair's identity contribution (mine_identity) and, if that is
+//     > 0, raises out[job.best_off + t] with a 64-bit atomic max on the bit pattern (non-negative doubles order like
+//     their patterns; out starts at +0.0).
+//   DIST = true (distances): it stores d at out[job.dist_off + (q - job.q0) * job.nt + t], job by job row-major.
+template <bool DIST> using MineOut = std::conditional_t<DIST, int32_t, unsigned long long>;
+
+template <int WR, bool DIST>
 __global__ __launch_bounds__(MINE_THREADS) void mine_kernel(const unsigned char *__restrict__ qbytes,
                                                             const uint64_t *__restrict__ qoff,
                                                             const unsigned char *__restrict__ tbytes,
                                                             const uint64_t *__restrict__ toff,
                                                             const int32_t *__restrict__ tlen,
-                                                            const MineItem *__restrict__ items, uint32_t n_items,
-                                                            int32_t *__restrict__ dist, u64 *scratch, int scratch_words) {
-    extern __shared__ u64 lds[];
-    unsigned short *rowmap = reinterpret_cast<unsigned short *>(lds);     // 512 B
-    unsigned *present = reinterpret_cast<unsigned *>(lds + 64);           // 1 KiB
-    u64 *peq = lds + MINE_LDS_HEAD;
-    for (uint32_t it = blockIdx.x; it < n_items; it += gridDim.x) {
-        const MineItem I = items[it];
-        const uint64_t q0 = qoff[I.q];
-        const int m = (int)(qoff[I.q + 1] - q0);
-        const int W = (m + 63) >> 6, Wp = W | 1;
-        __syncthreads();                           // the previous item's lanes are done with the table
-        mine_build_peq(qbytes + q0, m, W, Wp, peq, rowmap, present);
-        const unsigned lane = threadIdx.x;
-        if (lane < I.nt) {
-            const uint32_t ti = I.t0 + lane;
-            int d;
-            if constexpr (WR > 0) {
-                RegState<WR> st;
-                d = mine_pair<WR>(st, peq, rowmap, m, W, Wp, I.k, tbytes + toff[ti], tlen[ti]);
-            } else {
-                u64 *base = scratch + (size_t)blockIdx.x * 3 * scratch_words * MINE_THREADS;
-                GlobalState st{base + lane, base + (size_t)scratch_words * MINE_THREADS + lane,
-                               reinterpret_cast<int *>(base + (size_t)2 * scratch_words * MINE_THREADS) + lane};
-                d = mine_pair<0>(st, peq, rowmap, m, W, Wp, I.k, tbytes + toff[ti], tlen[ti]);
-            }
-            dist[I.out + lane] = d;
-        }
-    }
-}
-
-// Best identity without a distance matrix (smx_mine_best_identity_fused).  The work is the chunk list of (job, query)
-// pairs, pair p owning chunks [chunk_start[p], chunk_start[p + 1]) = MINE_THREADS targets each.  Workgroup b takes
-// the contiguous chunks [b * per_block, (b + 1) * per_block): one pair search per workgroup, the Peq table rebuilt
-// only when the query changes, and workgroups short enough that the hardware balances their uneven cost.  Each lane
-// turns its distance
-// into the pair's identity contribution (mine_identity) and, if that is > 0, raises best[job.best_off + t] with a
-// 64-bit atomic max on the bit pattern (non-negative doubles order like their patterns; best starts at +0.0).
-template <int WR>
-__global__ __launch_bounds__(MINE_THREADS) void mine_fused_kernel(const unsigned char *__restrict__ qbytes,
-                                                                  const uint64_t *__restrict__ qoff,
-                                                                  const unsigned char *__restrict__ tbytes,
-                                                                  const uint64_t *__restrict__ toff,
-                                                                  const int32_t *__restrict__ tlen,
-                                                                  const MineFusedPair *__restrict__ pairs,
-                                                                  const uint64_t *__restrict__ chunk_start, uint32_t n_pairs,
-                                                                  const MineJobDev *__restrict__ jobs,
-                                                                  uint64_t per_block, unsigned long long *best, u64 *scratch,
-                                                                  int scratch_words) {
+                                                            const MinePair *__restrict__ pairs,
+                                                            const uint64_t *__restrict__ chunk_start, uint32_t n_pairs,
+                                                            const MineJobDev *__restrict__ jobs,
+                                                            uint64_t per_block, MineOut<DIST> *out, u64 *scratch,
+                                                            int scratch_words) {
     extern __shared__ u64 lds[];
     unsigned short *rowmap = reinterpret_cast<unsigned short *>(lds);     // 512 B
     unsigned *present = reinterpret_cast<unsigned *>(lds + 64);           // 1 KiB
@@ -118,7 +85,7 @@ __global__ __launch_bounds__(MINE_THREADS) void mine_fused_kernel(const unsigned
     const unsigned lane = threadIdx.x;
     for (uint64_t v = lo; v < hi; v++) {
         while (chunk_start[p + 1] <= v) p++;
-        const MineFusedPair P = pairs[p];
+        const MinePair P = pairs[p];
         const MineJobDev J = jobs[P.job];
         const uint32_t c0 = (uint32_t)(v - chunk_start[p]) * MINE_THREADS;   // first target of the chunk in the job
         const uint64_t q0 = qoff[P.q];
@@ -141,116 +108,43 @@ __global__ __launch_bounds__(MINE_THREADS) void mine_fused_kernel(const unsigned
                                reinterpret_cast<int *>(sbase + (size_t)2 * scratch_words * MINE_THREADS) + lane};
                 d = mine_pair<0>(st, peq, rowmap, m, W, Wp, P.k, tbytes + toff[ti], tlen[ti]);
             }
-            const double identity = mine_identity(d, m, J.min_identity);
-            if (identity > 0.0) atomicMax(&best[J.best_off + c0 + lane], (unsigned long long)__double_as_longlong(identity));
+            if constexpr (DIST) {
+                out[J.dist_off + (uint64_t)(P.q - J.q0) * J.nt + c0 + lane] = d;
+            } else {
+                const double identity = mine_identity(d, m, J.min_identity);
+                if (identity > 0.0) atomicMax(&out[J.best_off + c0 + lane], (unsigned long long)__double_as_longlong(identity));
+            }
         }
     }
 }
 
-// best identity per (job, target): max over the job's queries of 1 - d / m among d != -1, identity >= min_identity
-// and identity > 0 (the reference's loop: best starts at 0 and only grows), in IEEE double.
-__global__ void mine_best_kernel(const MineJobDev *__restrict__ jobs, uint32_t n_jobs, const uint64_t *__restrict__ qoff,
-                                 const int32_t *__restrict__ dist, double *__restrict__ best, uint64_t n_out) {
-    const uint64_t g = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (g >= n_out) return;
-    uint32_t lo = 0, hi = n_jobs;                  // the job whose [best_off, best_off + nt) holds g
-    while (hi - lo > 1) {
-        const uint32_t mid = (lo + hi) / 2;
-        if (jobs[mid].best_off <= g) lo = mid; else hi = mid;
-    }
-    const MineJobDev J = jobs[lo];
-    const uint32_t t = (uint32_t)(g - J.best_off);
-    double b = 0.0;
-    for (uint32_t i = 0; i < J.nq; i++) {
-        const int d = dist[J.dist_off + (uint64_t)i * J.nt + t];
-        if (d == -1) continue;
-        const double m = (double)(qoff[J.q0 + i + 1] - qoff[J.q0 + i]);
-        const double identity = 1.0 - (double)d / m;
-        if (identity >= J.min_identity && identity > b) b = identity;
-    }
-    best[g] = b;
-}
-
 }  // namespace smx
 
-extern "C" int smx_launch_mine(void *stream, int wr, const unsigned char *d_q, const uint64_t *d_qoff,
+extern "C" int smx_launch_mine(void *stream, int wr, int dist, const unsigned char *d_q, const uint64_t *d_qoff,
                                const unsigned char *d_t, const uint64_t *d_toff, const int32_t *d_tlen,
-                               const void *d_items, uint32_t n_items, int grid, size_t lds_bytes, int32_t *d_dist,
+                               const void *d_pairs, const uint64_t *d_chunk_start, uint32_t n_pairs,
+                               const void *d_jobs, int grid, uint64_t per_block, size_t lds_bytes, void *d_out,
                                unsigned long long *d_scratch, int scratch_words) {
     using namespace smx;
+#define SMX_MINE_FN(WR) (dist ? (const void *)mine_kernel<WR, true> : (const void *)mine_kernel<WR, false>)
     const void *fn;
     switch (wr) {
-        case 1: fn = (const void *)mine_kernel<1>; break;
-        case 2: fn = (const void *)mine_kernel<2>; break;
-        case 4: fn = (const void *)mine_kernel<4>; break;
-        case 8: fn = (const void *)mine_kernel<8>; break;
-        case 16: fn = (const void *)mine_kernel<16>; break;
-        case 0: fn = (const void *)mine_kernel<0>; break;
+        case 1: fn = SMX_MINE_FN(1); break;
+        case 2: fn = SMX_MINE_FN(2); break;
+        case 4: fn = SMX_MINE_FN(4); break;
+        case 8: fn = SMX_MINE_FN(8); break;
+        case 16: fn = SMX_MINE_FN(16); break;
+        case 0: fn = SMX_MINE_FN(0); break;
         default: return (int)hipErrorInvalidValue;
     }
-    if (lds_bytes > 65536) {
-        hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-        if (e != hipSuccess) return (int)e;
-    }
-    const MineItem *items = (const MineItem *)d_items;
-    hipStream_t s = (hipStream_t)stream;
-    switch (wr) {
-        case 1: hipLaunchKernelGGL(mine_kernel<1>, dim3(grid), dim3(MINE_THREADS), lds_bytes, s, d_q, d_qoff, d_t, d_toff, d_tlen, items, n_items, d_dist, d_scratch, scratch_words); break;
-        case 2: hipLaunchKernelGGL(mine_kernel<2>, dim3(grid), dim3(MINE_THREADS), lds_bytes, s, d_q, d_qoff, d_t, d_toff, d_tlen, items, n_items, d_dist, d_scratch, scratch_words); break;
-        case 4: hipLaunchKernelGGL(mine_kernel<4>, dim3(grid), dim3(MINE_THREADS), lds_bytes, s, d_q, d_qoff, d_t, d_toff, d_tlen, items, n_items, d_dist, d_scratch, scratch_words); break;
-        case 8: hipLaunchKernelGGL(mine_kernel<8>, dim3(grid), dim3(MINE_THREADS), lds_bytes, s, d_q, d_qoff, d_t, d_toff, d_tlen, items, n_items, d_dist, d_scratch, scratch_words); break;
-        case 16: hipLaunchKernelGGL(mine_kernel<16>, dim3(grid), dim3(MINE_THREADS), lds_bytes, s, d_q, d_qoff, d_t, d_toff, d_tlen, items, n_items, d_dist, d_scratch, scratch_words); break;
-        default: hipLaunchKernelGGL(mine_kernel<0>, dim3(grid), dim3(MINE_THREADS), lds_bytes, s, d_q, d_qoff, d_t, d_toff, d_tlen, items, n_items, d_dist, d_scratch, scratch_words); break;
-    }
-    return (int)hipGetLastError();
-}
-
-extern "C" int smx_launch_mine_fused(void *stream, int wr, const unsigned char *d_q, const uint64_t *d_qoff,
-                                     const unsigned char *d_t, const uint64_t *d_toff, const int32_t *d_tlen,
-                                     const void *d_pairs, const uint64_t *d_chunk_start, uint32_t n_pairs,
-                                     const void *d_jobs, int grid, uint64_t per_block, size_t lds_bytes,
-                                     unsigned long long *d_best,
-                                     unsigned long long *d_scratch, int scratch_words) {
-    using namespace smx;
-    const void *fn;
-    switch (wr) {
-        case 1: fn = (const void *)mine_fused_kernel<1>; break;
-        case 2: fn = (const void *)mine_fused_kernel<2>; break;
-        case 4: fn = (const void *)mine_fused_kernel<4>; break;
-        case 8: fn = (const void *)mine_fused_kernel<8>; break;
-        case 16: fn = (const void *)mine_fused_kernel<16>; break;
-        case 0: fn = (const void *)mine_fused_kernel<0>; break;
-        default: return (int)hipErrorInvalidValue;
-    }
+#undef SMX_MINE_FN
     if (n_pairs == 0 || grid < 1 || per_block < 1) return (int)hipErrorInvalidValue;
     if (lds_bytes > 65536) {
         hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
         if (e != hipSuccess) return (int)e;
     }
-    const MineFusedPair *pairs = (const MineFusedPair *)d_pairs;
-    const MineJobDev *jobs = (const MineJobDev *)d_jobs;
-    hipStream_t s = (hipStream_t)stream;
-#define SMX_MINE_FUSED(WR) hipLaunchKernelGGL(mine_fused_kernel<WR>, dim3(grid), dim3(MINE_THREADS), lds_bytes, s, d_q, d_qoff, \
-                                              d_t, d_toff, d_tlen, pairs, d_chunk_start, n_pairs, jobs, per_block, d_best, \
-                                              d_scratch, scratch_words)
-    switch (wr) {
-        case 1: SMX_MINE_FUSED(1); break;
-        case 2: SMX_MINE_FUSED(2); break;
-        case 4: SMX_MINE_FUSED(4); break;
-        case 8: SMX_MINE_FUSED(8); break;
-        case 16: SMX_MINE_FUSED(16); break;
-        default: SMX_MINE_FUSED(0); break;
-    }
-#undef SMX_MINE_FUSED
-    return (int)hipGetLastError();
-}
-
-extern "C" int smx_launch_mine_best(void *stream, const void *d_jobs, uint32_t n_jobs, const uint64_t *d_qoff,
-                                    const int32_t *d_dist, double *d_best, uint64_t n_out) {
-    if (n_out == 0) return 0;
-    const unsigned threads = 256;
-    const unsigned grid = (unsigned)((n_out + threads - 1) / threads);
-    hipLaunchKernelGGL(smx::mine_best_kernel, dim3(grid), dim3(threads), 0, (hipStream_t)stream,
-                       (const smx::MineJobDev *)d_jobs, n_jobs, d_qoff, d_dist, d_best, n_out);
-    return (int)hipGetLastError();
+    // in the order of mine_kernel's parameters; every pointer is passed as the pointer it is
+    void *args[] = {&d_q, &d_qoff, &d_t, &d_toff, &d_tlen, &d_pairs, &d_chunk_start, &n_pairs, &d_jobs, &per_block,
+                    &d_out, &d_scratch, &scratch_words};
+    return (int)hipLaunchKernel(fn, dim3(grid), dim3(MINE_THREADS), args, lds_bytes, (hipStream_t)stream);
 }

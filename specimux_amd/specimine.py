@@ -5,7 +5,7 @@ src/specimux/specimine.py, entry cli.py:113-116).
 For one specimen's `full/` FASTQ, the partial reads of its forward / reverse barcode (`partial/<pool>/...`) are
 kept if they align to one of the specimen's full reads with identity >= --min-identity, where identity is
 1 - d / len(full) and d is the HW (infix) edit distance of the full read in the partial read, limited to
-k = int(len(full) * (1 - min_identity)).  Every distance is computed on the GPU (smx_mine_best_identity_fused, HIP kernel
+k = int(len(full) * (1 - min_identity)).  Every distance is computed on the GPU (smx_mine_best_identity, HIP kernel
 smx_mine.hip); there is no CPU path.  The output `<fastq>.mined` holds the mined partial records with the title
 `{id}_mined_{type}_{best:.2f} {title} mined_{type} identity={best:.2f}`.
 
@@ -60,8 +60,10 @@ def extract_specimen_id(fastq_path: str) -> str:
     return match.group(1)
 
 
-def find_barcodes(specimen_id: str, index_file: str) -> Tuple[Optional[str], Optional[str]]:
-    """(forward, reverse) barcode of the first index row of the specimen, upper-cased; (None, None) if none."""
+def read_index(index_file: str) -> Dict[str, Tuple[str, str]]:
+    """specimen id -> (forward, reverse) barcode, upper-cased, from one read of the index: columns SampleID / FwIndex /
+    RvIndex by header name (else 0 / 2 / 4), rows too short for them skipped, the first row of a specimen wins."""
+    table: Dict[str, Tuple[str, str]] = {}
     with open(index_file, "r") as fh:
         header = next(fh).strip().split("\t")
         sample_idx = header.index("SampleID") if "SampleID" in header else 0
@@ -70,10 +72,22 @@ def find_barcodes(specimen_id: str, index_file: str) -> Tuple[Optional[str], Opt
         need = max(sample_idx, fwd_idx, rev_idx)
         for line in fh:
             fields = line.strip().split("\t")
-            if len(fields) > need and fields[sample_idx] == specimen_id:
-                return fields[fwd_idx].upper(), fields[rev_idx].upper()
+            if len(fields) > need and fields[sample_idx] not in table:
+                table[fields[sample_idx]] = (fields[fwd_idx].upper(), fields[rev_idx].upper())
+    return table
+
+
+def _barcodes(table: Dict[str, Tuple[str, str]], specimen_id: str) -> Tuple[Optional[str], Optional[str]]:
+    """find_barcodes on read_index's table."""
+    if specimen_id in table:
+        return table[specimen_id]
     logging.error(f"Could not find specimen {specimen_id} in index file")
     return None, None
+
+
+def find_barcodes(specimen_id: str, index_file: str) -> Tuple[Optional[str], Optional[str]]:
+    """(forward, reverse) barcode of the first index row of the specimen, upper-cased; (None, None) if none."""
+    return _barcodes(read_index(index_file), specimen_id)
 
 
 def detect_input_level(fastq_path: str) -> Tuple[str, str, Optional[str]]:
@@ -198,137 +212,101 @@ def _plan(lookup, fastq, partial_forward, no_partial_reverse, min_identity) -> O
     return MineJob(fastq, partial_files, min_identity)
 
 
-def _best_identities(groups, kernel_ms=None) -> List[np.ndarray]:
-    """groups: [(full_seqs, partial_seqs, min_identity)] -> per group the best identity of every partial read, all
-    groups in one device call (smx_mine_best_identity)."""
+def _best_identity(queries: List[bytes], ks: List[int], targets: List[bytes], djobs, kernel_ms=None) -> np.ndarray:
+    """One smx_mine_best_identity call: the full reads (queries) with their limits k (max_distance), the partial reads
+    (targets) and the device jobs (q0, nq, t0, nt, min_identity).  Returns the best identity of every job's targets,
+    job after job."""
     from . import _lib
     lib = _lib.load()
-    qparts, tparts, qlens, tlens = [], [], [], []
-    jobs = np.zeros(len(groups), dtype=_lib.MINE_JOB_DTYPE)
-    k = []
-    nq = nt = 0
-    for g, (fulls, partials, min_identity) in enumerate(groups):
-        jobs[g] = (nq, len(fulls), nt, len(partials), min_identity)
-        for s in fulls:
-            b = s.encode("latin-1")
-            qparts.append(b)
-            qlens.append(len(b))
-            k.append(max_distance(len(b), min_identity))
-        for s in partials:
-            b = s.encode("latin-1")
-            tparts.append(b)
-            tlens.append(len(b))
-        nq += len(fulls)
-        nt += len(partials)
-    qoff = np.zeros(nq + 1, dtype=np.uint64)
-    qoff[1:] = np.cumsum(qlens, dtype=np.uint64)
-    toff = np.zeros(nt + 1, dtype=np.uint64)
-    toff[1:] = np.cumsum(tlens, dtype=np.uint64)
+    jarr = np.array(djobs, dtype=_lib.MINE_JOB_DTYPE)
+    qoff = np.zeros(len(queries) + 1, dtype=np.uint64)
+    qoff[1:] = np.cumsum([len(q) for q in queries], dtype=np.uint64)
+    toff = np.zeros(len(targets) + 1, dtype=np.uint64)
+    toff[1:] = np.cumsum([len(t) for t in targets], dtype=np.uint64)
     # a negative k means "no limit"; a limit that does not fit 32 bits is no limit either (d <= len(full) always)
-    karr = np.array([min(x, 2**31 - 1) if x >= 0 else -1 for x in k], dtype=np.int32)
-    best = np.zeros(max(nt, 1), dtype=np.float64)
+    karr = np.array([min(k, 2**31 - 1) if k >= 0 else -1 for k in ks], dtype=np.int32)
+    best = np.zeros(max(int(jarr["nt"].sum()), 1), dtype=np.float64)
     ms = _lib.C.c_float(0.0)
-    _lib.check(lib.smx_mine_best_identity(b"".join(qparts), _lib.ptr(qoff), nq, _lib.ptr(karr), b"".join(tparts),
-                                          _lib.ptr(toff), nt, _lib.ptr(jobs), len(groups), _lib.ptr(best),
-                                          _lib.C.byref(ms)))
+    _lib.check(lib.smx_mine_best_identity(b"".join(queries), _lib.ptr(qoff), len(queries), _lib.ptr(karr),
+                                          b"".join(targets), _lib.ptr(toff), len(targets), _lib.ptr(jarr), len(djobs),
+                                          _lib.ptr(best), _lib.C.byref(ms)))
     if kernel_ms is not None:
         kernel_ms.append(ms.value)
-    out, at = [], 0
-    for fulls, partials, _ in groups:
-        out.append(best[at:at + len(partials)])
-        at += len(partials)
-    return out
+    return best
 
 
-def _mine_call(jobs: Sequence[MineJob], kernel_ms=None, fused: bool = True) -> List[Optional[int]]:
-    """Mine every job in one device call and write each job's `<fastq>.mined`.  Returns the mined count per job, None
-    for a job whose full file holds no records (it gets the empty `.mined` the single CLI writes).
+def _mine(jobs: Sequence[MineJob], kernel_ms=None):
+    """Mine every job in one device call.  Yields per job its mined (title, record) pairs in the reference's order
+    (types in dict order, files in discovery order, records in file order), or None for a job whose full file holds
+    no records; logs each job as the single CLI does.
 
     Every partial file is read and uploaded once, however many jobs select it; a device job is one specimen's full
     reads x one partial file (the best identity of a partial read depends only on the specimen's full reads), the
-    forward and reverse jobs of a specimen share its query range.  fused=False: the two-step entry with its distance
-    matrix (smx_mine_best_identity), for comparison; the results are the same bit for bit."""
-    from . import _lib
-    lib = _lib.load()
+    forward and reverse jobs of a specimen share its query range."""
     files: Dict[str, int] = {}                     # partial file -> index in `parts`
     parts: List[List[SeqRecord]] = []
-    fulls_of, qparts, qlens, karr, tparts, tlens, djobs = [], [], [], [], [], [], []
+    fulls_of, queries, ks, targets, djobs = [], [], [], [], []
     t_at: List[int] = []                           # first target of each partial file
-    nq = nt = 0
     for job in jobs:
         fulls = read_fastq(job.fastq)
         fulls_of.append(fulls)
         if not fulls:
             continue
-        q0 = nq
+        q0 = len(queries)
         for r in fulls:
-            b = r.seq.encode("latin-1")
-            qparts.append(b)
-            qlens.append(len(b))
-            k = max_distance(len(b), job.min_identity)
-            # a negative k means "no limit"; a limit that does not fit 32 bits is no limit either (d <= len(full) always)
-            karr.append(min(k, 2**31 - 1) if k >= 0 else -1)
-        nq += len(fulls)
+            queries.append(r.seq.encode("latin-1"))
+            ks.append(max_distance(len(queries[-1]), job.min_identity))
         for flist in job.partial_files.values():
             for f in flist:
                 if f not in files:
                     files[f] = len(parts)
-                    recs = read_fastq(f)
-                    parts.append(recs)
-                    t_at.append(nt)
-                    for r in recs:
-                        b = r.seq.encode("latin-1")
-                        tparts.append(b)
-                        tlens.append(len(b))
-                    nt += len(recs)
+                    parts.append(read_fastq(f))
+                    t_at.append(len(targets))
+                    targets.extend(r.seq.encode("latin-1") for r in parts[-1])
                 i = files[f]
                 djobs.append((q0, len(fulls), t_at[i], len(parts[i]), job.min_identity))
-    best = np.zeros(0, dtype=np.float64)
-    if djobs:
-        jarr = np.array(djobs, dtype=_lib.MINE_JOB_DTYPE)
-        qoff = np.zeros(nq + 1, dtype=np.uint64)
-        qoff[1:] = np.cumsum(qlens, dtype=np.uint64)
-        toff = np.zeros(nt + 1, dtype=np.uint64)
-        toff[1:] = np.cumsum(tlens, dtype=np.uint64)
-        best = np.zeros(max(int(jarr["nt"].sum()), 1), dtype=np.float64)
-        ms = _lib.C.c_float(0.0)
-        entry = lib.smx_mine_best_identity_fused if fused else lib.smx_mine_best_identity
-        _lib.check(entry(b"".join(qparts), _lib.ptr(qoff), nq, _lib.ptr(np.array(karr, dtype=np.int32)), b"".join(tparts),
-                         _lib.ptr(toff), nt, _lib.ptr(jarr), len(djobs), _lib.ptr(best), _lib.C.byref(ms)))
-        if kernel_ms is not None:
-            kernel_ms.append(ms.value)
-    counts: List[Optional[int]] = []
+    best = _best_identity(queries, ks, targets, djobs, kernel_ms) if djobs else np.zeros(0, dtype=np.float64)
     at = 0                                         # next job's first output
     for job, fulls in zip(jobs, fulls_of):
-        out = []
         if not fulls:
             logging.error(f"No sequences found in full match file: {job.fastq}")
-        else:
-            logging.info(f"Loaded {len(fulls)} sequences from full match file")
-            for ptype, flist in job.partial_files.items():
-                logging.info(f"Processing {ptype} partial matches from {len(flist)} file(s)")
-                n_total = sum(len(parts[files[f]]) for f in flist)
-                logging.info(f"Found {n_total} sequences across all {ptype} partial match files")
-                match_count = 0
-                for f in flist:
-                    recs = parts[files[f]]
-                    for rec, b in zip(recs, best[at:at + len(recs)]):
-                        if b > 0:
-                            match_count += 1
-                            out.append(format_record(mined_title(rec, ptype, float(b)), rec))
-                    at += len(recs)
-                logging.info(f"Matched {match_count}/{n_total} sequences from {ptype} partial matches")
+            yield None
+            continue
+        logging.info(f"Loaded {len(fulls)} sequences from full match file")
+        mined = []
+        for ptype, flist in job.partial_files.items():
+            logging.info(f"Processing {ptype} partial matches from {len(flist)} file(s)")
+            n_total = sum(len(parts[files[f]]) for f in flist)
+            logging.info(f"Found {n_total} sequences across all {ptype} partial match files")
+            match_count = 0
+            for f in flist:
+                recs = parts[files[f]]
+                for rec, b in zip(recs, best[at:at + len(recs)]):
+                    if b > 0:
+                        match_count += 1
+                        mined.append((mined_title(rec, ptype, float(b)), rec))
+                at += len(recs)
+            logging.info(f"Matched {match_count}/{n_total} sequences from {ptype} partial matches")
+        yield mined
+
+
+def _mine_call(jobs: Sequence[MineJob], kernel_ms=None) -> List[Optional[int]]:
+    """Mine every job in one device call (_mine) and write each job's `<fastq>.mined`.  Returns the mined count per
+    job, None for a job whose full file holds no records (it gets the empty `.mined` the single CLI writes)."""
+    counts: List[Optional[int]] = []
+    for job, mined in zip(jobs, _mine(jobs, kernel_ms)):
+        out = [format_record(title, rec) for title, rec in mined or []]
         logging.info(f"Found {len(out)} mined sequences")
         with open(job.output, "w", encoding="latin-1") as fh:
             fh.write("".join(out))
         logging.info(f"Wrote {len(out)} sequences to {job.output}")
-        counts.append(len(out) if fulls else None)
+        counts.append(None if mined is None else len(out))
     return counts
 
 
-def mine_specimens(jobs: Sequence[MineJob], kernel_ms=None, fused: bool = True) -> List[int]:
+def mine_specimens(jobs: Sequence[MineJob], kernel_ms=None) -> List[int]:
     """Mine every job in one device call and write each job's `<fastq>.mined`; returns the mined count per job."""
-    return [c or 0 for c in _mine_call(jobs, kernel_ms, fused)]
+    return [c or 0 for c in _mine_call(jobs, kernel_ms)]
 
 
 # ------------------------------------------------------------------------------------------------ whole-run mining
@@ -359,23 +337,6 @@ def discover_specimens(output_dir: str, level: str = "pool") -> List[str]:
             if name.endswith(".fastq") and not name.startswith("primers.") and os.path.isfile(path):
                 out.append(path)
     return out
-
-
-def read_index(index_file: str) -> Dict[str, Tuple[str, str]]:
-    """specimen id -> (forward, reverse) barcode, upper-cased: find_barcodes for every specimen in one read of the
-    index (the same columns and row filter; the first matching row wins)."""
-    table: Dict[str, Tuple[str, str]] = {}
-    with open(index_file, "r") as fh:
-        header = next(fh).strip().split("\t")
-        sample_idx = header.index("SampleID") if "SampleID" in header else 0
-        fwd_idx = header.index("FwIndex") if "FwIndex" in header else 2
-        rev_idx = header.index("RvIndex") if "RvIndex" in header else 4
-        need = max(sample_idx, fwd_idx, rev_idx)
-        for line in fh:
-            fields = line.strip().split("\t")
-            if len(fields) > need and fields[sample_idx] not in table:
-                table[fields[sample_idx]] = (fields[fwd_idx].upper(), fields[rev_idx].upper())
-    return table
 
 
 def job_partials(job: MineJob) -> List[str]:
@@ -485,18 +446,12 @@ def mine_run(output_dir: str, index: str, level: str = "pool", partial_forward: 
     this rank's specimens plus (every rank) the specimens that could not be planned."""
     fastqs = discover_specimens(output_dir, level)
     table = read_index(index)
-
-    def lookup(sid):
-        if sid in table:
-            return table[sid]
-        logging.error(f"Could not find specimen {sid} in index file")
-        return None, None
-
     quiet = rank != 0                              # every rank plans the whole run; rank 0 logs it
     if quiet:
         logging.disable(logging.CRITICAL)
     try:
-        planned = [_plan(lookup, f, partial_forward, no_partial_reverse, min_identity) for f in fastqs]
+        planned = [_plan(lambda sid: _barcodes(table, sid), f, partial_forward, no_partial_reverse, min_identity)
+                   for f in fastqs]
     finally:
         if quiet:
             logging.disable(logging.NOTSET)
@@ -576,22 +531,7 @@ def mine_sequences(full_match_file: str, partial_match_files: Dict[str, List[str
                    min_identity: float) -> List[Tuple[str, SeqRecord]]:
     """The mined records of one specimen as (title, record) pairs, in the reference's order (types in dict order,
     files in discovery order, records in file order)."""
-    fulls = read_fastq(full_match_file)
-    if not fulls:
-        logging.error(f"No sequences found in full match file: {full_match_file}")
-        return []
-    logging.info(f"Loaded {len(fulls)} sequences from full match file")
-    types = [(t, [r for f in files for r in read_fastq(f)]) for t, files in partial_match_files.items()]
-    best = _best_identities([([r.seq for r in fulls], [r.seq for r in p], min_identity) for _, p in types])
-    mined = []
-    for (ptype, partials), b in zip(types, best):
-        n = 0
-        for rec, ident in zip(partials, b):
-            if ident > 0:
-                n += 1
-                mined.append((mined_title(rec, ptype, float(ident)), rec))
-        logging.info(f"Matched {n}/{len(partials)} sequences from {ptype} partial matches")
-    return mined
+    return next(_mine([MineJob(full_match_file, partial_match_files, min_identity)])) or []
 
 
 def main(argv=None):

@@ -210,20 +210,22 @@ def test_band_at_class_boundaries():
 
 
 def test_generic_class_grid_stride():
-    """More class-0 items than twice the grid cap, so that workgroups loop: each one rebuilds its LDS Peq for queries of
-    other lengths and reuses its scratch slice."""
+    """More class-0 chunks than MINE_BLOCK_CHUNKS times the grid cap, so that the cap binds and workgroups take longer
+    runs: each one rebuilds its LDS Peq for queries of other lengths and reuses its scratch slice."""
     rng = random.Random(22)
-    long_q = rand_seq(rng, 16400)
-    # smx_api.cpp, mine_run: grid0 = min(items, 256 MiB / slice), slice = 3 * W_max * MINE_THREADS * 8 bytes
+    long_q = rand_seq(rng, 130972)
+    # smx_api.cpp, mine_call: cap = 256 MiB / slice, slice = 3 * W_max * MINE_THREADS * 8 bytes;
+    # per_block = max(MINE_BLOCK_CHUNKS, ceil(chunks / cap)), one chunk per query here (1-3 targets each)
     w_max = (len(long_q) + 63) // 64
     cap = (256 << 20) // (3 * w_max * 128 * 8)
-    assert 300 <= cap <= 400
+    assert 40 <= cap <= 45
     queries, ks, targets, jobs = [], [], [], []
-    n_q = 2 * cap + 30
+    n_q = 10 * cap + 30
     for i in range(n_q):
-        if i == n_q // 2:
-            q, tl = long_q, [rand_seq(rng, 40) + mutate(rng, long_q, 0.05) + rand_seq(rng, 40)]
-            k = int(0.15 * len(q))
+        if i == n_q // 2:   # short targets: the oracle's O(m n) stays cheap; k = -1 runs all 2047 words of the band
+            s0 = rng.randrange(len(long_q) - 400)
+            q, tl = long_q, [rand_seq(rng, 40) + mutate(rng, long_q[s0:s0 + 300], 0.05), long_q[s0:s0 + 400]]
+            k = -1
         else:
             q = rand_seq(rng, rng.randrange(1025, 1401))
             tl = [mutate(rng, q, rng.uniform(0.02, 0.12)) for _ in range(rng.randrange(1, 4))]
@@ -234,8 +236,9 @@ def test_generic_class_grid_stride():
         queries.append(q)
         ks.append(k)
         targets.extend(tl)
-    n_items = len(queries)   # every query has 1-3 targets: one work item each, all in the generic class (W > 16)
-    assert all((len(q) + 63) // 64 > 16 for q in queries) and n_items > 2 * cap
+    n_chunks = len(queries)   # every query has 1-3 targets: one chunk each, all in the generic class (W > 16)
+    per_block = max(8, -(-n_chunks // cap))
+    assert all((len(q) + 63) // 64 > 16 for q in queries) and per_block > 8
     assert len({(len(q) + 63) // 64 for q in queries}) >= 5
     rc, got = mine_raw(queries, ks, targets, jobs)
     assert rc == _lib.OK, _lib.load().smx_last_error()
@@ -246,7 +249,7 @@ def test_generic_class_grid_stride():
 
 
 def lds_table_bytes(m, rows):
-    """LDS bytes of a query's Peq table (smx_api.cpp, mine_run): MINE_LDS_HEAD words + (rows + 1) x (W | 1) words."""
+    """LDS bytes of a query's Peq table (smx_api.cpp, mine_call): MINE_LDS_HEAD words + (rows + 1) x (W | 1) words."""
     return (192 + (rows + 1) * (((m + 63) // 64) | 1)) * 8
 
 
@@ -512,6 +515,9 @@ def test_mine_specimens_equals_one_run_per_specimen(tmp_path):
         single[f] = run_cli(f, index, True, False, 0.8)
         os.remove(f + ".mined")
     jobs = [specimine.plan_job(index, f, True, False, 0.8) for f in fastqs]
+    for job in jobs:
+        mined = specimine.mine_sequences(job.fastq, job.partial_files, 0.8)
+        assert "".join(specimine.format_record(title, rec) for title, rec in mined) == single[job.fastq]
     specimine.mine_specimens(jobs)
     for f in fastqs:
         with open(f + ".mined", encoding="latin-1") as fh:

@@ -1,5 +1,5 @@
-"""specimine at run scale on the GPU: smx_mine_best_identity_fused against smx_mine_best_identity bit for bit, and
---run-dir / mine_run against one single-file CLI run per specimen (whole trees, a small budget, shards)."""
+"""specimine at run scale on the GPU: smx_mine_best_identity against a host reduction of smx_mine_distances bit for
+bit, and --run-dir / mine_run against one single-file CLI run per specimen (whole trees, a small budget, shards)."""
 import os
 import random
 import shutil
@@ -33,7 +33,9 @@ def mutate(rng, s, rate, alphabet="ACGT"):
 
 
 def best_both(queries, ks, targets, jobs):
-    """(two-step best, fused best) of one job set, each output filled with a sentinel first."""
+    """(host best, device best) of one job set.  Host: the reference's expression, 1.0 - d / m in float64 over
+    smx_mine_distances' matrix, with d != -1, identity >= min_identity and identity > 0, the maximum per (job, target)
+    starting at 0.  Device: smx_mine_best_identity.  Each output is filled with a sentinel first."""
     lib = _lib.load()
     qb = [q.encode("latin-1") for q in queries]
     tb = [t.encode("latin-1") for t in targets]
@@ -42,23 +44,32 @@ def best_both(queries, ks, targets, jobs):
     jarr = np.array(jobs, dtype=_lib.MINE_JOB_DTYPE)
     karr = np.array(ks, dtype=np.int32)
     n_out = int(jarr["nt"].sum()) if len(jobs) else 0
-    out = []
-    for entry in (lib.smx_mine_best_identity, lib.smx_mine_best_identity_fused):
-        best = np.full(max(n_out, 1), np.nan)
-        _lib.check(entry(b"".join(qb), _lib.ptr(qoff), len(qb), _lib.ptr(karr), b"".join(tb), _lib.ptr(toff), len(tb),
-                         _lib.ptr(jarr), len(jobs), _lib.ptr(best), None))
-        out.append(best[:n_out])
-    return out
+    n_dist = int((jarr["nq"].astype(np.int64) * jarr["nt"]).sum()) if len(jobs) else 0
+    args = (b"".join(qb), _lib.ptr(qoff), len(qb), _lib.ptr(karr), b"".join(tb), _lib.ptr(toff), len(tb), _lib.ptr(jarr),
+            len(jobs))
+    dist = np.full(max(n_dist, 1), -7, dtype=np.int32)
+    _lib.check(lib.smx_mine_distances(*args, _lib.ptr(dist), None))
+    best = np.full(max(n_out, 1), np.nan)
+    _lib.check(lib.smx_mine_best_identity(*args, _lib.ptr(best), None))
+    m = np.array([len(q) for q in qb], dtype=np.float64)
+    host, at = [], 0
+    for q0, nq, t0, nt, mi in jobs:
+        d = dist[at:at + nq * nt].reshape(nq, nt)
+        at += nq * nt
+        identity = 1.0 - d / m[q0:q0 + nq, None]
+        ok = (d != -1) & (identity >= mi) & (identity > 0)
+        host.append(np.where(ok, identity, 0.0).max(axis=0, initial=0.0))
+    return (np.concatenate(host) if host else np.zeros(0)), best[:n_out]
 
 
 def assert_same(queries, ks, targets, jobs):
-    two, fused = best_both(queries, ks, targets, jobs)
-    bad = np.nonzero(two.view(np.uint64) != fused.view(np.uint64))[0]
-    assert bad.size == 0, f"{bad.size} of {two.size} differ: {[(float(two[i]), float(fused[i])) for i in bad[:10]]}"
-    return two
+    want, got = best_both(queries, ks, targets, jobs)
+    bad = np.nonzero(want.view(np.uint64) != got.view(np.uint64))[0]
+    assert bad.size == 0, f"{bad.size} of {want.size} differ: {[(float(want[i]), float(got[i])) for i in bad[:10]]}"
+    return want
 
 
-def test_fused_random_overlapping_jobs():
+def test_best_random_overlapping_jobs():
     rng = random.Random(41)
     base = [rand_seq(rng, rng.randrange(40, 400)) for _ in range(20)]
     queries = [mutate(rng, rng.choice(base), rng.uniform(0, 0.1)) for _ in range(300)]
@@ -76,21 +87,21 @@ def test_fused_random_overlapping_jobs():
     assert (want > 0).sum() > 1000 and (want == 0).sum() > 1000
 
 
-def test_fused_empty_targets_and_empty_jobs():
+def test_best_empty_targets_and_empty_jobs():
     rng = random.Random(42)
     q = rand_seq(rng, 150)
     targets = ["", mutate(rng, q, 0.05), "", q[:20], ""]
     want = assert_same([q, q[:70]], [-1, 10], targets, [(0, 2, 0, 5, 0.0), (0, 1, 0, 1, 0.0), (1, 1, 4, 1, 0.0)])
     assert want[0] == 0.0 and want[1] > 0.9     # an empty target costs the whole query: identity 0
-    two, fused = best_both([q], [5], ["", ""], [(0, 0, 0, 2, 0.0), (0, 1, 0, 0, 0.0)])
-    assert two.size == fused.size == 2 and not fused.any()
-    two, fused = best_both([q], [5], [], [])
-    assert fused.size == 0
-    two, fused = best_both([q], [5], [q], [(0, 1, 1, 0, 0.0)])
-    assert fused.size == 0
+    want, got = best_both([q], [5], ["", ""], [(0, 0, 0, 2, 0.0), (0, 1, 0, 0, 0.0)])
+    assert want.size == got.size == 2 and not got.any()
+    want, got = best_both([q], [5], [], [])
+    assert got.size == 0
+    want, got = best_both([q], [5], [q], [(0, 1, 1, 0, 0.0)])
+    assert got.size == 0
 
 
-def test_fused_every_register_class_and_generic():
+def test_best_every_register_class_and_generic():
     rng = random.Random(43)
     queries, ks, targets, jobs = [], [], [], []
     for m in (1, 63, 64, 65, 128, 129, 256, 257, 512, 513, 1024, 1025, 2100):
@@ -105,7 +116,7 @@ def test_fused_every_register_class_and_generic():
     assert (want > 0).sum() > 100
 
 
-def test_fused_thresholds_at_the_edges():
+def test_best_thresholds_at_the_edges():
     # the pinned case: m = 5, min_identity 0.2, k = int(5 * 0.8) = 4; d = 4 is within k but identity 0.19999999999999996
     q = "ACGTA"
     k = specimine.max_distance(5, 0.2)
@@ -127,7 +138,7 @@ def test_fused_thresholds_at_the_edges():
     assert_same(queries, [specimine.max_distance(len(q), 0.8) for q in queries], targets, jobs)
 
 
-def test_fused_many_queries_on_one_target():
+def test_best_many_queries_on_one_target():
     """Thousands of qualifying pairs raise the same few best slots at once: the atomic max must keep the largest."""
     rng = random.Random(45)
     t = rand_seq(rng, 600)

@@ -8,9 +8,9 @@ extrapolated.  The comparator is that DP, not edlib (edlib is not installed), so
     python tools/specimine_bench.py [--specimens 96 --full 300 --partial 300 --length 650 --min-identity 0.85]
 
 --run: the whole-run mode.  A plate-grid tree (specimens share forward barcodes, --fwd-groups of them) is mined with
-`specimine.mine_run` (what `--run-dir` runs); one JSON line: end-to-end seconds of mine_run, the fused kernel's
-pairs/s next to the two-step path (distance matrix + reduction) on the same device jobs, and the device memory each
-path takes, measured in a fresh child process per path (device free bytes before / after, workspaces are grow-only)."""
+`specimine.mine_run` (what `--run-dir` runs); one JSON line: end-to-end seconds of mine_run, the kernel time and
+pairs/s of all its device jobs in one call, and the device memory that call takes, measured in a fresh child process
+(device free bytes before / after, workspaces are grow-only)."""
 import argparse
 import json
 import os
@@ -37,7 +37,7 @@ def main():
     ap.add_argument("--workdir", default=None)
     ap.add_argument("--run", action="store_true", help="whole-run mode (see the module doc)")
     ap.add_argument("--fwd-groups", type=int, default=8, help="--run: forward barcodes shared by the specimens")
-    ap.add_argument("--peak", choices=("fused", "two-step"), default=None, help=argparse.SUPPRESS)
+    ap.add_argument("--peak", action="store_true", help=argparse.SUPPRESS)
     a = ap.parse_args()
     if a.peak:
         return peak_child(a)
@@ -103,14 +103,14 @@ def run_jobs(root, min_identity):
 
 
 def peak_child(a):
-    """One path over every job of the tree in one call, in a fresh process: device bytes it took."""
+    """Every job of the tree in one call, in a fresh process: device bytes it took."""
     import ctypes as C
     import torch
     lib = _lib.load()
     _lib.check(lib.smx_device_init(0, C.byref(C.c_int(0))))
     jobs = run_jobs(a.workdir, a.min_identity)
     free0, _ = torch.cuda.mem_get_info(0)
-    specimine._mine_call(jobs, fused=a.peak == "fused")
+    specimine._mine_call(jobs)
     free1, _ = torch.cuda.mem_get_info(0)
     print(json.dumps({"peak_device_bytes": free0 - free1}))
 
@@ -129,32 +129,24 @@ def run_mode(a):
         nf = len(specimine.read_fastq(job.fastq))
         pairs += nf * sum(len(specimine.read_fastq(f)) for f in specimine.job_partials(job))
     specimine._mine_call(jobs[:1])                             # warm-up: code objects, workspace
-    specimine._mine_call(jobs[:1], fused=False)
-    e2e, kms = [], {"fused": [], "two-step": []}
+    e2e, kms = [], []
     for _ in range(a.repeats):
         ms = []
         t0 = time.perf_counter()
-        res = specimine.mine_run(root, index, "pool", True, False, a.min_identity, kernel_ms=ms)
+        res = specimine.mine_run(root, index, "pool", True, False, a.min_identity)
         e2e.append(time.perf_counter() - t0)
-        for name, fused in (("fused", True), ("two-step", False)):
-            ms = []
-            specimine._mine_call(jobs, kernel_ms=ms, fused=fused)
-            kms[name].append(sum(ms))
-    peak = {}
-    for name in ("fused", "two-step"):
-        r = subprocess.run([sys.executable, os.path.abspath(__file__), "--peak", name, "--workdir", root,
-                            "--min-identity", repr(a.min_identity)], capture_output=True, text=True, timeout=900)
-        peak[name] = json.loads(r.stdout.strip().splitlines()[-1])["peak_device_bytes"] if r.returncode == 0 else None
-    fused_ms, two_ms = min(kms["fused"]), min(kms["two-step"])
+        specimine._mine_call(jobs, kernel_ms=ms)
+        kms.append(sum(ms))
+    r = subprocess.run([sys.executable, os.path.abspath(__file__), "--peak", "--workdir", root,
+                        "--min-identity", repr(a.min_identity)], capture_output=True, text=True, timeout=900)
+    peak = json.loads(r.stdout.strip().splitlines()[-1])["peak_device_bytes"] if r.returncode == 0 else None
+    k_ms = min(kms)
     print(json.dumps({
         "bench": "specimine_run", "specimens": len(ids), "fwd_groups": a.fwd_groups, "full_per_specimen": a.full,
         "partial_per_file": a.partial, "read_length": a.length, "min_identity": a.min_identity,
         "pairs": pairs, "mined_specimens": res["mined"], "mined_records": res["reads"],
         "run_dir_e2e_s": round(min(e2e), 3),
-        "fused_kernel_ms": round(fused_ms, 3), "fused_pairs_per_s": round(pairs / (fused_ms / 1e3), 1),
-        "two_step_kernel_ms": round(two_ms, 3), "two_step_pairs_per_s": round(pairs / (two_ms / 1e3), 1),
-        "fused_peak_device_bytes": peak["fused"], "two_step_peak_device_bytes": peak["two-step"],
-        "distance_matrix_bytes": 4 * pairs,
+        "kernel_ms": round(k_ms, 3), "pairs_per_s": round(pairs / (k_ms / 1e3), 1), "peak_device_bytes": peak,
     }))
 
 
