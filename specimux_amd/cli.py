@@ -61,6 +61,11 @@ def build_parser() -> argparse.ArgumentParser:
 def parse_args(argv):
     parser = build_parser()
     args = parser.parse_args(argv[1:])
+    return split_num_seqs(parser, args)
+
+
+def split_num_seqs(parser, args):
+    """-n N / -n start,num -> args.start_seq, args.num_seqs (a parser error otherwise)."""
     text = args.num_seqs
     try:
         if "," in text:
@@ -113,6 +118,13 @@ def specimine_main(argv=None):
     """Entry point of the specimine tool (reference cli.py:113-116); also `python -m specimux_amd.specimine`."""
     from . import specimine
     specimine.main(argv)
+
+
+def watch_main(argv=None):
+    """Entry point of the live-run watcher (reference: watch.py:408-447, `specimux-watch`); also
+    `python -m specimux_amd.watch`.  argv as for main(); returns the exit status."""
+    from . import watch
+    return watch.main(argv)
 
 
 if __name__ == "__main__":

@@ -79,19 +79,23 @@ class Lane:
         self.packed_stride = int(self._lib.smx_packed_stride(panel.handle))
         self.packed = self.windows.reshape(-1)[:self.max_reads * self.packed_stride].reshape(self.max_reads, self.packed_stride)
         self.n = 0
+        self.busy = False   # a submitted batch not yet waited for
 
     def submit(self, n):
         self.n = int(n)
         _lib.check(self._lib.smx_lane_submit(self.handle, self.n))
+        self.busy = True
 
     def submit_packed(self, n):
         """The staging holds 4-bit windows (Batch.pack_windows4_into(..., lane.packed, lane.lens))."""
         self.n = int(n)
         _lib.check(self._lib.smx_lane_submit_packed(self.handle, self.n))
+        self.busy = True
 
     def wait(self, counts):
         """-> (ops, extra) numpy views; `counts` (uint64, panel.counts_len) is accumulated into."""
         ops_p, extra_p, n_extra = C.c_void_p(), C.c_void_p(), C.c_uint32()
+        self.busy = False   # smx_lane_wait retires the batch whatever it returns
         _lib.check(self._lib.smx_lane_wait(self.handle, C.byref(ops_p), C.byref(extra_p), C.byref(n_extra), _lib.ptr(counts)))
         if self.n == 0:
             return np.zeros(0, dtype=_lib.OP_DTYPE), np.zeros(0, dtype=_lib.OP_DTYPE)
@@ -101,6 +105,12 @@ class Lane:
         else:
             extra = np.zeros(0, dtype=_lib.OP_DTYPE)
         return ops, extra
+
+    def drain(self):
+        """Retire a batch left in flight by a run that stopped early (its results are dropped), so that the lane takes the
+        next submit.  Raises SmxError if the batch failed on the device."""
+        if self.busy:
+            self.wait(np.zeros(self.panel.counts_len, dtype=np.uint64))
 
     def close(self):
         if self.handle:

@@ -233,6 +233,32 @@ def _finish(total, matched, start):
     logging.info(f"Elapsed time: {timeit.default_timer() - start:.2f} seconds")
 
 
+def _wrap_up(args, total, matched, start):
+    """The end of a `-F` run: the two summary lines, empty directories pruned, --sample-topq, lock files removed."""
+    _finish(total, matched, start)
+    cleanup_empty_directories(args.output_dir)
+    if getattr(args, "sample_topq", 0) > 0:
+        subsample_top_quality(args.output_dir, args.sample_topq)
+    cleanup_locks(args.output_dir)
+
+
+def _stream_file(args, panel, start, lanes=None):
+    from .pipeline import run_streaming
+    total, matched, _counts, _fq = run_streaming(args.sequence_file, panel, args.output_dir, args.output_file_prefix,
+                                                 start_seq=args.start_seq, num_seqs=args.num_seqs, lanes=lanes)
+    _wrap_up(args, total, matched, start)
+
+
+def run_native_file(args, specimens, panel, lanes=None):
+    """One `-F` file on one GPU through a panel compiled beforehand (and lanes kept by the caller, if given): the output
+    tree, log lines and counts of `_run_native` without the loading (specimux_amd/watch.py runs every file of a live run
+    through one resident panel)."""
+    from .io_utils import detect_file_format
+    args.isfastq = detect_file_format(args.sequence_file) == "fastq"
+    create_output_files(args, specimens)
+    _stream_file(args, panel, timeit.default_timer(), lanes)
+
+
 def _run_native(args):
     """`-F`: native reader -> GPU -> native writer, overlapped (specimux_amd/pipeline.py)."""
     from .demultiplex import compiled_panel   # needs libsmx.so: import late so --help works without it
@@ -266,25 +292,16 @@ def _run_native(args):
         if rank == 0:
             logging.info(f"Demultiplexed on {world} GPUs (read-sharded by " + ("batch striding inside the -n window" if window
                          else "byte range") + ", counts summed by all-reduce)")
-            _finish(total, matched, start)
-            cleanup_empty_directories(args.output_dir)
-            if getattr(args, "sample_topq", 0) > 0:
-                subsample_top_quality(args.output_dir, args.sample_topq)
-            cleanup_locks(args.output_dir)
+            _wrap_up(args, total, matched, start)
         return
-    total, matched, _counts, _fq = run_streaming(args.sequence_file, panel, args.output_dir, args.output_file_prefix,
-                                                 start_seq=args.start_seq, num_seqs=args.num_seqs)
-    _finish(total, matched, start)
-    cleanup_empty_directories(args.output_dir)
-    if getattr(args, "sample_topq", 0) > 0:
-        subsample_top_quality(args.output_dir, args.sample_topq)
-    cleanup_locks(args.output_dir)
+    _stream_file(args, panel, start)
 
 
-def _run_records(args, to_files: bool):
-    """Record-object path (stdout mode, --color): Python parser + process_sequences + OutputManager."""
+def _run_records(args, to_files: bool, loaded=None):
+    """Record-object path (stdout mode, --color): Python parser + process_sequences + OutputManager.
+    `loaded` = what _load(args) returns, when the caller has it already (specimux_amd/watch.py)."""
     from .demultiplex import process_sequences
-    specimens, parameters, prefilter = _load(args)
+    specimens, parameters, prefilter = loaded if loaded is not None else _load(args)
     if to_files:   # `-F -d`: trace events need record objects, but the input still comes through the native reader
         from .io_utils import native_sequence_records
         seq_records = native_sequence_records(args.sequence_file, args)

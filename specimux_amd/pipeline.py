@@ -31,15 +31,33 @@ FIRST_BATCH_READS = 32768     # the first batch is small: the writer (the longes
 N_LANES = 3
 
 
+def make_lanes(panel, n=N_LANES):
+    """The lanes run_streaming drives, for a caller that keeps them across runs (run_streaming(..., lanes=...))."""
+    lanes = []
+    try:
+        for _ in range(n):
+            lanes.append(Lane(panel, BATCH_READS))
+    except BaseException:
+        for ln in lanes:
+            ln.close()
+        raise
+    return lanes
+
+
 def run_streaming(sequence_file, panel, output_dir, prefix, start_seq=1, num_seqs=-1, on_batch=None, byte_range=None,
-                  stats=None, stride=None):
+                  stats=None, stride=None, lanes=None):
     """Returns (total_reads, matched_reads, counts vector, is_fastq).  `stats` (dict), if given, receives the stage
-    seconds: read, pack, submit, gpu_wait (main thread blocked on a lane), write, close, wall."""
+    seconds: read, pack, submit, gpu_wait (main thread blocked on a lane), write, close, wall.
+    `lanes` (make_lanes(panel)), if given, are used instead of N_LANES new ones and are not destroyed: the run returns or
+    raises with none of them holding a batch in flight."""
+    own_lanes = lanes is None
+    if not own_lanes and any(ln.panel is not panel for ln in lanes):
+        raise ValueError("run_streaming: the lanes belong to another panel")
     reader = Reader(sequence_file, byte_range=byte_range)
     keep_batch = [0]   # stride = (rank, world): batch i belongs to rank i % world (inputs that cannot be cut by byte range)
     writer = Writer(output_dir, prefix, reader.is_fastq, panel)
     counts = np.zeros(panel.counts_len, dtype=np.uint64)
-    lanes = []
+    lanes = [] if own_lanes else list(lanes)
     free_lanes, q_gpu, q_out = queue.Queue(), queue.Queue(maxsize=N_LANES), queue.Queue(maxsize=N_LANES)
     errors = []
     ascii_lanes = bool(os.environ.get("SMX_LANES_ASCII"))   # A/B and test hook: ship 8-bit windows
@@ -138,9 +156,13 @@ def run_streaming(sequence_file, panel, output_dir, prefix, start_seq=1, num_seq
     tr.start()
     try:
         # the lanes (pinned staging, device buffers, a stream each) are created while the reader parses its first batch
-        for _ in range(N_LANES):
-            lanes.append(Lane(panel, BATCH_READS))
-            free_lanes.put(lanes[-1])
+        if own_lanes:
+            for _ in range(N_LANES):
+                lanes.append(Lane(panel, BATCH_READS))
+                free_lanes.put(lanes[-1])
+        else:
+            for ln in lanes:
+                free_lanes.put(ln)
         while True:
             item = q_gpu.get()
             if item is None:
@@ -184,17 +206,28 @@ def run_streaming(sequence_file, panel, output_dir, prefix, start_seq=1, num_seq
             writer.close()
         except Exception:
             pass
+        if own_lanes:
+            for ln in lanes:
+                try:
+                    ln.close()
+                except Exception:
+                    pass
+            raise errors[0]
+        # the caller keeps the lanes: retire what the error left in flight, so that the next run can submit to them; a
+        # device error found there outranks the error that stopped the run
         for ln in lanes:
             try:
-                ln.close()
-            except Exception:
-                pass
+                ln.drain()
+            except _lib.SmxError as e:
+                if e.code == _lib.ERR_DEVICE:
+                    raise e from errors[0]
         raise errors[0]
     t0 = time.perf_counter()
     writer.close()
     timing["close"] = time.perf_counter() - t0
-    for ln in lanes:
-        ln.close()
+    if own_lanes:
+        for ln in lanes:
+            ln.close()
     tr.join()
     timing["wall"] = time.perf_counter() - t_start
     if int(counts[_lib.CNT_TOTAL]) != n_delivered[0]:
