@@ -45,7 +45,7 @@ typedef enum {
     SMX_ERR_ARG = -1,      /* bad argument / inconsistent descriptor */
     SMX_ERR_UNSUPPORTED = -2, /* panel outside the kernel's limits (pattern > 64 nt, ...) */
     SMX_ERR_DEVICE = -3,   /* HIP error or no device */
-    SMX_ERR_OVERFLOW = -4  /* the extra-record buffer was too small (retry with the reported size), or one read produced more than 65535 write operations (n_ops is 16 bits) */
+    SMX_ERR_OVERFLOW = -4  /* the extra-record buffer was too small (retry with the reported size), or one read produced more than 65535 write operations (n_ops is 16 bits), or the statistics table filled up (smx_stats_read) */
 } smx_status;
 
 /* trim modes (constants.py:40-45) and dereplication strategies (:48-51) */
@@ -303,6 +303,54 @@ int smx_mine_distances(const char *queries, const uint64_t *qoff, uint32_t n_que
 int smx_mine_best_identity(const char *queries, const uint64_t *qoff, uint32_t n_queries, const int32_t *k,
                            const char *targets, const uint64_t *toff, uint32_t n_targets, const smx_mine_job *jobs,
                            uint32_t n_jobs, double *best, float *kernel_ms);
+
+/*
+ * Match statistics (specimux-stats; reference trace_stats.py): the "pool -> primer pair -> outcome" tables counted on the
+ * device from what smx_batch_run_device leaves there -- the lean hit dump (d_hits without d_bdist) and the primary
+ * records -- instead of from a trace TSV.  Every row the reference's tool would build from a read's trace events (one
+ * per candidate match, or one synthesised row for a read without any) is packed into a 64-bit key and counted in an
+ * open-addressing hash table of (key, 64-bit count) in device memory that lives for the whole run.
+ *
+ * Key layout (bit 0 = least significant; names come back on the host from the panel):
+ *   [0, 2)    orientation: 0 unknown, 1 forward, 2 reverse
+ *   [2, 14)   1 + index of the attempted primer pair (pair_fwd / pair_rev / pair_pool order); 0 = the read has no
+ *             candidate (or was dropped by the length filter): every other field below is then 0 except `first`
+ *   14        forward primer matched          15        reverse primer matched
+ *   [16, 29)  1 + global index of the forward barcode (first of the tied best), 0 = none
+ *   [29, 42)  the same for the reverse barcode
+ *   [42, 45)  SMX_STATS_CLASS_*: the read-level resolution shared by the surviving candidates, or DISCARDED
+ *   45        first candidate of its read (the rows `--count-by sequences` counts)
+ * ~0 marks an empty slot.  Limits: n_pairs <= 4094, n_barcodes <= 8190 (smx_stats_create checks).
+ *
+ *   smx_stats_create            capacity = number of slots, rounded up to a power of two (>= 8)
+ *   smx_stats_accumulate_device asynchronous, ordered on `stream` behind the batch that produced d_hits / d_ops (both
+ *                               DEVICE pointers, n_reads * smx_hits_per_read() hits and n_reads records).  Reads whose
+ *                               primary record carries SMX_OPF_TRIM_EMPTY cannot be decided from the record; their
+ *                               indices go to d_fallback (fallback_cap uint32; may be NULL with cap 0) and
+ *                               *d_n_fallback (one uint32, WRITTEN by the call; may exceed fallback_cap, then only the
+ *                               first fallback_cap were stored) and they add nothing to the table: the host adds their rows.
+ *   smx_stats_read              waits for the device, then copies the occupied slots out (any order).  *n = number of
+ *                               distinct keys; SMX_ERR_ARG when cap < *n.  If any increment found the table full, the
+ *                               call fails with SMX_ERR_OVERFLOW, *dropped = the lost increments, and nothing is copied.
+ *   smx_stats_clear             empty the table (asynchronous on `stream`)
+ */
+enum { SMX_STATS_CLASS_UNKNOWN = 0, SMX_STATS_CLASS_FULL = 1, SMX_STATS_CLASS_PARTIAL_FWD = 2,
+       SMX_STATS_CLASS_PARTIAL_REV = 3, SMX_STATS_CLASS_MULTIPLE = 4, SMX_STATS_CLASS_DISCARDED = 5 };
+#define SMX_STATS_PAIR_SHIFT 2
+#define SMX_STATS_P1_SHIFT 14
+#define SMX_STATS_P2_SHIFT 15
+#define SMX_STATS_B1_SHIFT 16
+#define SMX_STATS_B2_SHIFT 29
+#define SMX_STATS_CLASS_SHIFT 42
+#define SMX_STATS_FIRST_SHIFT 45
+
+typedef struct smx_stats smx_stats;
+int smx_stats_create(const smx_panel *panel, uint32_t capacity, smx_stats **out);
+void smx_stats_destroy(smx_stats *stats);
+int smx_stats_accumulate_device(smx_stats *stats, void *stream, const smx_hit *d_hits, const smx_op *d_ops,
+                                uint32_t n_reads, uint32_t *d_fallback, uint32_t fallback_cap, uint32_t *d_n_fallback);
+int smx_stats_read(smx_stats *stats, uint64_t *keys, uint64_t *counts, uint32_t cap, uint32_t *n, uint64_t *dropped);
+int smx_stats_clear(smx_stats *stats, void *stream);
 
 /*
  * RCCL reduction of the per-specimen counts over xGMI (one communicator per process/GPU).

@@ -79,6 +79,11 @@ SYMBOLS = [
                                      C.POINTER(C.c_float)]),
     ("smx_mine_best_identity", C.c_int, [C.c_char_p, _P, C.c_uint32, _P, C.c_char_p, _P, C.c_uint32, _P, C.c_uint32, _P,
                                          C.POINTER(C.c_float)]),
+    ("smx_stats_create", C.c_int, [_P, C.c_uint32, C.POINTER(_P)]),
+    ("smx_stats_destroy", None, [_P]),
+    ("smx_stats_accumulate_device", C.c_int, [_P, _P, _P, _P, C.c_uint32, _P, C.c_uint32, _P]),
+    ("smx_stats_read", C.c_int, [_P, _P, _P, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]),
+    ("smx_stats_clear", C.c_int, [_P, _P]),
     ("smx_comm_unique_id", C.c_int, [_P]),
     ("smx_comm_init", C.c_int, [_P, C.c_int, C.c_int, C.POINTER(_P)]),
     ("smx_counts_allreduce", C.c_int, [_P, C.c_size_t, _P, _P]),

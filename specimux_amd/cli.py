@@ -127,5 +127,12 @@ def watch_main(argv=None):
     return watch.main(argv)
 
 
+def trace_main(argv=None):
+    """Entry point of the statistics tool (reference: trace_stats.py:608-697, `specimux-stats`); also
+    `python -m specimux_amd.trace_stats`.  argv without the program name; returns the exit status."""
+    from . import trace_stats
+    return trace_stats.main(argv)
+
+
 if __name__ == "__main__":
     main()

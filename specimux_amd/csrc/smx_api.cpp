@@ -17,6 +17,7 @@
 #include "smx_internal.h"
 #include "smx_prescan_core.h"
 #include "smx_barcode_core.h"
+#include "smx_stats_core.h"
 
 namespace {
 
@@ -1275,6 +1276,100 @@ int smx_lane_wait(smx_lane *L, const smx_op **ops, const smx_op **extra, uint32_
     if (extra) *extra = L->h_extra;
     if (L->h_counts[SMX_CNT_OVERFLOW])
         return fail(SMX_ERR_OVERFLOW, "%llu read(s) produced more than 65535 write operations", (unsigned long long)L->h_counts[SMX_CNT_OVERFLOW]);
+    return SMX_OK;
+}
+
+// ---- match statistics (smx_stats.hip, smx_stats_core.h)
+struct smx_stats {
+    smx_panel *panel = nullptr;
+    uint32_t cap = 0;
+    uint64_t *d_keys = nullptr, *d_counts = nullptr, *d_dropped = nullptr;   // one allocation: keys, counts, dropped
+    uint32_t *d_nfb_own = nullptr;                                         // fallback counter when the caller passes none
+};
+
+int smx_launch_stats(const smx::StatsPanel *P, void *stream, const smx_hit *d_hits, const smx_op *d_ops, uint32_t n_reads,
+                     uint64_t *d_keys, uint64_t *d_counts, uint32_t cap, uint64_t *d_dropped, uint32_t *d_fallback,
+                     uint32_t fallback_cap, uint32_t *d_n_fallback, int max_grid);   // smx_stats.hip
+
+int smx_stats_clear(smx_stats *S, void *stream) {
+    if (!S) return fail(SMX_ERR_ARG, "null argument");
+    HIP_TRY(hipMemsetAsync(S->d_keys, 0xff, (size_t)S->cap * 8, (hipStream_t)stream));
+    HIP_TRY(hipMemsetAsync(S->d_counts, 0, (size_t)S->cap * 8 + 16, (hipStream_t)stream));
+    return SMX_OK;
+}
+
+int smx_stats_create(const smx_panel *panel, uint32_t capacity, smx_stats **out) {
+    if (!panel || !out) return fail(SMX_ERR_ARG, "null argument");
+    smx_panel *P = const_cast<smx_panel *>(panel);
+    if (P->hp.NPAIR > 4094 || P->hp.NB > 8190)
+        return fail(SMX_ERR_UNSUPPORTED, "statistics keys hold at most 4094 primer pairs and 8190 barcodes (panel: %d, %d)",
+                    P->hp.NPAIR, P->hp.NB);
+    if (capacity > (1u << 28)) return fail(SMX_ERR_ARG, "statistics table capacity %u is above 2^28 slots", capacity);
+    int rc = ensure_device(P);
+    if (rc != SMX_OK) return rc;
+    uint32_t cap = 8;
+    while (cap < capacity) cap <<= 1;
+    smx_stats *S = new smx_stats();
+    S->panel = P;
+    S->cap = cap;
+    void *p = nullptr;
+    hipError_t e = hipMalloc(&p, (size_t)cap * 16 + 16);
+    if (e != hipSuccess) { delete S; return fail(SMX_ERR_DEVICE, "hipMalloc(statistics table): %s", hipGetErrorString(e)); }
+    S->d_keys = (uint64_t *)p;
+    S->d_counts = S->d_keys + cap;
+    S->d_dropped = S->d_counts + cap;
+    S->d_nfb_own = (uint32_t *)(S->d_dropped + 1);
+    rc = smx_stats_clear(S, nullptr);
+    if (rc == SMX_OK && hipStreamSynchronize(nullptr) != hipSuccess) rc = fail(SMX_ERR_DEVICE, "clearing the statistics table failed");
+    if (rc != SMX_OK) { (void)hipFree(p); delete S; return rc; }
+    *out = S;
+    return SMX_OK;
+}
+
+void smx_stats_destroy(smx_stats *S) {
+    if (!S) return;
+    if (S->d_keys) (void)hipFree(S->d_keys);
+    delete S;
+}
+
+int smx_stats_accumulate_device(smx_stats *S, void *stream, const smx_hit *d_hits, const smx_op *d_ops, uint32_t n_reads,
+                                uint32_t *d_fallback, uint32_t fallback_cap, uint32_t *d_n_fallback) {
+    if (!S || (n_reads && (!d_hits || !d_ops))) return fail(SMX_ERR_ARG, "null argument");
+    if (!d_fallback) fallback_cap = 0;
+    if (!d_n_fallback) d_n_fallback = S->d_nfb_own;
+    HIP_TRY(hipMemsetAsync(d_n_fallback, 0, 4, (hipStream_t)stream));
+    const smx::DevPanel &h = S->panel->hp;
+    smx::StatsPanel sp;
+    sp.NP = h.NP; sp.NPAIR = h.NPAIR; sp.preorient = h.preorient;
+    sp.pdir = h.pdir; sp.pair_f = h.pair_f; sp.pair_r = h.pair_r;
+    // grid-stride launch of `per_cu` workgroups per CU: fewer, longer workgroups combine more rows on chip before they
+    // touch the global table (SMX_STATS_BLOCKS_PER_CU: A/B hook of tools/stats_bench.py)
+    int per_cu = 2;   // tools/stats_bench.py --grid-sweep: 1, 2, 4, 8 are within 20% of each other; 2 is best or next to best on c2 and c3
+    if (const char *e = getenv("SMX_STATS_BLOCKS_PER_CU")) per_cu = std::max(1, atoi(e));
+    const int e = smx_launch_stats(&sp, stream, d_hits, d_ops, n_reads, S->d_keys, S->d_counts, S->cap, S->d_dropped,
+                                   d_fallback, fallback_cap, d_n_fallback, std::max(1, S->panel->n_cu) * per_cu);
+    if (e != 0) return fail(SMX_ERR_DEVICE, "statistics kernel launch: %s", hipGetErrorString((hipError_t)e));
+    return SMX_OK;
+}
+
+int smx_stats_read(smx_stats *S, uint64_t *keys, uint64_t *counts, uint32_t cap, uint32_t *n, uint64_t *dropped) {
+    if (!S || !n) return fail(SMX_ERR_ARG, "null argument");
+    HIP_TRY(hipDeviceSynchronize());
+    std::vector<uint64_t> h((size_t)S->cap * 2 + 1);
+    HIP_TRY(hipMemcpy(h.data(), S->d_keys, h.size() * 8, hipMemcpyDeviceToHost));
+    const uint64_t lost = h[(size_t)S->cap * 2];
+    if (dropped) *dropped = lost;
+    *n = 0;
+    if (lost)
+        return fail(SMX_ERR_OVERFLOW, "the statistics table (%u slots) is full: %llu increments found no slot; raise the "
+                    "capacity (--table-capacity)", S->cap, (unsigned long long)lost);
+    uint32_t used = 0;
+    for (uint32_t s = 0; s < S->cap; s++) used += h[s] != SMX_STATS_EMPTY;
+    *n = used;
+    if (used > cap || (used && (!keys || !counts))) return fail(SMX_ERR_ARG, "%u distinct keys do not fit the caller's %u", used, cap);
+    uint32_t at = 0;
+    for (uint32_t s = 0; s < S->cap; s++)
+        if (h[s] != SMX_STATS_EMPTY) { keys[at] = h[s]; counts[at] = h[(size_t)S->cap + s]; at++; }
     return SMX_OK;
 }
 
