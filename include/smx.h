@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define SMX_ABI_VERSION 5
+#define SMX_ABI_VERSION 6
 
 typedef enum {
     SMX_OK = 0,
@@ -351,6 +351,29 @@ int smx_stats_accumulate_device(smx_stats *stats, void *stream, const smx_hit *d
                                 uint32_t n_reads, uint32_t *d_fallback, uint32_t fallback_cap, uint32_t *d_n_fallback);
 int smx_stats_read(smx_stats *stats, uint64_t *keys, uint64_t *counts, uint32_t cap, uint32_t *n, uint64_t *dropped);
 int smx_stats_clear(smx_stats *stats, void *stream);
+
+/*
+ * Lanes that count: a lane with a statistics table attached leaves the rows of every batch in that table, in the same
+ * pass that produces the batch's records (an ordinary `-F` run then has its stats table as a by-product).
+ *   smx_lane_attach_stats   stats = NULL detaches.  SMX_ERR_ARG if `stats` was created on another panel or the lane holds a
+ *                           batch in flight.  The first attach allocates, for the life of the lane, a device buffer of
+ *                           max_reads * smx_hits_per_read() smx_hit and a 1 + max_reads uint32 fallback list (device, and
+ *                           a pinned copy); a lane that was never attached allocates nothing and enqueues exactly what
+ *                           it did before.  Attaching waits for the device, so a smx_stats_clear enqueued earlier on any
+ *                           stream is complete before the lane's first batch.  The table must outlive the attachment.
+ *   smx_lane_submit[_packed] with a table attached: the demux launch also gets the lane's hit buffer (no d_bdist: the
+ *                           panel's own kernel variant runs), smx_stats_accumulate_device follows on the lane's stream over
+ *                           the lane's records and hits, then the fallback count and indices are copied to the pinned list.
+ *                           Several lanes may count into one table at a time.
+ *   smx_lane_fallback       after smx_lane_wait, until the next submit on that lane: the batch's reads the device could
+ *                           not decide (smx_stats_accumulate_device's fallback list; any order), *idx pointing into the
+ *                           lane's pinned list.  Also valid when smx_lane_wait returned SMX_ERR_OVERFLOW: the rows of such
+ *                           a batch ARE in the table (counting needs the primary records only), so a caller that runs the
+ *                           batch again for its records must not count it again.  SMX_ERR_ARG if the retired batch was
+ *                           submitted without a table.
+ */
+int smx_lane_attach_stats(smx_lane *lane, smx_stats *stats);
+int smx_lane_fallback(smx_lane *lane, const uint32_t **idx, uint32_t *n);
 
 /*
  * RCCL reduction of the per-specimen counts over xGMI (one communicator per process/GPU).

@@ -9,7 +9,7 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SMX_LIB") or os.path.join(_HERE, "libsmx.so")   # SMX_LIB: A/B builds (tools/tune.sh)
 
-ABI_VERSION = 5
+ABI_VERSION = 6
 OK, ERR_ARG, ERR_UNSUPPORTED, ERR_DEVICE, ERR_OVERFLOW = 0, -1, -2, -3, -4
 TRIM = {"none": 0, "tails": 1, "barcodes": 2, "primers": 3}
 DEREP = {"none": 0, "best": 1}
@@ -84,6 +84,8 @@ SYMBOLS = [
     ("smx_stats_accumulate_device", C.c_int, [_P, _P, _P, _P, C.c_uint32, _P, C.c_uint32, _P]),
     ("smx_stats_read", C.c_int, [_P, _P, _P, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64)]),
     ("smx_stats_clear", C.c_int, [_P, _P]),
+    ("smx_lane_attach_stats", C.c_int, [_P, _P]),
+    ("smx_lane_fallback", C.c_int, [_P, C.POINTER(_P), C.POINTER(C.c_uint32)]),
     ("smx_comm_unique_id", C.c_int, [_P]),
     ("smx_comm_init", C.c_int, [_P, C.c_int, C.c_int, C.POINTER(_P)]),
     ("smx_counts_allreduce", C.c_int, [_P, C.c_size_t, _P, _P]),

@@ -7,6 +7,7 @@ import sys
 
 from . import __version__
 from .constants import MultipleMatchStrategy, TrimMode
+from .trace_stats import DEFAULT_TABLE_CAPACITY
 
 
 def version() -> str:
@@ -45,7 +46,17 @@ _OPTIONS = [
     (("-t", "--threads"), dict(_INT, default=-1, help="Number of worker threads to use")),
     (("--sample-topq",), dict(_INT, default=0, metavar="N",
                               help="Create subsample directories with top N sequences by average quality score (default: disabled)")),
+    # not in the reference: there the statistics come from a -d trace (specimux-stats out/trace ...)
+    (("--stats-table",), dict(default=None, metavar="FILE",
+                              help="With -F (and without -d): count the run's match statistics on the GPU in the same pass and write "
+                                   "them to FILE, for `specimux-stats --table FILE ...` (specimux-watch: one cumulative table for "
+                                   "the live run, rewritten after every file)")),
+    (("--stats-table-capacity",), dict(_INT, default=DEFAULT_TABLE_CAPACITY, metavar="N",
+                                       help=f"Slots of the device table behind --stats-table (default {DEFAULT_TABLE_CAPACITY}); "
+                                            "the run ends with status 1 and writes no table if it fills up")),
 ]
+# flags of this project that specimux-watch keeps for itself instead of handing them to every file's run
+WATCH_OWNED = ("stats_table", "stats_table_capacity")
 
 
 def build_parser() -> argparse.ArgumentParser:
@@ -61,7 +72,19 @@ def build_parser() -> argparse.ArgumentParser:
 def parse_args(argv):
     parser = build_parser()
     args = parser.parse_args(argv[1:])
+    check_stats_table(parser, args)
     return split_num_seqs(parser, args)
+
+
+def check_stats_table(parser, args):
+    """--stats-table belongs to the streaming `-F` path; runs with -d have a trace to count from, stdout runs have no lanes."""
+    if getattr(args, "stats_table", None):
+        if not args.output_to_files:
+            parser.error("--stats-table needs -F (it is counted by the streaming file path)")
+        if args.diagnostics:
+            parser.error("--stats-table cannot be combined with -d: such a run leaves a trace, use specimux-stats <output dir>/trace")
+        if args.stats_table_capacity < 1:
+            parser.error("--stats-table-capacity must be a positive number of slots")
 
 
 def split_num_seqs(parser, args):

@@ -1157,7 +1157,17 @@ struct smx_lane {
     smx_op *d_ops = nullptr, *d_extra = nullptr;
     uint64_t *d_counts = nullptr;   // same layout as h_counts
     bool busy = false;
+    // match statistics (smx_lane_attach_stats): allocated at the first attach, kept until the lane goes
+    smx_stats *stats = nullptr;
+    smx_hit *d_hits = nullptr;      // lean hit dump of the batch in flight
+    uint32_t *d_fb = nullptr;       // fallback count, then the indices
+    uint32_t *h_fb = nullptr;       // pinned copy of d_fb
+    bool counted = false;           // the batch in flight went into the table
+    bool fb_valid = false;          // h_fb describes the batch smx_lane_wait retired last
 };
+
+// the fallback indices that travel with every batch; smx_lane_fallback fetches the rest (trim-to-empty reads are rare)
+static uint32_t lane_fb_sent(const smx_lane *L) { return std::min<uint32_t>(L->cap, 4096u); }
 
 void smx_lane_destroy(smx_lane *L) {
     if (!L) return;
@@ -1176,6 +1186,9 @@ void smx_lane_destroy(smx_lane *L) {
     if (L->d_ops) (void)hipFree(L->d_ops);
     if (L->d_extra) (void)hipFree(L->d_extra);
     if (L->d_counts) (void)hipFree(L->d_counts);
+    if (L->d_hits) (void)hipFree(L->d_hits);
+    if (L->d_fb) (void)hipFree(L->d_fb);
+    if (L->h_fb) (void)hipHostFree(L->h_fb);
     if (L->stream) (void)hipStreamDestroy(L->stream);
     delete L;
 }
@@ -1222,6 +1235,8 @@ static int lane_submit(smx_lane *L, uint32_t n_reads, bool packed) {
     smx_panel *P = L->P;
     const size_t ncnt = smx_counts_len(P);
     L->n = n_reads;
+    L->counted = false;
+    L->fb_valid = false;
     HIP_TRY(hipMemsetAsync(L->d_counts, 0, (ncnt + 1) * 8, L->stream));
     if (n_reads) {
         if (packed) {   // the staging holds 4-bit windows: half the bytes over the link, unpacked into the ASCII layout on the device
@@ -1233,8 +1248,13 @@ static int lane_submit(smx_lane *L, uint32_t n_reads, bool packed) {
             HIP_TRY(hipMemcpyAsync(L->d_windows, L->h_windows, (size_t)n_reads * P->hp.wstride, hipMemcpyHostToDevice, L->stream));
         HIP_TRY(hipMemcpyAsync(L->d_lens, L->h_lens, (size_t)n_reads * 4, hipMemcpyHostToDevice, L->stream));
         int rc = smx_batch_run_device(P, L->stream, L->d_windows, L->d_lens, n_reads, L->d_ops, L->d_extra, L->cap,
-                                      (uint32_t *)(L->d_counts + ncnt), L->d_counts, nullptr, nullptr);
+                                      (uint32_t *)(L->d_counts + ncnt), L->d_counts, L->stats ? L->d_hits : nullptr, nullptr);
         if (rc) return rc;
+        if (L->stats) {   // the batch's rows go into the table behind its demux kernel; only the fallback list comes back
+            rc = smx_stats_accumulate_device(L->stats, L->stream, L->d_hits, L->d_ops, n_reads, L->d_fb + 1, L->cap, L->d_fb);
+            if (rc) return rc;
+            HIP_TRY(hipMemcpyAsync(L->h_fb, L->d_fb, (size_t)(1 + lane_fb_sent(L)) * 4, hipMemcpyDeviceToHost, L->stream));
+        }
         HIP_TRY(hipMemcpyAsync(L->h_ops, L->d_ops, (size_t)n_reads * sizeof(smx_op), hipMemcpyDeviceToHost, L->stream));
         // extra records are rare: the count is not known on the host yet, so a fixed small prefix travels with the batch and
         // smx_lane_wait fetches the rest if there is more
@@ -1242,6 +1262,10 @@ static int lane_submit(smx_lane *L, uint32_t n_reads, bool packed) {
                                hipMemcpyDeviceToHost, L->stream));
     }
     HIP_TRY(hipMemcpyAsync(L->h_counts, L->d_counts, (ncnt + 1) * 8, hipMemcpyDeviceToHost, L->stream));
+    if (L->stats) {
+        if (n_reads == 0) L->h_fb[0] = 0;   // nothing was enqueued that would write it
+        L->counted = true;
+    }
     L->busy = true;
     return SMX_OK;
 }
@@ -1260,6 +1284,7 @@ int smx_lane_wait(smx_lane *L, const smx_op **ops, const smx_op **extra, uint32_
             return fail(SMX_ERR_DEVICE, "lane batch failed: %s", hipGetErrorString(se));
         }
     }
+    L->fb_valid = L->counted;   // from here on, whatever this call returns: the batch's rows are in the table
     const uint32_t ne = (uint32_t)L->h_counts[ncnt];
     *n_extra = ne;
     if (L->h_counts[SMX_CNT_TOTAL] != L->n) {
@@ -1323,6 +1348,43 @@ int smx_stats_create(const smx_panel *panel, uint32_t capacity, smx_stats **out)
     if (rc == SMX_OK && hipStreamSynchronize(nullptr) != hipSuccess) rc = fail(SMX_ERR_DEVICE, "clearing the statistics table failed");
     if (rc != SMX_OK) { (void)hipFree(p); delete S; return rc; }
     *out = S;
+    return SMX_OK;
+}
+
+int smx_lane_attach_stats(smx_lane *L, smx_stats *S) {
+    if (!L) return fail(SMX_ERR_ARG, "null argument");
+    if (L->busy) return fail(SMX_ERR_ARG, "lane has a batch in flight: smx_lane_wait first");
+    if (S && S->panel != L->P) return fail(SMX_ERR_ARG, "the statistics table belongs to another panel");
+    if (!S) { L->stats = nullptr; return SMX_OK; }
+    HIP_TRY(hipSetDevice(L->P->device));
+    {   // first attach: the buffers stay with the lane (a failed attach leaves what it got to smx_lane_destroy)
+        const size_t hb = (size_t)L->cap * smx_hits_per_read(L->P) * sizeof(smx_hit), fb = ((size_t)L->cap + 1) * 4;
+        hipError_t e = hipSuccess;
+        if (!L->d_hits) e = hipMalloc((void **)&L->d_hits, hb);
+        if (e == hipSuccess && !L->d_fb) e = hipMalloc((void **)&L->d_fb, fb);
+        if (e == hipSuccess && !L->h_fb) e = hipHostMalloc((void **)&L->h_fb, fb, hipHostMallocDefault);
+        if (e != hipSuccess) return fail(SMX_ERR_DEVICE, "lane statistics buffers: %s", hipGetErrorString(e));
+    }
+    // the lane's stream does not wait for other streams: whatever was enqueued on the table before (smx_stats_clear on any
+    // stream) is complete before the lane's first batch counts into it
+    HIP_TRY(hipDeviceSynchronize());
+    L->stats = S;
+    return SMX_OK;
+}
+
+int smx_lane_fallback(smx_lane *L, const uint32_t **idx, uint32_t *n) {
+    if (!L || !idx || !n) return fail(SMX_ERR_ARG, "null argument");
+    *idx = nullptr;
+    *n = 0;
+    if (L->busy || !L->fb_valid) return fail(SMX_ERR_ARG, "no counted batch was retired on this lane since its last submit");
+    const uint32_t nf = L->h_fb[0], sent = lane_fb_sent(L);
+    if (nf > L->n) return fail(SMX_ERR_DEVICE, "statistics kernel reported %u fallback reads in a batch of %u", nf, L->n);
+    if (nf > sent) {   // the rest of the list
+        HIP_TRY(hipSetDevice(L->P->device));
+        HIP_TRY(hipMemcpy(L->h_fb + 1 + sent, L->d_fb + 1 + sent, (size_t)(nf - sent) * 4, hipMemcpyDeviceToHost));
+    }
+    *idx = L->h_fb + 1;
+    *n = nf;
     return SMX_OK;
 }
 

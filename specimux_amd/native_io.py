@@ -106,6 +106,20 @@ class Lane:
             extra = np.zeros(0, dtype=_lib.OP_DTYPE)
         return ops, extra
 
+    def attach_stats(self, device_stats):
+        """Count the rows of every following batch into `device_stats` (trace_stats.DeviceStats of this lane's panel) on the
+        lane's stream; None detaches.  The lane must not hold a batch in flight."""
+        _lib.check(self._lib.smx_lane_attach_stats(self.handle, device_stats.handle if device_stats is not None else None))
+
+    def fallback(self):
+        """Indices (numpy uint32, a copy) of the reads of the batch wait() retired last that the device could not decide.  Valid
+        after wait() -- also when it raised ERR_OVERFLOW for the extra-record buffer -- until the next submit."""
+        idx_p, n = C.c_void_p(), C.c_uint32()
+        _lib.check(self._lib.smx_lane_fallback(self.handle, C.byref(idx_p), C.byref(n)))
+        if not n.value:
+            return np.zeros(0, dtype=np.uint32)
+        return np.ctypeslib.as_array(C.cast(idx_p, C.POINTER(C.c_uint32)), shape=(n.value,)).copy()
+
     def drain(self):
         """Retire a batch left in flight by a run that stopped early (its results are dropped), so that the lane takes the
         next submit.  Raises SmxError if the batch failed on the device."""

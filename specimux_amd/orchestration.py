@@ -242,28 +242,54 @@ def _wrap_up(args, total, matched, start):
     cleanup_locks(args.output_dir)
 
 
-def _stream_file(args, panel, start, lanes=None):
+def _stream_file(args, panel, start, lanes=None, match_stats=None):
+    """One file through the streaming pipeline, then the end of the run.  With `match_stats` the run counts its match
+    statistics on the way; a device table that filled up (trace_stats.StatsTableFull) is raised again AFTER the wrap-up:
+    the tree is complete."""
     from .pipeline import run_streaming
-    total, matched, _counts, _fq = run_streaming(args.sequence_file, panel, args.output_dir, args.output_file_prefix,
-                                                 start_seq=args.start_seq, num_seqs=args.num_seqs, lanes=lanes)
+    from .trace_stats import StatsTableFull
+    full = None
+    try:
+        total, matched, _counts, _fq = run_streaming(args.sequence_file, panel, args.output_dir, args.output_file_prefix,
+                                                     start_seq=args.start_seq, num_seqs=args.num_seqs, lanes=lanes,
+                                                     match_stats=match_stats)
+    except StatsTableFull as e:
+        full = e
+        total, matched = e.result[:2]
     _wrap_up(args, total, matched, start)
+    if full is not None:
+        raise full
 
 
-def run_native_file(args, specimens, panel, lanes=None):
+def run_native_file(args, specimens, panel, lanes=None, match_stats=None):
     """One `-F` file on one GPU through a panel compiled beforehand (and lanes kept by the caller, if given): the output
     tree, log lines and counts of `_run_native` without the loading (specimux_amd/watch.py runs every file of a live run
-    through one resident panel)."""
+    through one resident panel).  `match_stats` (trace_stats.RunStats): the file's match statistics are counted on the way
+    and left in `match_stats.table`."""
     from .io_utils import detect_file_format
     args.isfastq = detect_file_format(args.sequence_file) == "fastq"
     create_output_files(args, specimens)
-    _stream_file(args, panel, timeit.default_timer(), lanes)
+    _stream_file(args, panel, timeit.default_timer(), lanes, match_stats)
+
+
+def _unlink_quietly(path):
+    try:
+        os.unlink(path)
+    except OSError:
+        pass
+
+
+def _stats_table_failed(path, e):
+    """--stats-table: a loud end.  The tree is complete and stays; no table file is written; exit status 1."""
+    import sys
+    logging.error(f"--stats-table {path}: not written: {e}")
+    sys.exit(1)
 
 
 def _run_native(args):
     """`-F`: native reader -> GPU -> native writer, overlapped (specimux_amd/pipeline.py)."""
     from .demultiplex import compiled_panel   # needs libsmx.so: import late so --help works without it
     from .io_utils import detect_file_format
-    from .pipeline import run_streaming
     specimens, parameters, prefilter = _load(args)
     args.isfastq = detect_file_format(args.sequence_file) == "fastq"
     from .distributed import env_rank
@@ -272,6 +298,25 @@ def _run_native(args):
         create_output_files(args, specimens)
     start = timeit.default_timer()
     panel = compiled_panel(specimens, parameters, args, prefilter)
+    table_path = getattr(args, "stats_table", None)
+    match_stats = None
+    if table_path:
+        # --stats-table: the lanes count the run's match statistics into a device table in the same pass
+        # (include/smx.h "Lanes that count"); every rank of a multi-GPU launch counts its own shard
+        from . import trace_stats
+        match_stats = trace_stats.RunStats(panel, parameters, specimens, args, prefilter is not None,
+                                           getattr(args, "stats_table_capacity", None))
+        if rank == 0:   # a table left by an earlier run must not pass for this run's if this one fails
+            _unlink_quietly(table_path)
+    try:
+        _run_native_panel(args, panel, rank, world, start, table_path, match_stats)
+    finally:
+        if match_stats is not None:
+            match_stats.close()
+
+
+def _run_native_panel(args, panel, rank, world, start, table_path, match_stats):
+    from .pipeline import run_streaming
     if world > 1:
         # one process per GPU (python -m torch.distributed.run ... -m specimux_amd.cli ...): the input file is cut
         # into byte ranges at record boundaries, every rank appends its records to the one output tree (or writes its own
@@ -281,20 +326,63 @@ def _run_native(args):
         # reads the whole file, applies the window, and keeps batch i iff i mod world == rank (batch striding).
         from .distributed import run_sharded
         window = args.start_seq > 1 or args.num_seqs >= 0
+        table_full = []
 
         def shard_runner(seqfile, out_dir, byte_range, stride):
-            t, m, c, _fq = run_streaming(seqfile, panel, out_dir, args.output_file_prefix, byte_range=byte_range, stride=stride,
-                                         start_seq=args.start_seq if window else 1, num_seqs=args.num_seqs if window else -1)
+            from . import trace_stats
+            if match_stats is not None:
+                match_stats.reset()   # a shard may be attempted twice (byte range, then batch striding)
+                table_full.clear()
+            try:
+                t, m, c, _fq = run_streaming(seqfile, panel, out_dir, args.output_file_prefix, byte_range=byte_range,
+                                             stride=stride, start_seq=args.start_seq if window else 1,
+                                             num_seqs=args.num_seqs if window else -1, match_stats=match_stats)
+            except trace_stats.StatsTableFull as e:   # the shard's records are written: the other ranks go on, this rank
+                table_full.append(e)                  # leaves no rank table, which fails the merge below
+                t, m, c, _fq = e.result
+            if match_stats is not None and not table_full:
+                # before the barrier that follows the shards: rank 0 merges the rank files by name afterwards, no collective
+                match_stats.table.save(trace_stats.rank_table_path(table_path, rank))
             return t, m, c
 
-        total, matched, _counts, _w = run_sharded(args.sequence_file, args.output_dir, args.output_file_prefix,
-                                                  panel.counts_len, shard_runner, window=window)
+        if match_stats is not None:
+            from . import trace_stats
+            # a stale rank table of a killed earlier run must not be merged into this one
+            _unlink_quietly(trace_stats.rank_table_path(table_path, rank))
+        try:
+            total, matched, _counts, _w = run_sharded(args.sequence_file, args.output_dir, args.output_file_prefix,
+                                                      panel.counts_len, shard_runner, window=window)
+        except BaseException:
+            if match_stats is not None:   # a failed run leaves no table and no rank table
+                _unlink_quietly(trace_stats.rank_table_path(table_path, rank))
+            raise
         if rank == 0:
             logging.info(f"Demultiplexed on {world} GPUs (read-sharded by " + ("batch striding inside the -n window" if window
                          else "byte range") + ", counts summed by all-reduce)")
             _wrap_up(args, total, matched, start)
+            if table_full:   # no rank table of this rank: drop the others', then the loud end below
+                for k in range(world):
+                    _unlink_quietly(trace_stats.rank_table_path(table_path, k))
+            elif match_stats is not None:
+                try:
+                    table = trace_stats.merge_rank_tables(table_path, world)
+                except Exception as e:   # a rank whose table filled up left none: it says so itself
+                    _stats_table_failed(table_path, e)
+                logging.info(f"Stats table {table_path}: {table.total('sequences'):,} reads counted, {len(table.counts):,} "
+                             f"distinct rows, host_replayed {table.host_replayed} ({world} rank tables merged)")
+        if table_full:
+            _stats_table_failed(table_path, table_full[0])
         return
-    _stream_file(args, panel, start)
+    if match_stats is None:
+        _stream_file(args, panel, start)
+        return
+    from .trace_stats import StatsTableFull
+    try:
+        _stream_file(args, panel, start, match_stats=match_stats)
+    except StatsTableFull as e:
+        _stats_table_failed(table_path, e)
+    match_stats.table.save(table_path)
+    logging.info(f"Stats table {table_path}: {match_stats.summary()}")
 
 
 def _run_records(args, to_files: bool, loaded=None):

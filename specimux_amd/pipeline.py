@@ -45,11 +45,17 @@ def make_lanes(panel, n=N_LANES):
 
 
 def run_streaming(sequence_file, panel, output_dir, prefix, start_seq=1, num_seqs=-1, on_batch=None, byte_range=None,
-                  stats=None, stride=None, lanes=None):
+                  stats=None, stride=None, lanes=None, match_stats=None):
     """Returns (total_reads, matched_reads, counts vector, is_fastq).  `stats` (dict), if given, receives the stage
     seconds: read, pack, submit, gpu_wait (main thread blocked on a lane), write, close, wall.
     `lanes` (make_lanes(panel)), if given, are used instead of N_LANES new ones and are not destroyed: the run returns or
-    raises with none of them holding a batch in flight."""
+    raises with none of them holding a batch in flight.
+    `match_stats` (trace_stats.RunStats of this panel: a DeviceStats `device`, a HostReplay `replay`, a StatsTable `table`),
+    if given, makes the run count its match statistics in the same pass: the lanes are attached to the device table for
+    the run (and detached on every way out), the reads the device cannot decide are replayed on the host while their batch
+    is alive, and at the end the device table is decoded into `match_stats.table`.  The tree does not depend on it.  A
+    device table that filled up raises trace_stats.StatsTableFull after the tree is complete and closed (`.result` = the
+    return value)."""
     own_lanes = lanes is None
     if not own_lanes and any(ln.panel is not panel for ln in lanes):
         raise ValueError("run_streaming: the lanes belong to another panel")
@@ -62,6 +68,27 @@ def run_streaming(sequence_file, panel, output_dir, prefix, start_seq=1, num_seq
     errors = []
     ascii_lanes = bool(os.environ.get("SMX_LANES_ASCII"))   # A/B and test hook: ship 8-bit windows
     timing = {"read": 0.0, "pack": 0.0, "submit": 0.0, "gpu_wait": 0.0, "write": 0.0, "close": 0.0}
+    if match_stats is not None:
+        timing["stats_replay"] = 0.0   # main thread: host replay of the fallback reads (outside gpu_wait)
+
+    def detach_stats():
+        if match_stats is not None:
+            for ln in lanes:
+                if ln.handle:
+                    ln.attach_stats(None)
+
+    def replay_fallback(b, lane):
+        # the reads whose primary record is a trim-to-empty fallback: their rows come from the host replay, with windows
+        # and sequences from the batch, which is alive until the writer has retired it.  Only those reads' windows are cut
+        # again (a handful per batch), not the batch's
+        idx = lane.fallback()
+        if len(idx):
+            seqs = [b.record(int(i))[1] for i in np.sort(idx)]
+            offsets = np.zeros(len(seqs) + 1, dtype=np.uint64)
+            offsets[1:] = np.cumsum([len(s) for s in seqs], dtype=np.uint64)
+            bases = np.frombuffer("".join(seqs).encode("latin-1"), dtype=np.uint8)
+            windows, lens = panel.pack_windows(bases, offsets)
+            match_stats.replay.add_rows(match_stats.table, windows, lens, seqs)
     n_delivered = [0]
     t_start = time.perf_counter()
 
@@ -159,8 +186,13 @@ def run_streaming(sequence_file, panel, output_dir, prefix, start_seq=1, num_seq
         if own_lanes:
             for _ in range(N_LANES):
                 lanes.append(Lane(panel, BATCH_READS))
+                if match_stats is not None:
+                    lanes[-1].attach_stats(match_stats.device)
                 free_lanes.put(lanes[-1])
         else:
+            if match_stats is not None:
+                for ln in lanes:
+                    ln.attach_stats(match_stats.device)
             for ln in lanes:
                 free_lanes.put(ln)
         while True:
@@ -178,10 +210,15 @@ def run_streaming(sequence_file, panel, output_dir, prefix, start_seq=1, num_seq
                 if e.code != _lib.ERR_OVERFLOW or "extra buffer" not in str(e):
                     raise
                 # more extra records than a lane holds (pathological tie storms): this batch again, synchronously,
-                # with a buffer of the size the kernel asked for
+                # with a buffer of the size the kernel asked for.  (With match_stats the lane has counted the batch already
+                # -- counting needs the primary records only -- and panel.run counts nothing: no row is counted twice.)
                 windows, lens = b.pack_windows(panel.search_len, panel.window_stride)
                 ops, extra, _ = panel.run(windows, lens, counts=counts)
-            timing["gpu_wait"] += time.perf_counter() - t0
+            t1 = time.perf_counter()
+            timing["gpu_wait"] += t1 - t0
+            if match_stats is not None:
+                replay_fallback(b, lane)
+                timing["stats_replay"] += time.perf_counter() - t1
             q_out.put((b, lane, ops, extra))
             if on_batch:
                 on_batch(int(counts[_lib.CNT_TOTAL]), int(counts[_lib.CNT_MATCHED]))
@@ -221,6 +258,10 @@ def run_streaming(sequence_file, panel, output_dir, prefix, start_seq=1, num_seq
             except _lib.SmxError as e:
                 if e.code == _lib.ERR_DEVICE:
                     raise e from errors[0]
+        try:
+            detach_stats()
+        except _lib.SmxError:
+            pass   # a lane that could not be drained: the error that stopped the run is the one to report
         raise errors[0]
     t0 = time.perf_counter()
     writer.close()
@@ -228,7 +269,15 @@ def run_streaming(sequence_file, panel, output_dir, prefix, start_seq=1, num_seq
     if own_lanes:
         for ln in lanes:
             ln.close()
+    else:
+        detach_stats()
     tr.join()
+    table_full = None
+    if match_stats is not None:
+        try:
+            match_stats.collect()
+        except Exception as e:   # raised below, once the run's accounting is done
+            table_full = e
     timing["wall"] = time.perf_counter() - t_start
     if int(counts[_lib.CNT_TOTAL]) != n_delivered[0]:
         raise RuntimeError(f"pipeline accounting: the reader delivered {n_delivered[0]} reads, the kernels counted "
@@ -243,4 +292,9 @@ def run_streaming(sequence_file, panel, output_dir, prefix, start_seq=1, num_seq
         print("[smx pipeline] wall %.3f s: reader %.3f + pack %.3f + submit %.3f (thread 1) | waiting for the GPU %.3f (main) | "
               "writer %.3f + close %.3f (thread 2)" % (timing["wall"], timing["read"], timing["pack"], timing["submit"],
                                                         timing["gpu_wait"], timing["write"], timing["close"]), file=sys.stderr)
-    return int(counts[_lib.CNT_TOTAL]), int(counts[_lib.CNT_MATCHED]), counts, reader.is_fastq
+    result = int(counts[_lib.CNT_TOTAL]), int(counts[_lib.CNT_MATCHED]), counts, reader.is_fastq
+    if table_full is not None:
+        if hasattr(table_full, "result"):   # trace_stats.StatsTableFull: the tree is complete, the caller may finish the run
+            table_full.result = result
+        raise table_full
+    return result

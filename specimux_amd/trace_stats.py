@@ -95,9 +95,28 @@ class StatsTable:
             t.add(rec[:len(STORED)], rec[len(STORED)], int(rec[len(STORED) + 1]))
         return t
 
+    def merge(self, other):
+        """Add another table's counts and host_replayed to this one (rows are names, so tables of different panel builds,
+        files or ranks add up).  Returns self."""
+        self.counts.update(other.counts)
+        self.host_replayed += other.host_replayed
+        return self
+
     def save(self, path):
-        with open(path, "w") as fh:
-            json.dump(self.to_json(), fh)
+        """Atomic: the table goes to a temporary file in the same directory, which then replaces `path`; a reader (or a
+        `--table` query during a live run) never sees half a table, and a failed write leaves the previous file."""
+        path = os.fspath(path)
+        tmp = f"{path}.tmp{os.getpid()}"
+        try:
+            with open(tmp, "w") as fh:
+                json.dump(self.to_json(), fh)
+            os.replace(tmp, path)
+        except BaseException:
+            try:
+                os.unlink(tmp)
+            except OSError:
+                pass
+            raise
 
     @classmethod
     def load(cls, path):
@@ -344,6 +363,10 @@ class HostReplay:
         cls = {"full_match": 1, "partial_forward": 2, "partial_reverse": 3, "multiple_specimens": 4}.get(res, 0)
         return _keys_of_read(self.panel.pairs, self.pdir, self.preorient, hits, filtered, cls)
 
+    def close(self):
+        """Nothing of its own on the device (the replay runs through the panel): drop the references."""
+        self.replayer = None
+
     def add_rows(self, table, windows, lens, seqs):
         """windows / lens: the packed windows of the reads (numpy), seqs: their sequences (only the lengths matter)."""
         import numpy as np
@@ -433,6 +456,74 @@ class DeviceStats:
             self.close()
         except Exception:
             pass
+
+
+class StatsTableFull(RuntimeError):
+    """The device table of a counting run filled up.  `result`: what the run returns otherwise (its tree is complete)."""
+    result = None
+
+
+class RunStats:
+    """What pipeline.run_streaming(..., match_stats=) counts a run into: the device table of the panel (`device`), the host
+    replay for the reads the device cannot decide (`replay`) and the host table of names (`table`) that receives the
+    replayed rows during the run and the decoded device table at its end."""
+
+    def __init__(self, panel, parameters, specimens, args, prefilter_on, capacity=None):
+        self.panel = panel
+        self.capacity = int(capacity or DEFAULT_TABLE_CAPACITY)
+        self.device = DeviceStats(panel, self.capacity)
+        self.replay = HostReplay(panel, parameters, specimens, args, prefilter_on)
+        self.table = StatsTable()
+
+    def reset(self):
+        """Empty device table (asynchronous: Lane.attach_stats waits for it) and a new host table, for the next run."""
+        self.device.clear()
+        self.table = StatsTable()
+
+    def collect(self):
+        """End of a run: the device table, decoded to names, is added to the host table."""
+        from . import _lib
+        try:
+            keys, cnts = self.device.read()
+        except _lib.SmxError as e:
+            if e.code != _lib.ERR_OVERFLOW:
+                raise
+            raise StatsTableFull(f"the statistics table ({self.capacity} slots asked for) filled up, nothing is lost but the "
+                                 f"table: run again with a larger --stats-table-capacity") from e
+        table_from_keys(self.panel, keys, cnts, self.table)
+        return self.table
+
+    def summary(self):
+        return (f"{self.table.total('sequences'):,} reads counted, {len(self.table.counts):,} distinct rows, "
+                f"host_replayed {self.table.host_replayed}")
+
+    def close(self):
+        self.replay.close()
+        self.device.close()
+
+
+def rank_table_path(path, rank):
+    return f"{os.fspath(path)}.rank{rank}"
+
+
+def merge_rank_tables(path, world):
+    """The tables `path`.rank0 .. `path`.rank<world-1> that the ranks of a sharded run saved, merged into `path`; the rank
+    files are removed.  A missing or unreadable rank file is an error: no `path` is written (the others are still removed)."""
+    parts = [rank_table_path(path, k) for k in range(world)]
+    try:
+        table = StatsTable()
+        for k, part in enumerate(parts):
+            if not os.path.exists(part):
+                raise FileNotFoundError(f"rank {k} left no stats table ({part}): {os.fspath(path)} is not written")
+            table.merge(StatsTable.load(part))
+        table.save(path)
+        return table
+    finally:
+        for part in parts:
+            try:
+                os.unlink(part)
+            except OSError:
+                pass
 
 
 class _Slot:

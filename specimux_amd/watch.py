@@ -77,6 +77,7 @@ def parse_args(argv):
     if world > 1:
         parser.error(f"specimux-watch runs in one process on one GPU; it cannot run under a multi-process launch "
                      f"(WORLD_SIZE={world})")
+    cli.check_stats_table(parser, args)
     return cli.split_num_seqs(parser, args)
 
 
@@ -90,7 +91,15 @@ def specimux_namespace(args, sequence_file) -> argparse.Namespace:
     for dest in _specimux_dests():
         setattr(ns, dest, str(sequence_file) if dest == "sequence_file" else getattr(args, dest))
     ns.start_seq = args.start_seq
+    # --stats-table is the watcher's own: one cumulative table for the live run, never a per-file table that every
+    # file's run would overwrite
+    for dest, default in _WATCH_OWNED_DEFAULTS.items():
+        setattr(ns, dest, default)
     return ns
+
+
+_WATCH_OWNED_DEFAULTS = {dest: kwargs.get("default") for flags, kwargs in cli._OPTIONS
+                         for dest in [flags[-1].lstrip("-").replace("-", "_")] if dest in cli.WATCH_OWNED}
 
 
 def specimux_flags(args) -> list:
@@ -99,6 +108,8 @@ def specimux_flags(args) -> list:
     out = []
     for flags, kwargs in cli._OPTIONS:
         dest = flags[-1].lstrip("-").replace("-", "_")
+        if dest in cli.WATCH_OWNED:
+            continue
         if dest == "num_seqs":
             if args.start_seq != 1:
                 out += [flags[0], f"{args.start_seq},{args.num_seqs}"]
@@ -173,7 +184,8 @@ class ProcessedFilesTracker:
 # ------------------------------------------------------------------ what stays resident between files
 class _PanelState:
     """Specimens, match parameters, prefilter, compiled panel and (for the streaming path) lanes of one version of the
-    primer and specimen files."""
+    primer and specimen files; with --stats-table also the panel's device statistics table and host replay
+    (`match_stats`, a trace_stats.RunStats)."""
 
     def __init__(self, args):
         from . import orchestration
@@ -182,10 +194,19 @@ class _PanelState:
         specimens, parameters, prefilter = self.loaded
         self.specimens = specimens
         self.lanes = []
+        self.match_stats = None
         if args.output_to_files and not args.diagnostics:
             from .pipeline import make_lanes
             self.panel = compiled_panel(specimens, parameters, args, prefilter)
             self.lanes = make_lanes(self.panel)
+            if getattr(args, "stats_table", None):
+                from .trace_stats import RunStats
+                try:
+                    self.match_stats = RunStats(self.panel, parameters, specimens, args, prefilter is not None,
+                                                args.stats_table_capacity)
+                except BaseException:
+                    self.close()
+                    raise
         else:
             # the panel process_sequences asks for on the record path (it finds it in the same cache)
             tracing_or_color = bool(args.diagnostics) or (bool(args.color) and not args.output_to_files)
@@ -195,6 +216,9 @@ class _PanelState:
         for ln in self.lanes:   # lanes first: they hold a stream slot of their panel
             ln.close()
         self.lanes = []
+        if self.match_stats is not None:   # device table and host replay go before their panel
+            self.match_stats.close()
+            self.match_stats = None
         for panel in self.specimens.__dict__.get("_smx_panels", {}).values():
             panel.close()
 
@@ -240,8 +264,8 @@ class FileProcessor:
     """One file, as `python -m specimux_amd.cli primer_file specimen_file FILE <flags>` would run it, through the
     resident panel.  With -F, <output_dir>/log.txt is rewritten and holds this file's run log."""
 
-    def __init__(self, args, resident: Resident):
-        self.args, self.resident = args, resident
+    def __init__(self, args, resident: Resident, live_stats=None):
+        self.args, self.resident, self.live_stats = args, resident, live_stats
         self.command = ["specimux", args.primer_file, args.specimen_file, "{}"] + specimux_flags(args)
 
     def __call__(self, path):
@@ -257,13 +281,39 @@ class FileProcessor:
             logging.info(f"Running: {' '.join(self.command).replace('{}', str(path))}")
             state = self.resident.current()
             if ns.output_to_files and not ns.diagnostics:
-                orchestration.run_native_file(ns, state.specimens, state.panel, state.lanes)
+                if self.live_stats is None:
+                    orchestration.run_native_file(ns, state.specimens, state.panel, state.lanes)
+                else:
+                    match_stats = state.match_stats
+                    match_stats.reset()   # the device table holds one file at a time
+                    orchestration.run_native_file(ns, state.specimens, state.panel, state.lanes, match_stats=match_stats)
+                    self.live_stats.add_file(match_stats.table)   # reached only when the file succeeded: a failed file adds nothing
             else:
                 orchestration._run_records(ns, to_files=ns.output_to_files, loaded=state.loaded)
         finally:
             if handler is not None:
                 logging.getLogger().removeHandler(handler)
                 handler.close()
+
+
+class LiveStats:
+    """--stats-table FILE: the cumulative stats table of the live run.  It lives on the host as rows of names, so it
+    outlives a panel reload (a new panel numbers its primers, barcodes and pools anew; names merge).  Empty at start-up,
+    as the state file is; FILE is rewritten (atomically) after every file that succeeded, never after one that failed."""
+
+    def __init__(self, path):
+        from .trace_stats import StatsTable
+        self.path = path
+        self.table = StatsTable()
+        self.files = 0
+
+    def add_file(self, table):
+        self.table.merge(table)
+        self.files += 1
+        self.table.save(self.path)
+        logging.info(f"Stats table {self.path}: this file {table.total('sequences'):,} reads (host_replayed "
+                     f"{table.host_replayed}); {self.table.total('sequences'):,} reads in {len(self.table.counts):,} "
+                     f"distinct rows from {self.files} file(s) so far")
 
 
 # ------------------------------------------------------------------ the poller
@@ -437,7 +487,7 @@ def main(argv=None, process=None, clock=time.monotonic, sleep=time.sleep, on_rea
             logging.error(f"Could not load the panel: {e}")
             resident.close()
             return 1
-        process = FileProcessor(args, resident)
+        process = FileProcessor(args, resident, LiveStats(args.stats_table) if args.stats_table else None)
 
     watcher = Watcher(args.watch_dir, args.pattern, args.settle_time, args.poll_interval, tracker, process,
                       stop_after=args.stop_after, clock=clock, sleep=sleep,

@@ -1,7 +1,7 @@
 """Per-file latency of a live run: one CLI process per file (what the reference's watcher pays, watch.py:131-168) against
 the resident watcher (specimux_amd/watch.py).  DESIGN.md section 9 quotes its output.
 
-    python tools/watch_latency.py [--files 20] [--reads 4000] [--json out.json]
+    python tools/watch_latency.py [--files 20] [--reads 4000] [--stats-table] [--json out.json]
 
 K files of N C2-shaped reads (specimux_amd.synth).  Latency = from the file appearing to its result being usable:
   (a) `python -m specimux_amd.cli P S FILE -F -O out` per file, one after another: the process's wall time (the file is
@@ -37,6 +37,8 @@ def main():
     ap.add_argument("--reads", type=int, default=4000)
     ap.add_argument("--timeout", type=float, default=120.0, help="seconds any one file may take")
     ap.add_argument("--json", default=None)
+    ap.add_argument("--stats-table", action="store_true",
+                    help="the watcher also keeps its cumulative stats table (--stats-table live.json), rewritten after every file")
     a = ap.parse_args()
     env = dict(os.environ, PYTHONPATH=REPO + os.pathsep + os.environ.get("PYTHONPATH", ""))
     work = tempfile.mkdtemp(prefix="watch_latency_")
@@ -67,9 +69,11 @@ def main():
         open(os.path.join(wdir, "before_start.fastq"), "w").close()   # marked ignored: the state file appears at start-up
         state = os.path.join(wdir, ".specimux-watch-state.json")
         t_launch = time.perf_counter()
-        proc = subprocess.Popen([sys.executable, "-m", "specimux_amd.watch", pf, sf, wdir, "-F", "-O",
-                                 os.path.join(work, "out_watch"), "--settle-time", "0", "--poll-interval", "0.05",
-                                 "--stop-after", str(len(files))], env=env, cwd=REPO, stdout=subprocess.DEVNULL,
+        watch_cmd = [sys.executable, "-m", "specimux_amd.watch", pf, sf, wdir, "-F", "-O", os.path.join(work, "out_watch"),
+                     "--settle-time", "0", "--poll-interval", "0.05", "--stop-after", str(len(files))]
+        if a.stats_table:
+            watch_cmd += ["--stats-table", os.path.join(work, "live.json")]
+        proc = subprocess.Popen(watch_cmd, env=env, cwd=REPO, stdout=subprocess.DEVNULL,
                                 stderr=open(os.path.join(work, "watch.log"), "w"))
 
         def entries():
@@ -111,7 +115,7 @@ def main():
         if proc.returncode != 0:
             raise RuntimeError(f"the watcher exited with {proc.returncode}")
         same = _tree(os.path.join(work, "out_cli")) == _tree(os.path.join(work, "out_watch"))
-        result = {"files": len(files), "reads_per_file": a.reads,
+        result = {"files": len(files), "reads_per_file": a.reads, "watch_stats_table": bool(a.stats_table),
                   "cli_process_per_file": summary(cli_lat),
                   "watch_first_file": round(watch_lat[0], 4),
                   "watch_later_files": summary(watch_lat[1:]) if len(watch_lat) > 1 else None,
