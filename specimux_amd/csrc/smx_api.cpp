@@ -118,22 +118,67 @@ struct DevBuf {   // grow-only device buffer of the host-buffer convenience path
     void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
 };
 
+// The environment switches of a panel: none is needed in production.  This struct is the source of truth (DESIGN.md,
+// section 8, has the table); read_switches fills it at every smx_panel_create, and nothing else in this file looks at the
+// environment on a panel's behalf.
+struct Switches {
+    bool no_prescan = false;         // SMX_NO_PRESCAN: every primer alignment by the demux kernel's scalar scan
+    bool no_bitslice = false;        // SMX_NO_BITSLICE: per-barcode scan instead of the bit-sliced one
+    bool no_table_sharing = false;   // SMX_NO_TABLE_SHARING: one barcode table per primer even when lists repeat
+    int cap_hits = 0, cap_ents = 0;  // SMX_TEST_CAPS=h,e: small barcode rounds
+    int no_sp = 0;                   // SMX_NO_SPECIALISE (bit 0), SMX_NO_SPECIALISE_NP (bit 1): generic instantiations
+    bool no_lean_tails = false;      // SMX_NO_LEAN_TAILS: --trim tails on the slots kernel
+    bool force_slots = false;        // SMX_FORCE_SLOTS: every launch on the slots kernel
+    bool debug = false;              // SMX_DEBUG: tile plan, occupancy (and placement, with phase timing) on stderr
+    bool debug_overflow = false;     // SMX_DEBUG_OVERFLOW: overflow tiles of every compact launch on stderr (synchronises)
+    bool phase_timing = false;       // SMX_PHASE_TIMING: per-phase cycle sums, printed when the panel is destroyed
+    bool lds_budget_set = false;     // SMX_LDS_BUDGET: LDS bytes a dense tile may take (default: a quarter / a third of a CU's)
+    size_t lds_budget = 0;
+    int tile_r = 64;                 // SMX_TILE_R: largest dense tile tried, 1..64 reads
+    size_t lds_pad = 0;              // SMX_LDS_PAD: bytes added to the lean tile's LDS request
+    bool compact_off = false;        // SMX_COMPACT=0: no compact tiles
+    int compact_items = -1;          // SMX_COMPACT_ITEMS: records per compact tile, 2 NP..256 (-1: unset, 256); forces compact mode
+    int compact_r = 0;               // SMX_COMPACT_R: reads per compact tile, 1..64 (0: unset); forces compact mode
+    int blocks_per_cu = 0;           // SMX_BLOCKS_PER_CU: grid multiplier of every demux launch, >= 1 (0: unset, occupancy)
+};
+
+static Switches read_switches() {
+    Switches w;
+    auto on = [](const char *name) { return getenv(name) != nullptr; };
+    w.no_prescan = on("SMX_NO_PRESCAN"); w.no_bitslice = on("SMX_NO_BITSLICE"); w.no_table_sharing = on("SMX_NO_TABLE_SHARING");
+    if (const char *e = getenv("SMX_TEST_CAPS")) sscanf(e, "%d,%d", &w.cap_hits, &w.cap_ents);
+    w.no_sp = (on("SMX_NO_SPECIALISE") ? 1 : 0) | (on("SMX_NO_SPECIALISE_NP") ? 2 : 0);
+    w.no_lean_tails = on("SMX_NO_LEAN_TAILS"); w.force_slots = on("SMX_FORCE_SLOTS");
+    w.debug = on("SMX_DEBUG"); w.debug_overflow = on("SMX_DEBUG_OVERFLOW"); w.phase_timing = on("SMX_PHASE_TIMING");
+    if (const char *e = getenv("SMX_LDS_BUDGET")) { w.lds_budget_set = true; w.lds_budget = (size_t)atol(e); }
+    if (const char *e = getenv("SMX_TILE_R")) w.tile_r = std::max(1, std::min(64, atoi(e)));
+    if (const char *e = getenv("SMX_LDS_PAD")) w.lds_pad = (size_t)atol(e);
+    if (const char *e = getenv("SMX_COMPACT")) w.compact_off = atoi(e) == 0;
+    if (const char *e = getenv("SMX_COMPACT_ITEMS")) w.compact_items = std::max(0, std::min(256, atoi(e)));
+    if (const char *e = getenv("SMX_COMPACT_R")) w.compact_r = std::max(1, std::min(64, atoi(e)));
+    if (const char *e = getenv("SMX_BLOCKS_PER_CU")) w.blocks_per_cu = std::max(1, atoi(e));
+    return w;
+}
+
+using smx::TilePlan;   // one per launch mode; ensure_device fills blocks_per_cu
+// lean: no per-barcode slots.  slots: --trim tails where the lean kernel cannot report the extent, parity dumps.  compact:
+// tiles of the lean kernel (panels with many primers) that keep per-alignment records only for the nitems alignments the match
+// words flag; a tile that needs more goes on the overflow list and is redone by a dense lean launch right behind the compact one.
+enum { LEAN, SLOTS, COMPACT, N_MODES };
+
 struct smx_panel {
     smx::DevPanel hp;                 // scalar fields valid; pointers filled at upload
     std::vector<unsigned char> blob;  // host image of the device allocation
     size_t o_ppeq, o_prpeq, o_bpeq, o_lut, o_pm, o_pk, o_pdir, o_pfidx, o_pbc_off, o_pbc, o_bm, o_pair_f, o_pair_r,
         o_pair_pool, o_bsre, o_bstab = 0, o_pairrec = 0, o_specrec = 0;
     int use64 = 0;
-    bool env_no_lean_tails = false, env_force_slots = false, env_debug_overflow = false, env_debug = false;   // read once at create
-    int R = 0;          // lean mode tile (no per-barcode slots)
-    size_t lds = 0;
-    int R_slots = 0;    // slots mode tile (--trim tails, parity dumps)
-    size_t lds_slots = 0;
+    Switches sw;
+    TilePlan plan[N_MODES];           // plan_tiles
+    int nitems = 0;                   // records per compact tile; 0: compact mode off
     // device state (lazy, one device per process)
     void *d_blob = nullptr;
     int device = -1;
     int n_cu = 0;
-    int blocks_per_cu = 1, blocks_per_cu_slots = 1;   // resident workgroups per CU: lean / slots kernel
     std::mutex ws_mutex;                     // smx_batch_run is serialised per panel (one workspace)
     DevBuf ws[8];                            // windows, lens, ops, extra, n_extra, counts, hits, bdist
     // Launch counters {tile queue head, -, finished workgroups, extra records}, 64 bytes per slot, self re-arming.
@@ -150,21 +195,76 @@ struct smx_panel {
     int pre_mr = 24, pre_nx = 0, pre_blocks_t = 1, pre_blocks_d = 8;   // longest primer, degenerate symbols, residency
     size_t pre_lds = 0;                      // transpose kernel staging
     DevBuf pre_planes[SMX_MAX_STREAMS];      // per stream slot: the 2-bit text planes of the batch (read-tile major)
-    DevBuf pre_recs[SMX_MAX_STREAMS];
+    DevBuf pre_recs[SMX_MAX_STREAMS];        // per stream slot: [2 * NP][search_len / 16][n_reads rounded up to a tile] flag words
     DevBuf pre_match[SMX_MAX_STREAMS];       // per stream slot: match words [tile][2 * NP][32 groups] (bit = read reaches the threshold)
     DevBuf pre_codes[SMX_MAX_STREAMS];       // per stream slot: row-major 2-bit codes [read][end][chunk] + one flag byte per read behind them
-    // compact mode of the lean kernel (panels with many primers): tiles of Rc reads that keep per-alignment records only
-    // for the nitems alignments the match words flag; a tile that needs more goes on the overflow list and is redone by a
-    // dense launch (R, lds) right behind the compact one.  nitems == 0: off.
-    int Rc = 0, nitems = 0, blocks_per_cu_c = 1;
     int share = 1;      // smx_panel_set_streams: batches the caller keeps in flight on as many streams
-    size_t lds_c = 0;
     DevBuf ovf[SMX_MAX_STREAMS];             // per stream slot: overflow list, one entry per compact tile
     hipEvent_t kev[4] = {nullptr, nullptr, nullptr, nullptr};   // smx_debug_kernel_times: start, after transpose, after DP, end
-    bool kev_on = false, kev_pre = false;        // per stream slot: [2 * NP][search_len / 16][n_reads rounded up to a tile] flag words
+    bool kev_on = false, kev_pre = false;
     unsigned long long *d_phase = nullptr;   // SMX_PHASE_TIMING diagnostic
     int phase_grid = 0;
 };
+
+// The tile plan of a panel (h: every scalar field set): plan[].R / .lds per mode, *nitems > 0 where compact mode is on.
+static void plan_tiles(const smx::DevPanel &h, int use64, bool pre_ok, const Switches &sw, TilePlan plan[N_MODES], int *nitems) {
+    // Tile size: the largest R (<= 64 reads, one scorer lane per read) whose tile fits a quarter of the CU's LDS, so that
+    // four workgroups stay resident; but a tile twice as large at three workgroups per CU keeps more reads in flight
+    // (6R vs 4R) and wins for panels with many primers (measured on the 8-primer panel: R = 32 x 3 beats R = 16 x 4 by 7 %,
+    // R = 64 x 2 loses 45 %).  SMX_TILE_R / SMX_LDS_BUDGET override for tuning experiments.
+    auto lds_blocks = [](size_t need) { return (int)(SMX_LDS_POOL / ((need + 511) & ~(size_t)511)); };   // workgroups of `need` bytes a CU holds
+    const size_t budget = sw.lds_budget_set ? sw.lds_budget : (SMX_LDS_POOL / 4) & ~(size_t)511;
+    for (int slots = 0; slots < 2; slots++) {
+        auto pick = [&](size_t bud) {
+            TilePlan t;
+            for (t.R = sw.tile_r; ; t.R >>= 1) {
+                t.lds = smx_demux_lds_bytes(&h, use64, t.R, slots, 0);
+                if (t.lds <= bud || t.R == 1) return t;
+            }
+        };
+        plan[slots ? SLOTS : LEAN] = pick(budget);
+        if (!sw.lds_budget_set && !slots) {   // (the slots kernel measured 2.5 % slower at three workgroups per CU)
+            const TilePlan t3 = pick((SMX_LDS_POOL / 3) & ~(size_t)511);
+            if (t3.R > plan[LEAN].R) plan[LEAN] = t3;
+        }
+    }
+    TilePlan &lean = plan[LEAN];
+    lean.lds += sw.lds_pad;   // tuning experiment: residency vs LDS size
+    // compact mode: worth it when the dense tile had to shrink (R * 2 NP records do not fit) and the prescan is there to say
+    // which alignments matter.  Largest tile (multiples of 8 reads) at four workgroups per CU, or a larger one at three if
+    // that keeps more reads in flight (8-primer panel: the kernel's time falls as a + b / reads in flight from R = 24 x 4 to
+    // R = 64 x 3).  SMX_COMPACT=0 turns it off, SMX_COMPACT_ITEMS / SMX_COMPACT_R are test / tuning hooks.
+    const bool items_set = sw.compact_items >= 0;
+    const int items = items_set ? std::max(2 * h.NP, sw.compact_items) : 256;
+    *nitems = 0;
+    if (!pre_ok || sw.compact_off || !(lean.R < 64 || items_set)) return;
+    auto need_c = [&](int R) { return smx_demux_lds_bytes(&h, use64, R, 0, items); };
+    int best_R = 0, best_blocks = 0;
+    size_t best_need = 0;
+    for (int R = 64; R >= 8; R -= 8) {
+        const size_t need = need_c(R);
+        if (need > SMX_LDS_POOL) continue;
+        const int blocks = std::min(4, lds_blocks(need));
+        if (blocks < 3) continue;   // two workgroups per CU lose more to exposed latency than their larger tiles win back
+                                    // (measured: 8-primer panel, -l 160: R = 64 x 2 is 40 % slower than R = 40 x 3)
+        if (R * blocks > best_R * best_blocks) { best_R = R; best_blocks = blocks; best_need = need; }
+    }
+    // a tile size that has a default-flags instantiation wins over a larger generic one (wide-window stress shape:
+    // 32-read tiles on `SP = 3` 1.11 ms per 10^6 reads, 48-read tiles on the generic compact kernel 1.15)
+    for (int R = 64; R >= 8; R -= 8) {
+        const size_t need = need_c(R);
+        if (need > SMX_LDS_POOL || lds_blocks(need) < 3) continue;
+        if (smx_demux_sp_query(&h, use64, 0, 1, R, items, 1) != 0) {
+            if (R != best_R) { best_R = R; best_blocks = std::min(4, lds_blocks(need)); best_need = need; }
+            break;
+        }
+    }
+    if (sw.compact_r) { best_R = sw.compact_r; best_need = need_c(best_R); best_blocks = 1; }
+    const int dense_blocks = std::min(4, lds_blocks(lean.lds));
+    if (best_R > 0 && (best_R * best_blocks >= lean.R * dense_blocks || items_set || sw.compact_r)) {
+        plan[COMPACT].R = best_R; plan[COMPACT].lds = best_need; *nitems = items;
+    }
+}
 
 extern "C" {
 
@@ -206,6 +306,7 @@ int smx_panel_create(const smx_panel_desc *d, smx_panel **out) {
     if (d->trim < 0 || d->trim > 3 || d->dereplicate < 0 || d->dereplicate > 1) return fail(SMX_ERR_ARG, "bad trim/dereplicate");
 
     smx_panel *P = new smx_panel();
+    const Switches &sw = P->sw = read_switches();
     smx::DevPanel &h = P->hp;
     memset(&h, 0, sizeof(h));
     h.NP = NP; h.NB = NB; h.NS = NS; h.NPAIR = NPAIR;
@@ -254,7 +355,7 @@ int smx_panel_create(const smx_panel_desc *d, smx_panel **out) {
             pl[p] = (int)pats[p].size();
         }
         memset(&P->pre, 0, sizeof(P->pre));
-        P->pre_ok = maxm <= smx::PRE_MAXROWS && !getenv("SMX_NO_PRESCAN") &&
+        P->pre_ok = maxm <= smx::PRE_MAXROWS && !sw.no_prescan &&
                     smx::prescan_build_desc(&P->pre, NP, h.S, pp.data(), pl.data(), pk.data(),
                                             [](unsigned char a, unsigned char b) { return a < 128 && b < 128 && eqt().eq[a][b]; });
         if (P->pre_ok) {
@@ -283,7 +384,7 @@ int smx_panel_create(const smx_panel_desc *d, smx_panel **out) {
     }
     // bit-sliced barcode tables: usable when every barcode has the same length <= 16 and k <= 7
     const int MBWh = (maxB + 31) / 32;
-    bool bs_ok = d->k_index <= 7 && !getenv("SMX_NO_BITSLICE");
+    bool bs_ok = d->k_index <= 7 && !sw.no_bitslice;
     for (int b = 0; b < NB; b++) if (bm[b] != bm[0] || bm[b] > 16) bs_ok = false;
     std::vector<unsigned> bsre((size_t)NP * 16 * 16 * MBWh, 0u);
     if (bs_ok)
@@ -305,18 +406,12 @@ int smx_panel_create(const smx_panel_desc *d, smx_panel **out) {
             if (found < 0) { packed.insert(packed.end(), bsre.begin() + (size_t)p * tw, bsre.begin() + (size_t)(p + 1) * tw); found = nt++; }
             bs_tab[p] = found;
         }
-        if (getenv("SMX_NO_TABLE_SHARING")) { nt = NP; for (int p = 0; p < NP; p++) bs_tab[p] = p; }   // A/B and test hook
+        if (sw.no_table_sharing) { nt = NP; for (int p = 0; p < NP; p++) bs_tab[p] = p; }   // A/B and test hook
         else bsre.swap(packed);
         h.n_bstab = nt;
     }
     h.bs_ok = bs_ok ? 1 : 0;
-    if (const char *e = getenv("SMX_TEST_CAPS")) sscanf(e, "%d,%d", &h.cap_hits, &h.cap_ents);
-    // the remaining test / A-B switches are read here, once: launches never look at the environment
-    h.no_sp = (getenv("SMX_NO_SPECIALISE") ? 1 : 0) | (getenv("SMX_NO_SPECIALISE_NP") ? 2 : 0);
-    P->env_no_lean_tails = getenv("SMX_NO_LEAN_TAILS") != nullptr;
-    P->env_force_slots = getenv("SMX_FORCE_SLOTS") != nullptr;
-    P->env_debug_overflow = getenv("SMX_DEBUG_OVERFLOW") != nullptr;
-    P->env_debug = getenv("SMX_DEBUG") != nullptr;
+    h.cap_hits = sw.cap_hits; h.cap_ents = sw.cap_ents; h.no_sp = sw.no_sp;   // the switches the kernel and its glue look at
     h.bs_m = bm[0];
     if (h.pfmin != 0 && h.pfmin < 2) { delete P; return fail(SMX_ERR_UNSUPPORTED, "prefilter min length %d < 2: disable the prefilter", h.pfmin); }
     if (h.bmax + h.kidx > 200) { delete P; return fail(SMX_ERR_UNSUPPORTED, "barcode length + k too large"); }
@@ -366,76 +461,9 @@ int smx_panel_create(const smx_panel_desc *d, smx_panel **out) {
     P->o_bstab = blob_add(B, bs_tab);
 
     P->use64 = maxm > 32 ? 1 : 0;
-    // tile size: largest R in {64, 32, ...} whose LDS image lets 4 workgroups share a CU's 160 KiB
-    // (SMX_TILE_R / SMX_LDS_BUDGET override for tuning experiments)
-    // Tile size: the largest R (<= 64 reads, one scorer lane per read) whose tile fits a quarter of the CU's LDS, so that
-    // four workgroups stay resident; but a tile twice as large at three workgroups per CU keeps more reads in flight
-    // (6R vs 4R) and wins for panels with many primers (measured on the 8-primer panel: R = 32 x 3 beats R = 16 x 4 by 7 %,
-    // R = 64 x 2 loses 45 %).  SMX_TILE_R / SMX_LDS_BUDGET override for tuning experiments.
-    const bool budget_forced = getenv("SMX_LDS_BUDGET") != nullptr;
-    auto lds_blocks = [](size_t need) { return (int)(SMX_LDS_POOL / ((need + 511) & ~(size_t)511)); };   // workgroups of `need` bytes a CU holds
-    size_t budget = (SMX_LDS_POOL / 4) & ~(size_t)511;
-    if (budget_forced) budget = (size_t)atol(getenv("SMX_LDS_BUDGET"));
-    int rmax = 64;
-    if (const char *e = getenv("SMX_TILE_R")) rmax = std::max(1, std::min(64, atoi(e)));
-    const int npmeta = 6 * NP + 1 + h.n_pbc + NB + 3 * NPAIR;
-    const int tails = h.trim == SMX_TRIM_TAILS ? 1 : 0;   // the per-entry extent array of the lean tails kernel (BSV 3)
-    for (int slots = 0; slots < 2; slots++) {
-        auto pick = [&](size_t bud, int *Rout, size_t *need_out) {
-            for (int R = rmax; R >= 1; R >>= 1) {
-                size_t need = smx_demux_lds_bytes(P->use64, NP, NB, h.S, R, maxB, h.need_starts, npmeta, h.kidx, slots,
-                                                  h.bs_ok, 0, 2 * NPAIR, tails, h.n_bstab);
-                if (need <= bud || R == 1) { *Rout = R; *need_out = need; return; }
-            }
-        };
-        int R4 = 1, R3 = 1;
-        size_t n4 = 0, n3 = 0;
-        pick(budget, &R4, &n4);
-        if (!budget_forced) pick((SMX_LDS_POOL / 3) & ~(size_t)511, &R3, &n3);
-        const bool three = !budget_forced && !slots && R3 > R4;   // (the slots kernel measured 2.5 % slower that way)
-        if (slots) { P->R_slots = three ? R3 : R4; P->lds_slots = three ? n3 : n4; }
-        else { P->R = three ? R3 : R4; P->lds = three ? n3 : n4; }
-    }
-    if (const char *e = getenv("SMX_LDS_PAD")) P->lds += (size_t)atol(e);   // tuning experiment: residency vs LDS size
-    // compact mode: worth it when the dense tile had to shrink (R * 2 NP records do not fit) and the prescan is there to say
-    // which alignments matter.  Largest tile (multiples of 8 reads) at four workgroups per CU, or a larger one at three if
-    // that keeps more reads in flight (8-primer panel: the kernel's time falls as a + b / reads in flight from R = 24 x 4 to
-    // R = 64 x 3).  SMX_COMPACT=0 turns it off, SMX_COMPACT_ITEMS / SMX_COMPACT_R are test / tuning hooks.
-    {
-        const char *ce = getenv("SMX_COMPACT");
-        int items = 256;
-        if (const char *e = getenv("SMX_COMPACT_ITEMS")) items = std::max(2 * NP, std::min(256, atoi(e)));
-        if (P->pre_ok && !(ce && atoi(ce) == 0) && (P->R < 64 || getenv("SMX_COMPACT_ITEMS"))) {
-            auto need_c = [&](int R) { return smx_demux_lds_bytes(P->use64, NP, NB, h.S, R, maxB, h.need_starts, npmeta, h.kidx, 0, h.bs_ok, items, 2 * NPAIR, tails, h.n_bstab); };
-            int best_R = 0, best_blocks = 0;
-            size_t best_need = 0;
-            for (int R = 64; R >= 8; R -= 8) {
-                const size_t need = need_c(R);
-                if (need > SMX_LDS_POOL) continue;
-                const int blocks = std::min(4, lds_blocks(need));
-                if (blocks < 3) continue;   // two workgroups per CU lose more to exposed latency than their larger tiles win back
-                                            // (measured: 8-primer panel, -l 160: R = 64 x 2 is 40 % slower than R = 40 x 3)
-                if (R * blocks > best_R * best_blocks) { best_R = R; best_blocks = blocks; best_need = need; }
-            }
-            // a tile size that has a default-flags instantiation wins over a larger generic one (wide-window stress shape:
-            // 32-read tiles on `SP = 3` 1.11 ms per 10^6 reads, 48-read tiles on the generic compact kernel 1.15)
-            for (int R = 64; R >= 8; R -= 8) {
-                const size_t need = need_c(R);
-                if (need > SMX_LDS_POOL || lds_blocks(need) < 3) continue;
-                if (smx_demux_sp_query(&h, P->use64, 0, 1, R, items, 1) != 0) {
-                    if (R != best_R) { best_R = R; best_blocks = std::min(4, lds_blocks(need)); best_need = need; }
-                    break;
-                }
-            }
-            if (const char *e = getenv("SMX_COMPACT_R")) { best_R = std::max(1, std::min(64, atoi(e))); best_need = need_c(best_R); best_blocks = 1; }
-            const int dense_blocks = std::min(4, lds_blocks(P->lds));
-            if (best_R > 0 && (best_R * best_blocks >= P->R * dense_blocks || getenv("SMX_COMPACT_ITEMS") || getenv("SMX_COMPACT_R"))) {
-                P->Rc = best_R; P->nitems = items; P->lds_c = best_need;
-            }
-        }
-    }
-    if (P->lds > 160 * 1024 || P->lds_slots > 160 * 1024) {
-        const size_t need = std::max(P->lds, P->lds_slots);
+    plan_tiles(h, P->use64, P->pre_ok, sw, P->plan, &P->nitems);
+    if (P->plan[LEAN].lds > 160 * 1024 || P->plan[SLOTS].lds > 160 * 1024) {
+        const size_t need = std::max(P->plan[LEAN].lds, P->plan[SLOTS].lds);
         delete P;
         return fail(SMX_ERR_UNSUPPORTED, "panel needs %zu bytes of LDS per read tile", need);
     }
@@ -453,18 +481,15 @@ void smx_panel_destroy(smx_panel *P) {
                 for (int i = 0; i < 10; i++) { sum[i] += h[(size_t)b * 16 + i]; tot += h[(size_t)b * 16 + i]; }
             const char *names[8] = {"zero+barrier", "primer_scan", "orient+scan", "entries", "barcode_scan", "summary",
                                     "scorer||encode", "store"};
-            fprintf(stderr, "[smx phase timing] R=%d lds=%zu blocks/CU=%d:", P->R, P->lds, P->blocks_per_cu);
+            fprintf(stderr, "[smx phase timing] R=%d lds=%zu blocks/CU=%d:", P->plan[LEAN].R, P->plan[LEAN].lds, P->plan[LEAN].blocks_per_cu);
             tot -= sum[8] + sum[9];   // [8] = the first encode wave's own encode time (inside the scorer||encode region), [9] = the scorer wave's own time
             for (int i = 0; i < 8; i++) fprintf(stderr, " %s=%.1f%%", names[i], tot ? 100.0 * sum[i] / tot : 0.0);
             fprintf(stderr, " (inside the region: scorer wave %.1f%%, first encode wave %.1f%%)", tot ? 100.0 * sum[9] / tot : 0.0, tot ? 100.0 * sum[8] / tot : 0.0);
             fprintf(stderr, "\n");
-            if (P->env_debug) {   // where did wave w of each workgroup land?  hist[w][simd]
-                {
-                    unsigned long long worked = 0, launches = 0;
-                    for (int b = 0; b < P->phase_grid; b++) { worked += h[(size_t)b * 16 + 14]; }
-                    fprintf(stderr, "[smx placement] workgroup-launches that processed at least one tile: %llu (grid %d)\n", worked, P->phase_grid);
-                    (void)launches;
-                }
+            if (P->sw.debug) {   // where did wave w of each workgroup land?  hist[w][simd]
+                unsigned long long worked = 0;
+                for (int b = 0; b < P->phase_grid; b++) worked += h[(size_t)b * 16 + 14];
+                fprintf(stderr, "[smx placement] workgroup-launches that processed at least one tile: %llu (grid %d)\n", worked, P->phase_grid);
                 int hist[4][4] = {{0}};
                 for (int b = 0; b < P->phase_grid; b++)
                     for (int w = 0; w < 4; w++) hist[w][(h[(size_t)b * 16 + 10 + w] >> 4) & 3]++;
@@ -578,25 +603,21 @@ static int ensure_device(smx_panel *P) {
     h.specrec = (const smx::SpecRec *)(b + P->o_specrec);
     h.bs_re = (const unsigned *)(b + P->o_bsre);
     h.bs_tab = (const int *)(b + P->o_bstab);
-    if (std::max(std::max(P->lds, P->lds_slots), P->lds_c) > 64 * 1024) {
-        const size_t lim = std::max(std::max(P->lds, P->lds_slots), P->lds_c);
-        int rc = smx_set_demux_lds_limit(P->use64, lim);
-        if (rc != 0) return fail(SMX_ERR_DEVICE, "cannot raise the dynamic LDS limit to %zu bytes", lim);
-    }
+    const size_t lim = std::max(std::max(P->plan[LEAN].lds, P->plan[SLOTS].lds), P->plan[COMPACT].lds);
+    if (lim > 64 * 1024 && smx_set_demux_lds_limit(P->use64, lim) != 0)
+        return fail(SMX_ERR_DEVICE, "cannot raise the dynamic LDS limit to %zu bytes", lim);
     // persistent grid = exactly the resident workgroups (tiles are pulled from a queue): a workgroup that starts
     // after the queue has drained would only pay the panel staging and its one-time register spills
-    {
-        int occ = 0;   // (behind a compact launch the dense lean kernel runs as the redo instantiation)
-        if (smx_query_occupancy(&P->hp, P->use64, 0, P->nitems > 0 ? 2 : 0, P->R, 0, P->lds, &occ, P->pre_ok ? 1 : 0) != 0 || occ < 1) occ = 4;
-        P->blocks_per_cu = occ;
-        occ = 0;
-        if (smx_query_occupancy(&P->hp, P->use64, 1, 0, P->R_slots, 0, P->lds_slots, &occ, P->pre_ok ? 1 : 0) != 0 || occ < 1) occ = 4;
-        P->blocks_per_cu_slots = occ;
-        if (P->nitems > 0) {
-            occ = 0;
-            if (smx_query_occupancy(&P->hp, P->use64, 0, 1, P->Rc, P->nitems, P->lds_c, &occ, P->pre_ok ? 1 : 0) != 0 || occ < 1) occ = 4;
-            P->blocks_per_cu_c = occ;
-        }
+    auto occupancy = [&](int m, int *occ) {   // (behind a compact launch the dense lean kernel runs as the redo instantiation)
+        const int cm = m == COMPACT ? 1 : (m == LEAN && P->nitems > 0 ? 2 : 0);
+        return smx_query_occupancy(&P->hp, P->use64, m == SLOTS, cm, P->plan[m].R, m == COMPACT ? P->nitems : 0, P->plan[m].lds, occ,
+                                   P->pre_ok ? 1 : 0);
+    };
+    for (int m = 0; m < N_MODES; m++) {
+        int occ = 0;
+        if (m == COMPACT && P->nitems == 0) continue;
+        if (occupancy(m, &occ) != 0 || occ < 1) occ = 4;
+        P->plan[m].blocks_per_cu = occ;
     }
     if (P->pre_ok) {
         if (P->pre_lds > 64 * 1024 && smx_prescan_set_lds_limit(P->pre_lds) != 0)
@@ -605,20 +626,22 @@ static int ensure_device(smx_panel *P) {
         if (smx_prescan_occupancy(P->hp.S, P->pre_mr, P->pre_nx, P->pre_lds, &occ_t, &occ_d) != 0 || occ_t < 1 || occ_d < 1) { occ_t = 1; occ_d = 8; }
         P->pre_blocks_t = occ_t;
         P->pre_blocks_d = occ_d;
-        if (P->env_debug) fprintf(stderr, "[smx] prescan: transpose %d workgroups/CU (lds %zu), DP %d waves/CU\n", occ_t, P->pre_lds, occ_d);
+        if (P->sw.debug) fprintf(stderr, "[smx] prescan: transpose %d workgroups/CU (lds %zu), DP %d waves/CU\n", occ_t, P->pre_lds, occ_d);
     }
-    if (const char *e = getenv("SMX_BLOCKS_PER_CU")) P->blocks_per_cu = P->blocks_per_cu_slots = P->blocks_per_cu_c = std::max(1, atoi(e));
-    if (P->env_debug) {
+    if (P->sw.blocks_per_cu)
+        for (TilePlan &t : P->plan) t.blocks_per_cu = P->sw.blocks_per_cu;
+    const TilePlan &lean = P->plan[LEAN], &slots = P->plan[SLOTS], &comp = P->plan[COMPACT];
+    if (P->sw.debug) {
         int occ = -1;
-        (void)smx_query_occupancy(&P->hp, P->use64, 0, P->nitems > 0 ? 2 : 0, P->R, 0, P->lds, &occ, P->pre_ok ? 1 : 0);
+        (void)occupancy(LEAN, &occ);
         fprintf(stderr, "[smx] lean R=%d lds=%zu | slots R=%d lds=%zu | occupancy API (lean): %d blocks/CU, grid multiplier %d, CUs %d\n",
-                P->R, P->lds, P->R_slots, P->lds_slots, occ, P->blocks_per_cu, P->n_cu);
+                lean.R, lean.lds, slots.R, slots.lds, occ, lean.blocks_per_cu, P->n_cu);
         if (P->nitems > 0)
-            fprintf(stderr, "[smx] compact lean tiles: R=%d, %d records, lds=%zu, %d blocks/CU (overflow tiles redone dense)\n", P->Rc,
-                    P->nitems, P->lds_c, P->blocks_per_cu_c);
+            fprintf(stderr, "[smx] compact lean tiles: R=%d, %d records, lds=%zu, %d blocks/CU (overflow tiles redone dense)\n", comp.R,
+                    P->nitems, comp.lds, comp.blocks_per_cu);
     }
-    if (getenv("SMX_PHASE_TIMING")) {
-        P->phase_grid = P->n_cu * std::max(std::max(P->blocks_per_cu, P->blocks_per_cu_slots), P->blocks_per_cu_c);
+    if (P->sw.phase_timing) {
+        P->phase_grid = P->n_cu * std::max(std::max(lean.blocks_per_cu, slots.blocks_per_cu), comp.blocks_per_cu);
         HIP_TRY(hipMalloc((void **)&P->d_phase, (size_t)P->phase_grid * 16 * 8));
         HIP_TRY(hipMemset(P->d_phase, 0, (size_t)P->phase_grid * 16 * 8));
         h.dbg_phase = P->d_phase;
@@ -644,19 +667,14 @@ int smx_batch_run_device(const smx_panel *Pc, void *stream, const uint8_t *d_win
     // --trim tails when the bit-sliced scan cannot report the tail extent (it can for k <= 3 and at most 32 barcodes
     // per primer).  The hit dump alone (d_hits) comes from whichever kernel the flags select, so that the parity tests
     // see the hit table of the kernel that is benchmarked; its tail_end is defined only where that kernel computes it.
-    const bool lean_tails = P->hp.bs_ok && P->hp.kidx < 4 && P->hp.maxB <= 32 && !P->env_no_lean_tails;
-    const int use_slots = ((P->hp.trim == SMX_TRIM_TAILS && !lean_tails) || d_bdist || P->env_force_slots) ? 1 : 0;
+    const bool lean_tails = P->hp.bs_ok && P->hp.kidx < 4 && P->hp.maxB <= 32 && !P->sw.no_lean_tails;
+    const int use_slots = ((P->hp.trim == SMX_TRIM_TAILS && !lean_tails) || d_bdist || P->sw.force_slots) ? 1 : 0;
     const bool compact = !use_slots && P->nitems > 0 && P->pre_ok;
-    const int R = use_slots ? P->R_slots : P->R;
-    const size_t lds = use_slots ? P->lds_slots : P->lds;
-    unsigned *tc = nullptr;
-    size_t slot = 0;
-    {
-        int sl = stream_slot(P, stream, true);
-        if (sl < 0) return fail(SMX_ERR_UNSUPPORTED, "one panel launched on more than %d streams at a time", SMX_MAX_STREAMS);
-        slot = (size_t)sl;
-        tc = P->d_tile_counter + 16 * slot;
-    }
+    const TilePlan &dense = P->plan[use_slots ? SLOTS : LEAN], &comp = P->plan[COMPACT];
+    const int sl = stream_slot(P, stream, true);
+    if (sl < 0) return fail(SMX_ERR_UNSUPPORTED, "one panel launched on more than %d streams at a time", SMX_MAX_STREAMS);
+    const size_t slot = (size_t)sl;
+    unsigned *tc = P->d_tile_counter + 16 * slot;
     // primer prescan in front of the demux kernel (same stream: ordered)
     const unsigned *d_pre = nullptr, *d_codes2 = nullptr;
     const uint8_t *d_naflag = nullptr;
@@ -668,7 +686,7 @@ int smx_batch_run_device(const smx_panel *Pc, void *stream, const uint8_t *d_win
         DevBuf &pb = P->pre_recs[slot], &pp = P->pre_planes[slot], &pm = P->pre_match[slot], &ov = P->ovf[slot];
         const size_t need_planes = (size_t)(npad / smx::PRE_TILE) * (P->hp.S >> 4) * 8 * 64 * 4 * sizeof(unsigned);
         const size_t need_match = P->nitems > 0 ? (size_t)(npad / smx::PRE_TILE) * 2 * P->hp.NP * smx::PRE_G * sizeof(unsigned) : 0;
-        const size_t need_ovf = compact ? ((size_t)n_reads / P->Rc + 2) * sizeof(unsigned) : 0;
+        const size_t need_ovf = compact ? ((size_t)n_reads / comp.R + 2) * sizeof(unsigned) : 0;
         DevBuf &pc = P->pre_codes[slot];
         const size_t codes_bytes = (size_t)npad * 2 * (P->hp.S >> 4) * sizeof(unsigned);   // 2-bit codes, then the flag bytes
         const size_t need_codes = codes_bytes + npad;
@@ -696,44 +714,36 @@ int smx_batch_run_device(const smx_panel *Pc, void *stream, const uint8_t *d_win
         d_pre = (const unsigned *)pb.p;
         if (P->kev_on) (void)hipEventRecord(P->kev[2], (hipStream_t)stream);
     }
-    uint32_t tiles = (n_reads + R - 1) / R;
     // (batches in flight on several streams share the CUs' workgroup slots: each demux launch takes its part of them, so
     // that the next batch's memory-bound and VALU-bound prescan kernels run beside this batch's latency-bound demux kernel)
-    auto slots_of = [&](int blocks) {
-        int per = std::max(1, (blocks + P->share - 1) / P->share);
+    auto grid_of = [&](const TilePlan &t) {
+        int per = std::max(1, (t.blocks_per_cu + P->share - 1) / P->share);
         // two launches side by side must not claim more slots than the CU has: nothing of the next batch's prescan kernels
         // would fit beside them (five slots, two streams: 3 + 3 measured 0.335 ms per step, 2 + 2 0.306-0.319)
-        if (P->share == 2 && per * 2 > blocks) per = std::max(1, blocks / 2);
-        return (uint32_t)(P->n_cu * per);
+        if (P->share == 2 && per * 2 > t.blocks_per_cu) per = std::max(1, t.blocks_per_cu / 2);
+        return (int)std::min<uint32_t>((n_reads + t.R - 1) / t.R, (uint32_t)(P->n_cu * per));
     };
-    int grid = (int)std::min<uint32_t>(tiles, slots_of(use_slots ? P->blocks_per_cu_slots : P->blocks_per_cu));
+    const smx::DemuxBatch batch = {d_windows, d_lens, n_reads, d_ops, d_extra, extra_cap, d_n_extra, d_counts, d_hits, d_bdist,
+                                   stream, tc, d_pre, npad};
+    auto launch = [&](const TilePlan &t, int grid, const smx::DemuxAux &ax) {
+        return smx_launch_demux(&P->hp, P->use64, use_slots, &t, grid, &batch, &ax);
+    };
     int e;
     if (compact) {
         // compact launch over all reads, then the dense launch over the reads of the tiles it put on the overflow list
         // (usually none: its workgroups find an empty list and leave)
-        smx::DemuxAux ax = {(const unsigned *)P->pre_match[slot].p, (unsigned *)P->ovf[slot].p, P->nitems, 0, P->Rc, 1, d_codes2, d_naflag};
-        const uint32_t ctiles = (n_reads + P->Rc - 1) / P->Rc;
-        const int cgrid = (int)std::min<uint32_t>(ctiles, slots_of(P->blocks_per_cu_c));
-        e = smx_launch_demux(&P->hp, P->use64, P->Rc, cgrid, P->lds_c, stream, d_windows, d_lens, n_reads, d_ops, d_extra,
-                             extra_cap, d_n_extra, d_counts, d_hits, d_bdist, tc, 0, d_pre, npad, &ax);
-        if (e == 0 && P->env_debug_overflow) {   // diagnostic: how many compact tiles went on the overflow list
+        e = launch(comp, grid_of(comp), {(const unsigned *)P->pre_match[slot].p, (unsigned *)P->ovf[slot].p, P->nitems, 0, comp.R, 1, d_codes2, d_naflag});
+        if (e == 0 && P->sw.debug_overflow) {   // diagnostic: how many compact tiles went on the overflow list
             unsigned n_ovf = 0;
             (void)hipMemcpyAsync(&n_ovf, tc + 1, sizeof(unsigned), hipMemcpyDeviceToHost, (hipStream_t)stream);
             (void)hipStreamSynchronize((hipStream_t)stream);
-            fprintf(stderr, "[smx] compact launch: %u of %u tiles left to the redo launch\n", n_ovf, ctiles);
+            fprintf(stderr, "[smx] compact launch: %u of %u tiles left to the redo launch\n", n_ovf, (n_reads + comp.R - 1) / comp.R);
         }
-        if (e == 0) {
-            // the redo launch usually finds an empty list: one workgroup per CU is enough to start with (its workgroups
-            // loop over the list), and an empty 256-workgroup launch costs less than an empty full-residency one
-            smx::DemuxAux rx = {nullptr, (unsigned *)P->ovf[slot].p, 0, 1, P->Rc, 0, d_codes2, d_naflag};
-            grid = std::min(grid, P->n_cu);
-            e = smx_launch_demux(&P->hp, P->use64, R, grid, lds, stream, d_windows, d_lens, n_reads, d_ops, d_extra,
-                                 extra_cap, d_n_extra, d_counts, d_hits, d_bdist, tc, 0, d_pre, npad, &rx);
-        }
+        // the redo launch usually finds an empty list: one workgroup per CU is enough to start with (its workgroups
+        // loop over the list), and an empty 256-workgroup launch costs less than an empty full-residency one
+        if (e == 0) e = launch(dense, std::min(grid_of(dense), P->n_cu), {nullptr, (unsigned *)P->ovf[slot].p, 0, 1, comp.R, 0, d_codes2, d_naflag});
     } else {
-        smx::DemuxAux dx = {nullptr, nullptr, 0, 0, 0, 0, d_codes2, d_naflag};
-        e = smx_launch_demux(&P->hp, P->use64, R, grid, lds, stream, d_windows, d_lens, n_reads, d_ops, d_extra,
-                             extra_cap, d_n_extra, d_counts, d_hits, d_bdist, tc, use_slots, d_pre, npad, &dx);
+        e = launch(dense, grid_of(dense), {nullptr, nullptr, 0, 0, 0, 0, d_codes2, d_naflag});
     }
     if (e != 0) return fail(SMX_ERR_DEVICE, "demux kernel launch failed: %s", hipGetErrorString((hipError_t)e));
     if (P->kev_on) (void)hipEventRecord(P->kev[3], (hipStream_t)stream);

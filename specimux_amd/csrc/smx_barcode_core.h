@@ -13,7 +13,7 @@
 #define SMX_BARCODE_CORE_H
 
 #ifndef SMX_HD
-#if defined(__HIPCC__) || defined(__CUDACC__)
+#if defined(__HIPCC__)
 #define SMX_HD __host__ __device__ __forceinline__
 #else
 #define SMX_HD inline

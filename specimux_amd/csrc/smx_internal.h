@@ -51,7 +51,7 @@ struct DevPanel {
     int n_bstab;              // distinct per-primer tables in bs_re (primers with the same barcode list share one)
     const int *bs_tab;        // per primer: its table
     int cap_hits, cap_ents;   // test hook (SMX_TEST_CAPS=h,e): force small barcode rounds; 0 = default sizing
-    int no_sp;                // SMX_NO_SPECIALISE (bit 0) / SMX_NO_SPECIALISE_NP (bit 1), read once at smx_panel_create
+    int no_sp;                // SMX_NO_SPECIALISE (bit 0) / SMX_NO_SPECIALISE_NP (bit 1)
     const unsigned *bs_re;
     unsigned long long *dbg_phase;        // SMX_PHASE_TIMING=1: [grid][16] cycle sums per phase (diagnostic build-in)
 };
@@ -66,6 +66,19 @@ struct DemuxAux {
     int chain;               // 1: another launch of this batch follows: the extra-record and overflow counters stay
     const unsigned *codes2;  // prescan: row-major 2-bit codes per read in DP order (smx_prescan_core.h codes2_word); nullptr: encode from ASCII
     const uint8_t *naflag;   // prescan: per read, 1 = a window holds something other than upper-case ACGT (ASCII path for that read)
+};
+
+// One launch mode's tile: reads per tile, its LDS image, and the resident workgroups per CU the grid counts on.
+struct TilePlan { int R = 0; size_t lds = 0; int blocks_per_cu = 1; };
+
+// One batch as smx_batch_run_device receives it (the ten buffers of include/smx.h), and where it runs.
+struct DemuxBatch {
+    const uint8_t *windows; const int32_t *lens; uint32_t n_reads;
+    smx_op *ops, *extra; uint32_t extra_cap, *n_extra; uint64_t *counts;
+    smx_hit *hits; int8_t *bdist;   // optional dumps
+    void *stream;
+    unsigned *tile_counter;         // the stream's launch counters on this panel
+    const unsigned *pre; uint32_t npad;   // prescan flag words of the batch (nullptr: no prescan), npad reads per (alignment, chunk)
 };
 
 // specimine (smx_mine.hip): chunks of one query x up to MINE_THREADS (smx_mine_core.h) targets, one target per lane
@@ -87,10 +100,8 @@ struct MinePair {     // one (job, query) pair, ceil(nt / MINE_THREADS) target c
 }  // namespace smx
 
 extern "C" {
-int smx_launch_demux(const smx::DevPanel *P, int use64, int R, int grid, size_t lds_bytes, void *stream,
-                     const uint8_t *d_windows, const int32_t *d_lens, uint32_t n_reads, smx_op *d_ops, smx_op *d_extra,
-                     uint32_t extra_cap, uint32_t *d_n_extra, uint64_t *d_counts, smx_hit *d_hits, int8_t *d_bdist,
-                     unsigned *d_tile_counter, int use_slots, const unsigned *d_pre, uint32_t npad, const smx::DemuxAux *aux);
+int smx_launch_demux(const smx::DevPanel *P, int use64, int use_slots, const smx::TilePlan *plan, int grid,
+                     const smx::DemuxBatch *batch, const smx::DemuxAux *aux);
 // primer prescan (smx_prescan.hip)
 size_t smx_prescan_lds_bytes(int S);
 int smx_launch_prescan(const smx::PreDesc *D, int mr, int nx, int grid_t, size_t lds_t, int grid_d, void *stream,
@@ -99,8 +110,7 @@ int smx_launch_prescan(const smx::PreDesc *D, int mr, int nx, int grid_t, size_t
 int smx_prescan_set_lds_limit(size_t bytes);
 int smx_prescan_occupancy(int S, int mr, int nx, size_t lds_t, int *blocks_t, int *blocks_d);
 int smx_prescan_transpose_threads(int S);
-size_t smx_demux_lds_bytes(int use64, int NP, int NB, int S, int R, int maxB, int need_starts, int npmeta, int kidx,
-                           int slots, int bs, int nitems, int ncand, int tails, int nbstab);
+size_t smx_demux_lds_bytes(const smx::DevPanel *P, int use64, int R, int slots, int nitems);
 int smx_set_demux_lds_limit(int use64, size_t bytes);
 int smx_demux_sp_query(const smx::DevPanel *P, int use64, int use_slots, int cm, int R, int nitems, int have_prescan);
 int smx_query_occupancy(const smx::DevPanel *P, int use64, int use_slots, int cm, int R, int nitems, size_t lds_bytes,

@@ -1,14 +1,23 @@
 // smx_kernels.hip -- gfx950 (MI355X / CDNA4) kernels of the specimux hot path.
 //
-// One fused kernel per read batch ("demux kernel"), no intermediate HBM traffic: workgroups of 256 threads pull
-// tiles of R reads from a global tile queue; everything between the windows and the 32-byte result records lives
-// in LDS (layout: make_layout).
+// A read batch takes three kernels on one stream.  The two prescan kernels (smx_prescan.hip) come first: the transpose
+// kernel turns the windows into bit-sliced 2-bit planes, row-major 2-bit codes and one "not plain ACGT" flag byte per read;
+// the primer DP kernel aligns every primer over the planes and writes one flag word per (primer, end, 16-column chunk,
+// read), plus match words per 32-read group.  Planes, codes, flag words and match words go through HBM.  The demux kernel
+// of this file comes last: it decodes the flag words instead of scanning for primers itself, and redoes only the alignments
+// the prescan cannot take (reads flagged by the byte; every alignment when a panel has no prescan: primers over 31 nt,
+// SMX_NO_PRESCAN).  A many-primer panel runs it twice, a compact launch and the dense redo launch for its overflow tiles.
+//
+// Demux kernel: workgroups of 256 threads pull tiles of R reads from a global tile queue; everything between its inputs
+// and the 32-byte result records lives in LDS (layout: make_layout).
 // The tile loop is software-pipelined: phase 4 of tile t (one wave) runs beside phase 1 of tile t+1 (three waves).
 //     phase 0  panel tables staged once per workgroup: primer Peq [code][primer] (patterns left-aligned), bit-sliced
 //              barcode tables [primer][32-barcode word][row][code], ASCII->code LUTs, pair / barcode lists
 //     phase 1  coalesced 16-byte loads of the two `search_len` end windows, ASCII -> 4-bit IUPAC code,
-//              window A reverse-complemented on the fly           (demultiplex.py:142, :757-766)
-//     phase 2  primer scan: one lane per (read, primer, end): Myers/Hyyro bit-vector HW (infix) DP,
+//              window A reverse-complemented on the fly           (demultiplex.py:142, :757-766);
+//              reads of plain upper-case ACGT take the prescan's 2-bit codes instead of the ASCII windows
+//     phase 2  primer hits: one lane per (read, primer, end) decodes the prescan's flag words (prescan_decode); without
+//              them the scalar primer scan: Myers/Hyyro bit-vector HW (infix) DP,
 //              all optimal end columns kept as an LDS bitmask     (match_one_end :755-770, align_seq)
 //              + orientation votes from the same alignments       (determine_orientation :602-638, A.6)
 //     phase 3  barcode scan per optimal primer location ("entry"), exact-set prefilter rule per entry
@@ -239,6 +248,13 @@ __host__ __device__ inline TileLayout make_layout(int NP, int NB, int S, int R, 
     t.pmeta = o; o += npmeta * 4;
     t.total = (o + 15) & ~15;
     return t;
+}
+
+// The make_layout arguments that follow from a panel's sizes.  The host (smx_demux_lds_bytes: the LDS a launch reserves) and
+// DemuxTile::setup (the LDS the kernel addresses) both take them from here; a specialised kernel passes its constants.
+struct LayoutArgs { int npmeta, ncand, tails; };
+__host__ __device__ __forceinline__ LayoutArgs layout_args(int NP, int NB, int n_pbc, int NPAIR, int trim) {
+    return {6 * NP + 1 + n_pbc + NB + 3 * NPAIR, 2 * NPAIR, trim == SMX_TRIM_TAILS ? 1 : 0};
 }
 
 // exclusive scan of a[0..n) in LDS by ONE wave (all 64 lanes of it call this); a[n] = total.
@@ -990,13 +1006,14 @@ struct DemuxTile {
         NP = SP == 2 ? 2 : P->NP; NB = P->NB; S = SP == 3 ? 160 : (sp ? 80 : P->S); H = 2 * NP; MW = (S + 31) / 32; maxB = P->maxB;
         need_starts = sp ? 0 : P->need_starts;
         n_pbc = P->n_pbc; NPAIR = SP == 2 ? 1 : P->NPAIR;
-        npmeta = 6 * NP + 1 + n_pbc + NB + 3 * NPAIR;
+        const LayoutArgs la = layout_args(NP, NB, n_pbc, NPAIR, P->trim);
+        npmeta = la.npmeta;
         // (the default-flags kernels are lean bit-sliced launches by construction: no slots-mode state in them)
         use_slots = SP != 0 ? 0 : use_slots_arg;
         dbg_bdist = SP != 0 ? nullptr : dbg_bdist_arg;
         use_bs = SP != 0 ? 1 : ((BSV != 0 && P->bs_ok && !use_slots) ? 1 : 0);
-        ncand = 2 * NPAIR;
-        const int tails = sp ? 0 : (P->trim == SMX_TRIM_TAILS ? 1 : 0);
+        ncand = la.ncand;
+        const int tails = sp ? 0 : la.tails;
         T = make_layout<PW>(NP, NB, S, R, maxB, need_starts, npmeta, sp ? 3 : P->kidx, use_slots, P->bs_ok, ncand,
                             sp ? 0 : P->cap_hits, sp ? 0 : P->cap_ents, (sp && CM == 1) ? 256 : aux.nitems, tails, P->n_bstab);
         ppeq = (PW *)(lds + T.ppeq);        // [code][primer], stride NPs
@@ -2085,122 +2102,115 @@ __global__ __launch_bounds__(64) void align_batch_kernel(const unsigned long lon
 
 // ------------------------------------------------------------------------------------------------
 // launch glue used by smx_api.cpp
-// The kernel's instantiations -- one per (primer word width, barcode scan variant, compact / redo mode, default-flags
-// specialisation): 19 of them, half a minute of compile time each -- are spread over three translation units: this file is
-// compiled three times (-DSMX_PART=1 / 2 / 3, in parallel), each part instantiates the kernels its table names, part 1 also
-// holds the alignment kernels and the glue.
-#define SMX_FN(B, C, S_) (const void *)smx::demux_kernel<unsigned, 256, B, C, S_>
+// The kernel's instantiations, 20 of them at half a minute of compile time each, one row per (part, primer word bits,
+// barcode scan variant BSV, dense / compact / redo mode CM, default-flags specialisation SP).  This file is compiled three
+// times (-DSMX_PART=1 / 2 / 3, in parallel); each part instantiates the rows that name it, part 1 also holds the alignment
+// kernels and the glue.  A new instantiation is one row here plus the condition in demux_variant that selects it.
+#define SMX_DEMUX_VARIANTS(P1, P2, P3)                                                                           \
+    P1(64, 0, 0, 0) P1(64, 1, 0, 0) P1(64, 2, 0, 0) P1(64, 3, 0, 0)   /* 64-bit primer words */                  \
+    P1(32, 0, 0, 0) P1(32, 0, 1, 0) P1(32, 0, 2, 0)                   /* per-barcode scan */                     \
+    P2(32, 1, 0, 0) P2(32, 1, 1, 0) P2(32, 1, 2, 0)                   /* bit-sliced scan, k <= 3 */              \
+    P2(32, 2, 0, 0) P2(32, 2, 1, 0) P2(32, 2, 2, 0)                   /* bit-sliced scan, k 4..7 */              \
+    P3(32, 3, 0, 0) P3(32, 3, 1, 0) P3(32, 3, 2, 0)                   /* the tails variant */                    \
+    P3(32, 1, 0, 2) P3(32, 1, 1, 3) P3(32, 1, 1, 1) P3(32, 1, 0, 1)   /* the default-flags kernels */
+struct DemuxVariant { int wbits, bsv, cm, sp; };
+typedef unsigned smx_w32;
+typedef unsigned long long smx_w64;
+#define SMX_ROW_SKIP(W, B, C, S_)
+#define SMX_ROW_FN(W, B, C, S_) \
+    if (v.wbits == W && v.bsv == B && v.cm == C && v.sp == S_) return (const void *)smx::demux_kernel<smx_w##W, 256, B, C, S_>;
+// the kernel of a row of this part (nullptr: the row is not one of them)
 #if SMX_PART == 1
-extern "C" const void *smx_demux_fn_p1(int use64, int bsv, int cm, int sp) {   // 64-bit primer words; per-barcode scan (BSV 0)
-    (void)sp;
-    if (use64) {
-        switch (bsv) {
-            case 0: return (const void *)smx::demux_kernel<unsigned long long, 256, 0>;
-            case 1: return (const void *)smx::demux_kernel<unsigned long long, 256, 1>;
-            case 2: return (const void *)smx::demux_kernel<unsigned long long, 256, 2>;
-            default: return (const void *)smx::demux_kernel<unsigned long long, 256, 3>;
-        }
-    }
-    return cm == 0 ? SMX_FN(0, 0, 0) : (cm == 1 ? SMX_FN(0, 1, 0) : SMX_FN(0, 2, 0));
-}
+extern "C" const void *smx_demux_fn_p1(DemuxVariant v) { SMX_DEMUX_VARIANTS(SMX_ROW_FN, SMX_ROW_SKIP, SMX_ROW_SKIP) return nullptr; }
 #elif SMX_PART == 2
-extern "C" const void *smx_demux_fn_p2(int use64, int bsv, int cm, int sp) {   // bit-sliced scans k <= 3 and k 4..7, generic
-    (void)use64; (void)sp;
-    if (bsv == 1) return cm == 0 ? SMX_FN(1, 0, 0) : (cm == 1 ? SMX_FN(1, 1, 0) : SMX_FN(1, 2, 0));
-    return cm == 0 ? SMX_FN(2, 0, 0) : (cm == 1 ? SMX_FN(2, 1, 0) : SMX_FN(2, 2, 0));
-}
+extern "C" const void *smx_demux_fn_p2(DemuxVariant v) { SMX_DEMUX_VARIANTS(SMX_ROW_SKIP, SMX_ROW_FN, SMX_ROW_SKIP) return nullptr; }
 #else
-extern "C" const void *smx_demux_fn_p3(int use64, int bsv, int cm, int sp) {   // the tails variant; the default-flags kernels
-    (void)use64;
-    if (bsv == 3) return cm == 0 ? SMX_FN(3, 0, 0) : (cm == 1 ? SMX_FN(3, 1, 0) : SMX_FN(3, 2, 0));
-    if (sp == 2) return SMX_FN(1, 0, 2);
-    if (sp == 3) return SMX_FN(1, 1, 3);
-    return cm == 1 ? SMX_FN(1, 1, 1) : SMX_FN(1, 0, 1);
-}
+extern "C" const void *smx_demux_fn_p3(DemuxVariant v) { SMX_DEMUX_VARIANTS(SMX_ROW_SKIP, SMX_ROW_SKIP, SMX_ROW_FN) return nullptr; }
 #endif
-#undef SMX_FN
 
 #if SMX_PART == 1
-extern "C" const void *smx_demux_fn_p2(int use64, int bsv, int cm, int sp);
-extern "C" const void *smx_demux_fn_p3(int use64, int bsv, int cm, int sp);
+extern "C" const void *smx_demux_fn_p2(DemuxVariant v);
+extern "C" const void *smx_demux_fn_p3(DemuxVariant v);
 namespace {
-const void *demux_fn(int use64, int bsv, int cm, int sp) {
-    if (use64 || bsv == 0) return smx_demux_fn_p1(use64, bsv, cm, sp);
-    if (bsv == 3 || (sp && bsv == 1 && cm != 2)) return smx_demux_fn_p3(use64, bsv, cm, sp);
-    return smx_demux_fn_p2(use64, bsv, cm, sp);
+// each part knows its rows of the list.  nullptr: no such instantiation; every caller turns that into an error
+const void *demux_fn(DemuxVariant v) {
+    const void *fn = smx_demux_fn_p1(v);
+    if (!fn) fn = smx_demux_fn_p2(v);
+    return fn ? fn : smx_demux_fn_p3(v);
 }
-int demux_bsv(const smx::DevPanel *P, int use_slots) {
-    return (use_slots || !P->bs_ok) ? 0 : (P->kidx < 4 ? (P->trim == SMX_TRIM_TAILS ? 3 : 1) : 2);
-}
-// the default-flags specialisation applies to the k <= 3 lean kernel (not its tails variant, not the redo launch) with
-// 64-read tiles
-int demux_sp(const smx::DevPanel *P, int use64, int bsv, int cm, int R, int nitems, bool have_codes2) {
-    const bool flags = have_codes2 && !use64 && bsv == 1 && cm != 2 && (cm == 0 || nitems == 256) && !P->cap_hits && !P->cap_ents &&
+// The variant a launch with these parameters gets (cm: 0 dense, 1 compact, 2 redo).  Slots mode never uses the bit-sliced
+// scan.  The default-flags specialisation applies to the k <= 3 lean kernel (not its tails variant, not the redo launch)
+// with the tile sizes it is built for.
+DemuxVariant demux_variant(const smx::DevPanel *P, int use64, int use_slots, int cm, int R, int nitems, bool have_prescan) {
+    const int bsv = (use_slots || !P->bs_ok) ? 0 : (P->kidx < 4 ? (P->trim == SMX_TRIM_TAILS ? 3 : 1) : 2);
+    DemuxVariant v = {use64 ? 64 : 32, bsv, cm, 0};
+    const bool flags = have_prescan && !use64 && bsv == 1 && cm != 2 && (cm == 0 || nitems == 256) && !P->cap_hits && !P->cap_ents &&
                        P->kidx == 3 && P->maxB <= 32 && !P->need_starts && P->trim == SMX_TRIM_BARCODES && P->derep == SMX_DEREP_BEST &&
                        P->preorient && P->minlen == -1 && P->maxlen == -1 && !P->dbg_phase && !(P->no_sp & 1);
-    if (!flags) return 0;
-    if (P->S == 160 && R == 32 && cm == 1) return 3;                       // wide windows, compact 32-read tiles
-    if (P->S != 80) return 0;
-    if (R == SMX_SP2_R && cm == 0 && P->NP == 2 && P->NPAIR == 1 && !(P->no_sp & 2)) return 2;
-    return R == 64 ? 1 : 0;
+    if (!flags) return v;
+    if (P->S == 160 && R == 32 && cm == 1) v.sp = 3;                       // wide windows, compact 32-read tiles
+    else if (P->S == 80 && R == SMX_SP2_R && cm == 0 && P->NP == 2 && P->NPAIR == 1 && !(P->no_sp & 2)) v.sp = 2;
+    else if (P->S == 80 && R == 64) v.sp = 1;
+    return v;
 }
 }  // namespace
 
 // which default-flags instantiation a launch with these parameters would get (0: the generic kernel)
 extern "C" int smx_demux_sp_query(const smx::DevPanel *P, int use64, int use_slots, int cm, int R, int nitems, int have_prescan) {
-    return demux_sp(P, use64, demux_bsv(P, use_slots), cm, R, nitems, have_prescan != 0);
+    return demux_variant(P, use64, use_slots, cm, R, nitems, have_prescan != 0).sp;
 }
 
-extern "C" int smx_launch_demux(const smx::DevPanel *P, int use64, int R, int grid, size_t lds_bytes, void *stream,
-                                const uint8_t *d_windows, const int32_t *d_lens, uint32_t n_reads, smx_op *d_ops,
-                                smx_op *d_extra, uint32_t extra_cap, uint32_t *d_n_extra, uint64_t *d_counts,
-                                smx_hit *d_hits, int8_t *d_bdist, unsigned *d_tile_counter, int use_slots,
-                                const unsigned *d_pre, uint32_t npad, const smx::DemuxAux *aux_in) {
-    smx::DemuxAux aux = {nullptr, nullptr, 0, 0, 0, 0, nullptr, nullptr};
-    if (aux_in) aux = *aux_in;
-    if (aux.nitems > 0 && (use_slots || !d_pre || !aux.match || !aux.ovf_list || aux.nitems > 256)) return (int)hipErrorInvalidValue;
+extern "C" int smx_launch_demux(const smx::DevPanel *P, int use64, int use_slots, const smx::TilePlan *plan, int grid,
+                                const smx::DemuxBatch *b, const smx::DemuxAux *aux_in) {
+    smx::DemuxAux aux = *aux_in;
+    smx::DemuxBatch a = *b;
+    int R = plan->R;
+    if (aux.nitems > 0 && (use_slots || !a.pre || !aux.match || !aux.ovf_list || aux.nitems > 256)) return (int)hipErrorInvalidValue;
     if (aux.redo && (!aux.ovf_list || aux.Rc < 1)) return (int)hipErrorInvalidValue;
     if ((aux.nitems > 0 || aux.redo) && use64) return (int)hipErrorInvalidValue;   // (the prescan serves primers of <= 31 nt only)
     if (aux.nitems > 0 && !aux.chain) return (int)hipErrorInvalidValue;              // a compact launch needs its redo launch
     if (R > 64) return (int)hipErrorInvalidValue;
-    // d_tile_counter = {tile queue head, overflow tiles, finished workgroups, extra records}: zero at allocation, re-armed
-    // by the last workgroup of every launch (of the last launch of a chain).  Slots mode never uses the bit-sliced scan.
-    const int bsv = demux_bsv(P, use_slots), cm = aux.nitems > 0 ? 1 : (aux.redo ? 2 : 0);
-    const void *fn = demux_fn(use64, bsv, cm, demux_sp(P, use64, bsv, cm, R, aux.nitems, aux.codes2 != nullptr && d_pre != nullptr));
+    // tile_counter = {tile queue head, overflow tiles, finished workgroups, extra records}: zero at allocation, re-armed
+    // by the last workgroup of every launch (of the last launch of a chain).
+    const void *fn = demux_fn(demux_variant(P, use64, use_slots, aux.nitems > 0 ? 1 : (aux.redo ? 2 : 0), R, aux.nitems,
+                                            aux.codes2 != nullptr && a.pre != nullptr));
+    if (!fn) return (int)hipErrorInvalidDeviceFunction;
     smx::DevPanel pv = *P;
-    unsigned long long *counts = (unsigned long long *)d_counts;
-    void *args[] = {&pv, &d_windows, &d_lens, &n_reads, &R, &d_ops, &d_extra, &extra_cap, &d_n_extra, &counts, &d_hits, &d_bdist,
-                    &d_tile_counter, &use_slots, &d_pre, &npad, &aux};
-    hipError_t e = hipLaunchKernel(fn, dim3(grid), dim3(256), args, lds_bytes, (hipStream_t)stream);
+    unsigned long long *counts = (unsigned long long *)a.counts;
+    void *args[] = {&pv, &a.windows, &a.lens, &a.n_reads, &R, &a.ops, &a.extra, &a.extra_cap, &a.n_extra, &counts, &a.hits, &a.bdist,
+                    &a.tile_counter, &use_slots, &a.pre, &a.npad, &aux};
+    hipError_t e = hipLaunchKernel(fn, dim3(grid), dim3(256), args, plan->lds, (hipStream_t)a.stream);
     return (int)(e != hipSuccess ? e : hipGetLastError());
 }
 
-extern "C" size_t smx_demux_lds_bytes(int use64, int NP, int NB, int S, int R, int maxB, int need_starts, int npmeta,
-                                      int kidx, int slots, int bs, int nitems, int ncand, int tails, int nbstab) {
-    return use64 ? (size_t)smx::make_layout<unsigned long long>(NP, NB, S, R, maxB, need_starts, npmeta, kidx, slots, bs, ncand, 0, 0, nitems, tails, nbstab).total
-                 : (size_t)smx::make_layout<unsigned>(NP, NB, S, R, maxB, need_starts, npmeta, kidx, slots, bs, ncand, 0, 0, nitems, tails, nbstab).total;
+// LDS bytes of a tile of R reads (nitems > 0: a compact tile with that many records).  The test caps only shrink a tile.
+extern "C" size_t smx_demux_lds_bytes(const smx::DevPanel *P, int use64, int R, int slots, int nitems) {
+    const smx::LayoutArgs la = smx::layout_args(P->NP, P->NB, P->n_pbc, P->NPAIR, P->trim);
+    auto total = [&](auto w) {
+        return (size_t)smx::make_layout<decltype(w)>(P->NP, P->NB, P->S, R, P->maxB, P->need_starts, la.npmeta, P->kidx, slots, P->bs_ok,
+                                                     la.ncand, 0, 0, nitems, la.tails, P->n_bstab).total;
+    };
+    return use64 ? total(smx_w64()) : total(smx_w32());
 }
 
 extern "C" int smx_set_demux_lds_limit(int use64, size_t bytes) {
     hipError_t e = hipSuccess;
-    for (int bsv = 0; bsv < 4; bsv++)
-        for (int cm = 0; cm < (use64 ? 1 : 3); cm++)
-            for (int sp = 0; sp < (use64 ? 1 : 4); sp++) {
-                if (sp && (bsv != 1 || cm == 2)) continue;
-                if (sp == 2 && cm != 0) continue;
-                if (sp == 3 && cm != 1) continue;
-                hipError_t r = hipFuncSetAttribute(demux_fn(use64, bsv, cm, sp), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-                if (r != hipSuccess) e = r;
-            }
+#define SMX_ROW_LIMIT(W, B, C, S_)                                                                                       \
+    if (W == (use64 ? 64 : 32)) {                                                                                        \
+        const void *fn = demux_fn({W, B, C, S_});                                                                        \
+        hipError_t r = fn ? hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) : hipErrorInvalidDeviceFunction; \
+        if (r != hipSuccess) e = r;                                                                                      \
+    }
+    SMX_DEMUX_VARIANTS(SMX_ROW_LIMIT, SMX_ROW_LIMIT, SMX_ROW_LIMIT)
     return (int)e;
 }
 
 // resident workgroups per CU of the kernel a launch with these parameters would use (cm: 0 dense, 1 compact, 2 redo)
 extern "C" int smx_query_occupancy(const smx::DevPanel *P, int use64, int use_slots, int cm, int R, int nitems, size_t lds_bytes,
                                    int *blocks_per_cu, int have_prescan) {
-    const int bsv = demux_bsv(P, use_slots);
-    hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, demux_fn(use64, bsv, cm, demux_sp(P, use64, bsv, cm, R, nitems, have_prescan != 0)),
-                                                             256, lds_bytes);
+    const void *fn = demux_fn(demux_variant(P, use64, use_slots, cm, R, nitems, have_prescan != 0));
+    if (!fn) return (int)hipErrorInvalidDeviceFunction;
+    hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, fn, 256, lds_bytes);
     // The API divides the CU's 163 840 bytes by the request.  The hardware hands LDS out in 512-byte granules from 159 744
     // bytes (tools/ubench/lds_residency.hip: a 32 256-byte workgroup is resident four times, not five; 54 272 bytes twice,
     // not three times): workgroups the grid counts on but the CU cannot hold would start after the tile queue has drained.

@@ -16,14 +16,14 @@
 #include <stdint.h>
 
 #ifndef SMX_HD
-#if defined(__HIPCC__) || defined(__CUDACC__)
+#if defined(__HIPCC__)
 #define SMX_HD __host__ __device__ __forceinline__
 #else
 #define SMX_HD inline
 #endif
 #endif
 
-#if defined(__HIPCC__) || defined(__CUDACC__)
+#if defined(__HIPCC__)
 #define SMX_MINE_HD __host__ __device__
 #else
 #define SMX_MINE_HD
@@ -37,7 +37,7 @@ namespace smx {
 typedef unsigned long long u64;
 
 // 16 target bytes, one global_load_dwordx4 on the device.  A host caller keeps its targets in arrays of mine_u4.
-#if defined(__HIPCC__) || defined(__CUDACC__)
+#if defined(__HIPCC__)
 typedef uint4 mine_u4;
 SMX_HD mine_u4 mine_u4_zero() { return make_uint4(0, 0, 0, 0); }
 #else

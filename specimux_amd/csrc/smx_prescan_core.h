@@ -36,7 +36,7 @@
 #define SMX_PRESCAN_CORE_H
 #include <stdint.h>
 
-#if defined(__HIPCC__) || defined(__CUDACC__)
+#if defined(__HIPCC__)
 #define SMX_HD __host__ __device__ __forceinline__
 #else
 #define SMX_HD inline
