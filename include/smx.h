@@ -21,6 +21,7 @@
  *           (demultiplex.py:757-766, :612-624): the only bases the hot path ever reads.
  *   smx_mine_*        <- specimine.py's mine_sequences (the separate specimine tool, :197-257): batched long-read
  *           HW distances and the per-partial-read best identity.
+ *   smx_inner_scan    <- nothing: the reference never looks between the two end windows.
  *   smx_counts_*      <- the parent summing (batch_total, batch_matched) (orchestration.py:203-207).
  *
  * Conventions: plain pointers and sizes only; the caller owns every buffer; no callbacks; every
@@ -38,7 +39,7 @@
 extern "C" {
 #endif
 
-#define SMX_ABI_VERSION 6
+#define SMX_ABI_VERSION 7
 
 typedef enum {
     SMX_OK = 0,
@@ -420,6 +421,13 @@ uint32_t smx_batch_size(const smx_batch *batch);
 /* record i: pointers into the batch (valid until the batch is refilled or freed); qual == NULL for FASTA */
 int smx_batch_record(const smx_batch *batch, uint32_t i, const char **id, uint32_t *id_len, const char **seq,
                      const char **qual, uint32_t *seq_len);
+/* record i's whole title: the header line after '@' / '>' (and any white space behind it), trailing white space
+ * stripped; its first white-space-delimited word is the id smx_batch_record gives */
+int smx_batch_title(const smx_batch *batch, uint32_t i, const char **title, uint32_t *title_len);
+/* append every record of the batch, untrimmed, to one of two files: record i goes to flagged_path if flags[i] != 0, else to
+ * clean_path (either may be NULL: those records are dropped).  "@title\nseq\n+\nqual\n", or ">title\nseq\n" for FASTA
+ * records.  The files are opened for appending and closed again; the caller truncates them before the first batch. */
+int smx_batch_write_split(const smx_batch *batch, const uint8_t *flags, const char *clean_path, const char *flagged_path);
 int smx_pack_windows_batch(const smx_batch *batch, int32_t search_len, uint8_t *windows, int32_t *lens);
 int smx_pack_windows4_batch(const smx_batch *batch, int32_t search_len, uint8_t *packed, int32_t *lens, uint32_t *n_ascii_only);
 
@@ -437,6 +445,31 @@ int smx_writer_open(const char *output_dir, const char *prefix, int is_fastq, co
 int smx_writer_write(smx_writer *writer, const smx_batch *batch, const smx_op *ops, uint32_t n_reads,
                      const smx_op *extra, uint32_t n_extra);
 int smx_writer_close(smx_writer *writer);   /* flushes; returns the first I/O error seen, if any */
+
+/*
+ * Inner scan (specimux-chimera): every pattern against the WHOLE read, reporting where it matches outside the two end
+ * windows the demultiplexer searches.  Stand-alone, no panel handle.  Exact, IUPAC equalities as in the demux kernels (a
+ * read byte outside the 15 upper-case letters matches nothing).
+ *   patterns / poff   n_patterns (1..128) patterns (concatenated, n_patterns + 1 offsets), each 1..64 IUPAC letters
+ *   k                 per pattern: threshold, 0 <= k < length
+ *   bases / off       n_reads reads (concatenated, n_reads + 1 offsets), any length, empty allowed
+ *   margin            columns margin <= c < len - margin of a read are internal (margin >= 0)
+ *   max_hits          H, 1..8
+ * D(c) = the last row of the HW (infix) DP of the pattern against the whole read at 0-based column c, i.e. the best NW
+ * distance of the pattern to a read substring that ends at c.  A hit is a maximal run of consecutive internal columns with
+ * D(c) <= k; its distance is the minimum of D over the run, its end the first column of the run with that minimum.
+ *   nhit[r * Q + j]                      number of hits of pattern j in read r, saturating at 255
+ *   hit_dist / hit_end [(r * Q + j) * H + h]   the first min(nhit, H) hits in column order; unused slots -1 / 0
+ * budget_bytes (0 = 1 GiB) bounds the device memory of one launch group: larger inputs run as several chunks of whole
+ * reads inside the call (a single read larger than the budget still runs, alone).  kernel_ms (may be NULL) receives
+ * the device time of the kernels (HIP events).  smx_inner_scan_batch reads the records of a reader batch in place.
+ */
+int smx_inner_scan(const char *patterns, const uint32_t *poff, uint32_t n_patterns, const int32_t *k, const uint8_t *bases,
+                   const uint64_t *off, uint32_t n_reads, int32_t margin, uint32_t max_hits, uint64_t budget_bytes,
+                   uint8_t *nhit, int8_t *hit_dist, int32_t *hit_end, float *kernel_ms);
+int smx_inner_scan_batch(const smx_batch *batch, const char *patterns, const uint32_t *poff, uint32_t n_patterns,
+                         const int32_t *k, int32_t margin, uint32_t max_hits, uint64_t budget_bytes, uint8_t *nhit,
+                         int8_t *hit_dist, int32_t *hit_end, float *kernel_ms);
 
 /* ---- run setup helper (host only)
  * Minimum global edit distance (exact character equality) over all pairs of the n strings seqs[off[i]..off[i+1]):

@@ -9,7 +9,7 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SMX_LIB") or os.path.join(_HERE, "libsmx.so")   # SMX_LIB: A/B builds (tools/tune.sh)
 
-ABI_VERSION = 6
+ABI_VERSION = 7
 OK, ERR_ARG, ERR_UNSUPPORTED, ERR_DEVICE, ERR_OVERFLOW = 0, -1, -2, -3, -4
 TRIM = {"none": 0, "tails": 1, "barcodes": 2, "primers": 3}
 DEREP = {"none": 0, "best": 1}
@@ -79,6 +79,10 @@ SYMBOLS = [
                                      C.POINTER(C.c_float)]),
     ("smx_mine_best_identity", C.c_int, [C.c_char_p, _P, C.c_uint32, _P, C.c_char_p, _P, C.c_uint32, _P, C.c_uint32, _P,
                                          C.POINTER(C.c_float)]),
+    ("smx_inner_scan", C.c_int, [C.c_char_p, _P, C.c_uint32, _P, _P, _P, C.c_uint32, C.c_int32, C.c_uint32, C.c_uint64,
+                                 _P, _P, _P, C.POINTER(C.c_float)]),
+    ("smx_inner_scan_batch", C.c_int, [_P, C.c_char_p, _P, C.c_uint32, _P, C.c_int32, C.c_uint32, C.c_uint64, _P, _P, _P,
+                                       C.POINTER(C.c_float)]),
     ("smx_stats_create", C.c_int, [_P, C.c_uint32, C.POINTER(_P)]),
     ("smx_stats_destroy", None, [_P]),
     ("smx_stats_accumulate_device", C.c_int, [_P, _P, _P, _P, C.c_uint32, _P, C.c_uint32, _P]),
@@ -100,6 +104,8 @@ SYMBOLS = [
     ("smx_batch_size", C.c_uint32, [_P]),
     ("smx_batch_record", C.c_int, [_P, C.c_uint32, C.POINTER(C.c_char_p), C.POINTER(C.c_uint32),
                                    C.POINTER(_P), C.POINTER(_P), C.POINTER(C.c_uint32)]),
+    ("smx_batch_title", C.c_int, [_P, C.c_uint32, C.POINTER(_P), C.POINTER(C.c_uint32)]),
+    ("smx_batch_write_split", C.c_int, [_P, _P, C.c_char_p, C.c_char_p]),
     ("smx_pack_windows_batch", C.c_int, [_P, C.c_int32, _P, _P]),
     ("smx_writer_open", C.c_int, [C.c_char_p, C.c_char_p, C.c_int, _P, C.POINTER(_P)]),
     ("smx_writer_write", C.c_int, [_P, _P, _P, C.c_uint32, _P, C.c_uint32]),

@@ -157,5 +157,12 @@ def trace_main(argv=None):
     return trace_stats.main(argv)
 
 
+def chimera_main(argv=None):
+    """Entry point of the concatemer scan (not in the reference: specimux_amd/chimera.py, `specimux-chimera`); also
+    `python -m specimux_amd.chimera`.  argv without the program name; returns the exit status."""
+    from . import chimera
+    return chimera.main(argv)
+
+
 if __name__ == "__main__":
     main()

@@ -1150,6 +1150,226 @@ int smx_mine_best_identity(const char *queries, const uint64_t *qoff, uint32_t n
     return mine_call(false, queries, qoff, n_queries, k, targets, toff, n_targets, jobs, n_jobs, best, kernel_ms);
 }
 
+// ---- inner scan: every pattern against the whole read, hits on the internal columns (smx_inner.hip)
+extern "C" int smx_batch_seq_view(const smx_batch *b, const char **seq, uint32_t *len);   // smx_io.cpp
+
+namespace {
+std::mutex g_inner_mutex;
+DevBuf g_inner_ws[7];   // bases, read offsets, unit starts, unit reads, records, outputs, pattern tables
+
+struct InnerClass {      // the patterns of one word width, in passes of G
+    int w64 = 0, G = 4, npass = 0;
+    std::vector<uint32_t> idx;        // pattern indices of the call
+    size_t peq_at = 0, tab_at = 0;    // offsets into the table blob: match words; pm, pk, jmap (npass * G ints each)
+};
+
+constexpr uint64_t INNER_DEFAULT_BUDGET = (uint64_t)1 << 30;
+
+// The reads are seq[i][0 .. len[i]); with `flat` they also lie back to back from flat (seq[i] = flat + flat_off[i]).
+int inner_call(const char *patterns, const uint32_t *poff, uint32_t Q, const int32_t *k, const char *const *seq,
+               const uint32_t *len, const uint8_t *flat, uint32_t n_reads, int32_t margin, uint32_t H,
+               uint64_t budget, uint8_t *nhit, int8_t *hit_dist, int32_t *hit_end, float *kernel_ms) {
+    if (!patterns || !poff || !k) return fail(SMX_ERR_ARG, "null argument");
+    if (n_reads && (!seq || !len || !nhit || !hit_dist || !hit_end)) return fail(SMX_ERR_ARG, "null argument");
+    if (Q < 1 || Q > INNER_MAX_PATTERNS) return fail(SMX_ERR_ARG, "n_patterns %u outside 1..%d", Q, INNER_MAX_PATTERNS);
+    if (H < 1 || H > INNER_MAX_HITS) return fail(SMX_ERR_ARG, "max_hits %u outside 1..%d", H, INNER_MAX_HITS);
+    if (margin < 0) return fail(SMX_ERR_ARG, "margin %d is negative", margin);
+    std::vector<unsigned long long> peq((size_t)Q * 16);
+    std::vector<int> pm(Q);
+    InnerClass cls[2];
+    cls[1].w64 = 1;
+    int lead = 1;
+    for (uint32_t j = 0; j < Q; j++) {
+        if (poff[j + 1] <= poff[j] || poff[j + 1] - poff[j] > 64)
+            return fail(SMX_ERR_ARG, "pattern %u: length outside 1..64", j);
+        const int m = (int)(poff[j + 1] - poff[j]);
+        if (k[j] < 0 || k[j] >= m) return fail(SMX_ERR_ARG, "pattern %u: threshold %d outside 0..%d", j, k[j], m - 1);
+        std::string bad;
+        if (!build_peq(patterns + poff[j], m, &peq[(size_t)j * 16], &bad)) return fail(SMX_ERR_ARG, "pattern %u: %s", j, bad.c_str());
+        pm[j] = m;
+        lead = std::max(lead, m + k[j]);
+        cls[m > 32 ? 1 : 0].idx.push_back(j);
+    }
+    const int PL = smx::inner_piece_len(lead), RW = smx::inner_rec_words((int)H);
+    std::lock_guard<std::mutex> guard(g_inner_mutex);
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(SMX_ERR_DEVICE, "libsmx has no CPU path: no HIP device");
+    if (kernel_ms) *kernel_ms = 0.0f;
+    if (n_reads == 0) return SMX_OK;
+    // pattern tables: byte -> code map, then per class the match words [pass][code][G] and pm / pk / jmap
+    std::vector<unsigned char> blob(256);
+    for (int c = 0; c < 256; c++) blob[c] = (unsigned char)code_of((unsigned char)c);
+    for (InnerClass &C : cls) {
+        if (C.idx.empty()) continue;
+        C.G = C.idx.size() <= 4 ? 4 : 8;
+        C.npass = (int)((C.idx.size() + C.G - 1) / C.G);
+        const size_t slots = (size_t)C.npass * C.G;
+        std::vector<int> tab(3 * slots);
+        for (size_t s = 0; s < slots; s++) {
+            const bool real = s < C.idx.size();
+            tab[s] = real ? pm[C.idx[s]] : 1;
+            tab[slots + s] = real ? k[C.idx[s]] : -1;
+            tab[2 * slots + s] = real ? (int)C.idx[s] : -1;
+        }
+        if (C.w64) {
+            std::vector<uint64_t> w(slots * 16, 0);
+            for (size_t s = 0; s < C.idx.size(); s++)
+                for (int c = 0; c < 16; c++) w[((s / C.G) * 16 + c) * C.G + s % C.G] = peq[(size_t)C.idx[s] * 16 + c];
+            C.peq_at = blob_add(blob, w);
+        } else {
+            std::vector<uint32_t> w(slots * 16, 0);
+            for (size_t s = 0; s < C.idx.size(); s++)
+                for (int c = 0; c < 16; c++) w[((s / C.G) * 16 + c) * C.G + s % C.G] = (uint32_t)peq[(size_t)C.idx[s] * 16 + c];
+            C.peq_at = blob_add(blob, w);
+        }
+        C.tab_at = blob_add(blob, tab);
+    }
+    DevBuf *B = g_inner_ws;
+    HIP_TRY(B[6].ensure(blob.size()));
+    HIP_TRY(hipMemcpy(B[6].p, blob.data(), blob.size(), hipMemcpyHostToDevice));
+    if (budget == 0) budget = INNER_DEFAULT_BUDGET;
+    auto pieces_of = [&](uint32_t n) -> uint64_t {
+        return (uint64_t)n > 2 * (uint64_t)margin ? ((uint64_t)n - 2 * (uint64_t)margin + PL - 1) / PL : 0;
+    };
+    const uint64_t out_per_read = (uint64_t)Q * (1 + 5 * (uint64_t)H);
+    struct Events {   // destroyed on every way out of the call
+        hipEvent_t ev[2] = {nullptr, nullptr};
+        ~Events() {
+            for (hipEvent_t e : ev)
+                if (e) (void)hipEventDestroy(e);
+        }
+    } events;
+    hipEvent_t *ev = events.ev;
+    if (kernel_ms) {
+        HIP_TRY(hipEventCreate(&ev[0]));
+        HIP_TRY(hipEventCreate(&ev[1]));
+    }
+    std::vector<uint64_t> roff;
+    std::vector<uint32_t> ustart, unit_read;
+    std::vector<unsigned char> stage, out;
+    // chunks of whole reads: everything one launch group keeps on the device fits the budget (one read always goes)
+    for (uint32_t r0 = 0; r0 < n_reads;) {
+        uint64_t bytes = 64, units = 0, nb = 0;
+        uint32_t r1 = r0;
+        while (r1 < n_reads) {
+            if (len[r1] > (uint32_t)INT32_MAX) return fail(SMX_ERR_ARG, "read %u: longer than 2^31 - 1 bases", r1);
+            const uint64_t np = pieces_of(len[r1]);
+            const uint64_t cost = (uint64_t)len[r1] + 12 + np * (4 + (uint64_t)Q * RW * 4) + out_per_read;
+            if (r1 > r0 && (bytes + cost > budget || units + np > 0x7fffffffull)) break;
+            bytes += cost;
+            units += np;
+            nb += len[r1];
+            r1++;
+        }
+        if (units > 0xffffffffull) return fail(SMX_ERR_UNSUPPORTED, "read %u: too many pieces for one launch", r0);
+        const uint32_t nr = r1 - r0;
+        roff.resize((size_t)nr + 1);
+        ustart.resize((size_t)nr + 1);
+        unit_read.resize((size_t)units);
+        roff[0] = 0;
+        ustart[0] = 0;
+        for (uint32_t i = 0; i < nr; i++) {
+            const uint32_t np = (uint32_t)pieces_of(len[r0 + i]);
+            roff[i + 1] = roff[i] + len[r0 + i];
+            for (uint32_t p = 0; p < np; p++) unit_read[(size_t)ustart[i] + p] = i;
+            ustart[i + 1] = ustart[i] + np;
+        }
+        const unsigned char *src;
+        if (flat) {
+            src = (const unsigned char *)seq[r0];
+        } else {
+            stage.resize((size_t)nb);
+            for (uint32_t i = 0; i < nr; i++)
+                if (len[r0 + i]) memcpy(stage.data() + roff[i], seq[r0 + i], len[r0 + i]);
+            src = stage.data();
+        }
+        const size_t he_bytes = (size_t)nr * Q * H * 4, hd_bytes = (size_t)nr * Q * H, nh_bytes = (size_t)nr * Q;
+        HIP_TRY(B[0].ensure((size_t)nb + 32));
+        HIP_TRY(B[1].ensure(roff.size() * 8));
+        HIP_TRY(B[2].ensure(ustart.size() * 4));
+        HIP_TRY(B[3].ensure(std::max<size_t>(unit_read.size() * 4, 16)));
+        HIP_TRY(B[4].ensure(std::max<size_t>((size_t)units * Q * RW * 4, 16)));
+        HIP_TRY(B[5].ensure(he_bytes + hd_bytes + nh_bytes));
+        if (nb) HIP_TRY(hipMemcpy(B[0].p, src, (size_t)nb, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(B[1].p, roff.data(), roff.size() * 8, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(B[2].p, ustart.data(), ustart.size() * 4, hipMemcpyHostToDevice));
+        if (units) HIP_TRY(hipMemcpy(B[3].p, unit_read.data(), unit_read.size() * 4, hipMemcpyHostToDevice));
+        smx::InnerArgs A{};
+        A.lut = (const unsigned char *)B[6].p;
+        A.bases = (const smx::mine_u4 *)B[0].p;
+        A.roff = (const uint64_t *)B[1].p;
+        A.ustart = (const uint32_t *)B[2].p;
+        A.unit_read = (const uint32_t *)B[3].p;
+        A.n_units = (uint32_t)units;
+        A.Q = (int)Q;
+        A.H = (int)H;
+        A.margin = margin;
+        A.PL = PL;
+        A.lead = lead;
+        A.recs = (uint32_t *)B[4].p;
+        int32_t *d_he = (int32_t *)B[5].p;
+        int8_t *d_hd = (int8_t *)B[5].p + he_bytes;
+        uint8_t *d_nh = (uint8_t *)B[5].p + he_bytes + hd_bytes;
+        if (kernel_ms) HIP_TRY(hipEventRecord(ev[0], nullptr));
+        int e = 0;
+        for (const InnerClass &C : cls) {
+            if (C.idx.empty() || units == 0 || e != 0) continue;
+            const size_t slots = (size_t)C.npass * C.G;
+            A.peq = (const char *)B[6].p + C.peq_at;
+            A.pm = (const int *)((const char *)B[6].p + C.tab_at);
+            A.pk = A.pm + slots;
+            A.jmap = A.pm + 2 * slots;
+            e = smx_launch_inner_scan(nullptr, C.w64, C.G, C.npass, &A);
+        }
+        if (e == 0) e = smx_launch_inner_merge(nullptr, &A, nr, d_nh, d_hd, d_he);
+        if (e != 0) return fail(SMX_ERR_DEVICE, "inner scan launch failed: %s", hipGetErrorString((hipError_t)e));
+        if (kernel_ms) {
+            float ms = 0.0f;
+            HIP_TRY(hipEventRecord(ev[1], nullptr));
+            HIP_TRY(hipEventSynchronize(ev[1]));
+            HIP_TRY(hipEventElapsedTime(&ms, ev[0], ev[1]));
+            *kernel_ms += ms;
+        }
+        HIP_TRY(hipDeviceSynchronize());
+        out.resize(he_bytes + hd_bytes + nh_bytes);
+        HIP_TRY(hipMemcpy(out.data(), B[5].p, out.size(), hipMemcpyDeviceToHost));
+        memcpy(hit_end + (size_t)r0 * Q * H, out.data(), he_bytes);
+        memcpy(hit_dist + (size_t)r0 * Q * H, out.data() + he_bytes, hd_bytes);
+        memcpy(nhit + (size_t)r0 * Q, out.data() + he_bytes + hd_bytes, nh_bytes);
+        r0 = r1;
+    }
+    return SMX_OK;
+}
+}  // namespace
+
+int smx_inner_scan(const char *patterns, const uint32_t *poff, uint32_t n_patterns, const int32_t *k, const uint8_t *bases,
+                   const uint64_t *off, uint32_t n_reads, int32_t margin, uint32_t max_hits, uint64_t budget_bytes,
+                   uint8_t *nhit, int8_t *hit_dist, int32_t *hit_end, float *kernel_ms) {
+    if (n_reads && (!bases || !off)) return fail(SMX_ERR_ARG, "null argument");
+    std::vector<const char *> seq(n_reads);
+    std::vector<uint32_t> len(n_reads);
+    for (uint32_t i = 0; i < n_reads; i++) {
+        if (off[i + 1] < off[i] || off[i + 1] - off[i] > (uint64_t)INT32_MAX) return fail(SMX_ERR_ARG, "read %u: bad offsets", i);
+        seq[i] = (const char *)bases + off[i];
+        len[i] = (uint32_t)(off[i + 1] - off[i]);
+    }
+    return inner_call(patterns, poff, n_patterns, k, seq.data(), len.data(), bases, n_reads, margin, max_hits, budget_bytes,
+                      nhit, hit_dist, hit_end, kernel_ms);
+}
+
+int smx_inner_scan_batch(const smx_batch *batch, const char *patterns, const uint32_t *poff, uint32_t n_patterns,
+                         const int32_t *k, int32_t margin, uint32_t max_hits, uint64_t budget_bytes, uint8_t *nhit,
+                         int8_t *hit_dist, int32_t *hit_end, float *kernel_ms) {
+    if (!batch) return fail(SMX_ERR_ARG, "null argument");
+    const uint32_t n_reads = smx_batch_size(batch);
+    std::vector<const char *> seq(n_reads);
+    std::vector<uint32_t> len(n_reads);
+    int rc = smx_batch_seq_view(batch, seq.data(), len.data());
+    if (rc != SMX_OK) return rc;
+    return inner_call(patterns, poff, n_patterns, k, seq.data(), len.data(), nullptr, n_reads, margin, max_hits, budget_bytes,
+                      nhit, hit_dist, hit_end, kernel_ms);
+}
+
 // ---- lanes: asynchronous host-buffer path (pinned staging, one stream per lane)
 struct smx_lane {
     smx_panel *P = nullptr;

@@ -6,6 +6,7 @@
 #include "smx.h"
 #include "smx_prescan_core.h"
 #include "smx_mine_core.h"
+#include "smx_inner_core.h"
 
 // LDS a CU of gfx950 gives to workgroups (in 512-byte granules): measured, tools/ubench/lds_residency.hip
 #define SMX_LDS_POOL ((size_t)159744)
@@ -97,6 +98,20 @@ struct MinePair {     // one (job, query) pair, ceil(nt / MINE_THREADS) target c
     uint32_t pad;
 };
 
+// inner scan (smx_inner.hip): one chunk of whole reads and one word-width class of patterns.  Device pointers.
+struct InnerArgs {
+    const void *peq;               // [pass][16 codes][G] match words, 32 or 64 bits wide
+    const int *pm, *pk, *jmap;     // [pass * G]: pattern length, threshold (-1: padding slot), index in the call (-1: padding)
+    const unsigned char *lut;      // 256: read byte -> code
+    const mine_u4 *bases;          // the chunk's reads back to back, 16 spare bytes behind them
+    const uint64_t *roff;          // n_reads + 1 byte offsets into bases
+    const uint32_t *unit_read;     // per unit: its read
+    const uint32_t *ustart;        // n_reads + 1: first unit of each read
+    uint32_t n_units;
+    int Q, H, margin, PL, lead;
+    uint32_t *recs;                // n_units * Q records of inner_rec_words(H) words
+};
+
 }  // namespace smx
 
 extern "C" {
@@ -131,5 +146,10 @@ int smx_launch_mine(void *stream, int wr, int dist, const unsigned char *d_q, co
                     const uint64_t *d_toff, const int32_t *d_tlen, const void *d_pairs, const uint64_t *d_chunk_start,
                     uint32_t n_pairs, const void *d_jobs, int grid, uint64_t per_block, size_t lds_bytes, void *d_out,
                     unsigned long long *d_scratch, int scratch_words);
+// inner scan (smx_inner.hip): the scan over A->n_units units x npass passes of G (4 or 8) patterns, w64 = 64-bit words;
+// then one merge launch over n_reads x A->Q (read, pattern) pairs once every class has left its records
+int smx_launch_inner_scan(void *stream, int w64, int G, int npass, const smx::InnerArgs *A);
+int smx_launch_inner_merge(void *stream, const smx::InnerArgs *A, uint32_t n_reads, uint8_t *d_nhit, int8_t *d_hit_dist,
+                           int32_t *d_hit_end);
 }
 #endif

@@ -113,6 +113,7 @@ struct Mapping {
 struct Rec {
     uint64_t id_off, seq_off, qual_off;   // into the segment's base; qual_off == UINT64_MAX for FASTA
     uint32_t id_len, seq_len;
+    uint32_t title_len;                   // the whole title (trailing white space stripped) starts at id_off; the id is its first word
     uint64_t src_off;                     // fast engine: offset of the record's '@' inside the block
 };
 
@@ -249,9 +250,12 @@ int next_general(smx_reader *r, uint32_t max_reads, uint64_t max_bytes, smx_batc
             while (a < n && is_space((unsigned char)p[a])) a++;
             size_t e = a;
             while (e < n && !is_space((unsigned char)p[e])) e++;
+            size_t te = n;
+            while (te > e && is_space((unsigned char)p[te - 1])) te--;
             rec.id_off = data.size();
             rec.id_len = (uint32_t)(e - a);
-            data.insert(data.end(), p + a, p + e);
+            rec.title_len = (uint32_t)(te - a);
+            data.insert(data.end(), p + a, p + te);
             rec.seq_off = data.size();
             bool plus = false;
             while (r->next_line(&p, &n)) {
@@ -284,9 +288,12 @@ int next_general(smx_reader *r, uint32_t max_reads, uint64_t max_bytes, smx_batc
             while (a < n && is_space((unsigned char)p[a])) a++;
             size_t e = a;
             while (e < n && !is_space((unsigned char)p[e])) e++;
+            size_t te = n;
+            while (te > e && is_space((unsigned char)p[te - 1])) te--;
             rec.id_off = data.size();
             rec.id_len = (uint32_t)(e - a);
-            data.insert(data.end(), p + a, p + e);
+            rec.title_len = (uint32_t)(te - a);
+            data.insert(data.end(), p + a, p + te);
             rec.seq_off = data.size();
             for (;;) {
                 int c = r->peek();
@@ -355,6 +362,9 @@ bool parse_strict(const char *base, const char *p, const char *stop, const char 
         while (ie < e1 && !is_space((unsigned char)*ie)) ie++;
         r.id_off = (uint64_t)(a - base);
         r.id_len = (uint32_t)(ie - a);
+        const char *te = e1;
+        while (te > ie && is_space((unsigned char)te[-1])) te--;
+        r.title_len = (uint32_t)(te - a);
         const char *se = e2;
         while (se > s && is_space((unsigned char)se[-1])) se--;
         const char *qe = e4;
@@ -994,6 +1004,64 @@ int smx_batch_record(const smx_batch *b, uint32_t i, const char **id, uint32_t *
     if (seq) *seq = sg->base + r->seq_off;
     if (qual) *qual = r->qual_off == UINT64_MAX ? nullptr : sg->base + r->qual_off;
     if (seq_len) *seq_len = r->seq_len;
+    return SMX_OK;
+}
+
+int smx_batch_title(const smx_batch *b, uint32_t i, const char **title, uint32_t *title_len) {
+    if (!b || i >= b->n || !title || !title_len) return smx_set_error(SMX_ERR_ARG, "record index out of range");
+    const Segment *sg;
+    const Rec *r;
+    b->locate(i, &sg, &r);
+    *title = sg->base + r->id_off;
+    *title_len = r->title_len;
+    return SMX_OK;
+}
+
+int smx_batch_write_split(const smx_batch *b, const uint8_t *flags, const char *clean_path, const char *flagged_path) {
+    if (!b || (b->n && !flags)) return smx_set_error(SMX_ERR_ARG, "null argument");
+    std::string out[2];
+    const char *paths[2] = {clean_path, flagged_path};
+    for (size_t k = 0; k < b->segs.size(); k++) {
+        const Segment &sg = b->segs[k];
+        for (size_t j = 0; j < sg.recs.size(); j++) {
+            const Rec &r = sg.recs[j];
+            const int side = flags[(size_t)b->first[k] + j] ? 1 : 0;
+            if (!paths[side]) continue;
+            std::string &o = out[side];
+            const bool fq = r.qual_off != UINT64_MAX;
+            o.push_back(fq ? '@' : '>');
+            o.append(sg.base + r.id_off, r.title_len);
+            o.push_back('\n');
+            o.append(sg.base + r.seq_off, r.seq_len);
+            if (fq) {
+                o.append("\n+\n");
+                o.append(sg.base + r.qual_off, r.seq_len);
+            }
+            o.push_back('\n');
+        }
+    }
+    for (int side = 0; side < 2; side++) {
+        if (!paths[side]) continue;
+        FILE *fh = fopen(paths[side], "ab");
+        if (!fh) return smx_set_error(SMX_ERR_ARG, "cannot open %s: %s", paths[side], strerror(errno));
+        const bool ok = out[side].empty() || fwrite(out[side].data(), 1, out[side].size(), fh) == out[side].size();
+        if (fclose(fh) != 0 || !ok) return smx_set_error(SMX_ERR_ARG, "write %s: %s", paths[side], strerror(errno));
+    }
+    return SMX_OK;
+}
+
+// internal (smx_api.cpp, smx_inner_scan_batch): where every record's sequence lies, in batch order; the pointers are
+// valid as long as smx_batch_record's are
+extern "C" int smx_batch_seq_view(const smx_batch *b, const char **seq, uint32_t *len) {
+    if (!b || (b->n && (!seq || !len))) return smx_set_error(SMX_ERR_ARG, "null argument");
+    for (size_t k = 0; k < b->segs.size(); k++) {
+        const Segment &sg = b->segs[k];
+        for (size_t j = 0; j < sg.recs.size(); j++) {
+            const size_t i = (size_t)b->first[k] + j;
+            seq[i] = sg.base + sg.recs[j].seq_off;
+            len[i] = sg.recs[j].seq_len;
+        }
+    }
     return SMX_OK;
 }
 

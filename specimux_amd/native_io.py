@@ -30,6 +30,20 @@ class Batch:
             qual = C.string_at(pqual.value, nseq.value).decode("latin-1") if nseq.value else ""
         return rid, seq, qual
 
+    def title(self, i):
+        """The whole header line of record i (without '@' / '>', trailing white space stripped) as bytes."""
+        p, n = C.c_void_p(), C.c_uint32()
+        _lib.check(self._lib.smx_batch_title(self.handle, i, C.byref(p), C.byref(n)))
+        return C.string_at(p.value, n.value) if n.value else b""
+
+    def write_split(self, flags, clean_path, flagged_path):
+        """Append the batch's records, untrimmed and with their whole titles, to clean_path (flags[i] == 0) or flagged_path
+        (either may be None).  Written by libsmx (smx_batch_write_split)."""
+        flags = np.ascontiguousarray(flags, dtype=np.uint8)
+        assert len(flags) == len(self)
+        _lib.check(self._lib.smx_batch_write_split(self.handle, _lib.ptr(flags), clean_path.encode() if clean_path else None,
+                                                   flagged_path.encode() if flagged_path else None))
+
     def pack_windows(self, search_len, stride):
         n = len(self)
         windows = np.empty((n, stride), dtype=np.uint8)
