@@ -1,0 +1,481 @@
+// smx_calls.cpp -- the one-shot calls of libsmx.so over host buffers: alignments (smx_align, smx_align_batch), specimine
+// (smx_mine.hip) and the inner scan (smx_inner.hip).  Each keeps one grow-only device workspace; its calls are serialised.
+#include "smx_host.h"
+
+int smx_align(const char *query, int qlen, const char *target, int tlen, int k, int mode, int *dist, int *starts,
+              int *ends, int cap, int *nloc) {
+    if (!query || !target || !dist || !nloc) return fail(SMX_ERR_ARG, "null argument");
+    if (qlen < 1 || qlen > 64) return fail(SMX_ERR_UNSUPPORTED, "query length %d outside 1..64", qlen);
+    if (mode != 0 && mode != 1) return fail(SMX_ERR_UNSUPPORTED, "mode %d (0 = HW, 1 = SHW)", mode);
+    if (tlen < 1) return fail(SMX_ERR_UNSUPPORTED, "empty target");
+    SMX_TRY(require_device());
+    unsigned long long peq[32];
+    std::string bad, q(query, qlen), rq(q.rbegin(), q.rend());
+    if (!build_peq(q.data(), qlen, peq, &bad) || !build_peq(rq.data(), qlen, peq + 16, &bad))
+        return fail(SMX_ERR_UNSUPPORTED, "%s", bad.c_str());
+    std::vector<unsigned char> codes(tlen);
+    for (int i = 0; i < tlen; i++) codes[i] = (unsigned char)code_of((unsigned char)target[i]);
+    DevMem<unsigned char> d;
+    size_t o_codes = 256, o_flag = o_codes + ((tlen + 15) & ~15), o_starts = o_flag + ((tlen + 15) & ~15),
+           o_dist = o_starts + (size_t)tlen * 4, total = o_dist + 16;
+    HIP_TRY(d.alloc(total));
+    hipError_t e = hipMemcpy(d, peq, 256, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d + o_codes, codes.data(), tlen, hipMemcpyHostToDevice);
+    if (e == hipSuccess)
+        e = (hipError_t)smx_launch_align(nullptr, (unsigned long long *)d.p, (unsigned long long *)d.p + 16, qlen, d + o_codes,
+                                         tlen, k, mode, (int *)(d + o_dist), d + o_flag, (int *)(d + o_starts));
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    std::vector<unsigned char> flag(tlen);
+    std::vector<int> st(tlen);
+    if (e == hipSuccess) e = hipMemcpy(dist, d + o_dist, 4, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(flag.data(), d + o_flag, tlen, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(st.data(), d + o_starts, (size_t)tlen * 4, hipMemcpyDeviceToHost);
+    if (e != hipSuccess) return fail(SMX_ERR_DEVICE, "smx_align: %s", hipGetErrorString(e));
+    int cnt = 0;
+    if (*dist >= 0)
+        for (int j = 0; j < tlen; j++)
+            if (flag[j]) {
+                if (cnt < cap && starts && ends) { starts[cnt] = st[j]; ends[cnt] = j; }
+                cnt++;
+            }
+    *nloc = cnt;
+    return SMX_OK;
+}
+
+// ---- batched alignments: grow-only device workspace shared by all calls (serialised)
+static struct {
+    std::mutex mutex;
+    DevBuf qpeq, qlen, qidx, codes, toff, k, mode;    // what the call uploads
+    DevBuf scores, dist, nloc, starts, ends;    // the raw score of every target column, and what comes back
+} g_align;
+
+int smx_align_batch(const char *queries, const uint32_t *qoff, uint32_t n_queries, const char *targets, const uint64_t *toff,
+                    const uint32_t *qidx, const int32_t *k, const uint8_t *mode, uint32_t n, int32_t *dist, int32_t *nloc,
+                    int32_t *starts, int32_t *ends, uint32_t cap) {
+    if (!queries || !qoff || !targets || !toff || !qidx || !k || !mode || !dist || !nloc || (cap && (!starts || !ends)))
+        return fail(SMX_ERR_ARG, "null argument");
+    if (n == 0) return SMX_OK;
+    SMX_TRY(require_device());
+    std::vector<unsigned long long> qpeq((size_t)n_queries * 32);
+    std::vector<int> qlen(n_queries);
+    std::string bad;
+    for (uint32_t q = 0; q < n_queries; q++) {
+        const int m = (int)(qoff[q + 1] - qoff[q]);
+        if (m < 1 || m > 64) return fail(SMX_ERR_UNSUPPORTED, "query %u: length %d outside 1..64", q, m);
+        std::string s(queries + qoff[q], m), r(s.rbegin(), s.rend());
+        if (!build_peq(s.data(), m, &qpeq[(size_t)q * 32], &bad) || !build_peq(r.data(), m, &qpeq[(size_t)q * 32 + 16], &bad))
+            return fail(SMX_ERR_UNSUPPORTED, "query %u: %s", q, bad.c_str());
+        qlen[q] = m;
+    }
+    const uint64_t tbytes = toff[n];
+    std::vector<unsigned char> codes(tbytes);
+    for (uint32_t i = 0; i < n; i++) {
+        if (toff[i + 1] <= toff[i]) return fail(SMX_ERR_UNSUPPORTED, "alignment %u: empty target", i);
+        if (qidx[i] >= n_queries || mode[i] > 1) return fail(SMX_ERR_ARG, "alignment %u: bad query index or mode", i);
+        if (k[i] < 0 || k[i] > 250) return fail(SMX_ERR_ARG, "alignment %u: bad max distance", i);
+    }
+    for (uint64_t j = 0; j < tbytes; j++) codes[j] = (unsigned char)code_of((unsigned char)targets[j]);
+    std::lock_guard<std::mutex> guard(g_align.mutex);
+    auto &W = g_align;
+    const size_t nbytes = (size_t)n * 4, loc_bytes = (size_t)n * cap * 4;
+    HIP_TRY(W.qpeq.upload(qpeq));
+    HIP_TRY(W.qlen.upload(qlen));
+    HIP_TRY(W.qidx.upload(qidx, nbytes));
+    HIP_TRY(W.codes.upload(codes));
+    HIP_TRY(W.toff.upload(toff, ((size_t)n + 1) * 8));
+    HIP_TRY(W.k.upload(k, nbytes));
+    HIP_TRY(W.mode.upload(mode, n));
+    HIP_TRY(W.scores.ensure((size_t)tbytes));
+    for (DevBuf *b : {&W.dist, &W.nloc}) HIP_TRY(b->ensure(nbytes));
+    for (DevBuf *b : {&W.starts, &W.ends}) HIP_TRY(b->ensure(loc_bytes));
+    int e = smx_launch_align_batch(nullptr, W.qpeq.as<unsigned long long>(), W.qlen.as<int>(), W.qidx.as<unsigned>(),
+                                   W.codes.as<unsigned char>(), W.toff.as<unsigned long long>(), W.k.as<int>(),
+                                   W.mode.as<unsigned char>(), n, W.scores.as<unsigned char>(), W.dist.as<int>(),
+                                   W.nloc.as<int>(), W.starts.as<int>(), W.ends.as<int>(), cap);
+    if (e != 0) return fail(SMX_ERR_DEVICE, "alignment kernel launch failed: %s", hipGetErrorString((hipError_t)e));
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(dist, W.dist.p, nbytes, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(nloc, W.nloc.p, nbytes, hipMemcpyDeviceToHost));
+    if (cap) {
+        HIP_TRY(hipMemcpy(starts, W.starts.p, loc_bytes, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(ends, W.ends.p, loc_bytes, hipMemcpyDeviceToHost));
+    }
+    return SMX_OK;
+}
+
+// ---- specimine: batched long-read HW distances (smx_mine.hip); grow-only device workspace, calls serialised
+namespace {
+struct {
+    std::mutex mutex;
+    DevBuf queries, qoff, targets, tdoff, tlen, pairs, chunk_start;
+    DevBuf scratch;     // per-lane state of the generic class, one slice per workgroup
+    DevBuf jobs_out;    // the jobs, then the output
+} g_mine;
+
+// per query: LDS bytes of its Peq table ((distinct bytes + 1) x padded words) and the register class of its per-lane state
+int mine_queries(const char *queries, const uint64_t *qoff, uint32_t n_queries, std::vector<size_t> *qlds_out,
+                 std::vector<int> *qclass_out) {
+    std::vector<size_t> &qlds = *qlds_out;
+    std::vector<int> &qclass = *qclass_out;
+    qlds.assign(n_queries, 0);
+    qclass.assign(n_queries, 0);
+    for (uint32_t q = 0; q < n_queries; q++) {
+        if (qoff[q + 1] <= qoff[q]) return fail(SMX_ERR_ARG, "query %u is empty", q);
+        const uint64_t m = qoff[q + 1] - qoff[q];
+        if (m > (uint64_t)INT32_MAX) return fail(SMX_ERR_UNSUPPORTED, "query %u: length %llu", q, (unsigned long long)m);
+        bool seen[256] = {false};
+        int rows = 0;
+        for (uint64_t i = qoff[q]; i < qoff[q + 1]; i++) {
+            const unsigned char c = (unsigned char)queries[i];
+            if (!seen[c]) { seen[c] = true; rows++; }
+        }
+        const size_t W = (size_t)((m + 63) / 64), Wp = W | 1;
+        qlds[q] = (MINE_LDS_HEAD + (size_t)(rows + 1) * Wp) * 8;
+        if (qlds[q] > SMX_LDS_POOL)
+            return fail(SMX_ERR_UNSUPPORTED, "query %u: %d distinct bytes x %zu words do not fit the LDS (%zu > %zu bytes)", q,
+                        rows, W, qlds[q], (size_t)SMX_LDS_POOL);
+        qclass[q] = W <= 1 ? 1 : W <= 2 ? 2 : W <= 4 ? 3 : W <= 8 ? 4 : W <= 16 ? 5 : 0;
+    }
+    return SMX_OK;
+}
+
+// targets: 16-byte aligned copies, 16 bytes of slack at the end (the kernel loads 16 bytes at a time)
+int mine_targets(const char *targets, const uint64_t *toff, uint32_t n_targets, std::vector<uint64_t> *tdoff_out,
+                 std::vector<int32_t> *tlen_out, std::vector<unsigned char> *tpad) {
+    std::vector<uint64_t> &tdoff = *tdoff_out;
+    std::vector<int32_t> &tlen = *tlen_out;
+    tdoff.assign(n_targets, 0);
+    tlen.assign(n_targets, 0);
+    uint64_t tbytes = 0;
+    for (uint32_t t = 0; t < n_targets; t++) {
+        if (toff[t + 1] < toff[t] || toff[t + 1] - toff[t] > (uint64_t)INT32_MAX) return fail(SMX_ERR_ARG, "target %u: bad offsets", t);
+        tdoff[t] = tbytes;
+        tlen[t] = (int32_t)(toff[t + 1] - toff[t]);
+        tbytes += ((uint64_t)tlen[t] + 15) & ~(uint64_t)15;
+    }
+    tbytes += 16;
+    tpad->assign(tbytes, 0);
+    for (uint32_t t = 0; t < n_targets; t++) memcpy(tpad->data() + tdoff[t], targets + toff[t], (size_t)tlen[t]);
+    return SMX_OK;
+}
+
+// One smx_mine_* call.  distances: job j's nq x nt distances at out[sum over earlier jobs of nq * nt] (int32); else
+// the best identities at out[sum over earlier jobs of nt] (double).  Device and host memory hold the queries, the
+// targets, sum(nq) (job, query) pairs and the output: only the distance output grows with sum(nq * nt).
+int mine_call(bool distances, const char *queries, const uint64_t *qoff, uint32_t n_queries, const int32_t *k,
+              const char *targets, const uint64_t *toff, uint32_t n_targets, const smx_mine_job *jobs, uint32_t n_jobs,
+              void *out, float *kernel_ms) {
+    if (!out && n_jobs) return fail(SMX_ERR_ARG, "null argument");
+    if (!queries || !qoff || !k || !targets || !toff || (n_jobs && !jobs)) return fail(SMX_ERR_ARG, "null argument");
+    std::lock_guard<std::mutex> guard(g_mine.mutex);
+    SMX_TRY(require_device());
+    std::vector<size_t> qlds;
+    std::vector<int> qclass;
+    SMX_TRY(mine_queries(queries, qoff, n_queries, &qlds, &qclass));
+    std::vector<uint64_t> tdoff;
+    std::vector<int32_t> tlen;
+    std::vector<unsigned char> tpad;
+    SMX_TRY(mine_targets(targets, toff, n_targets, &tdoff, &tlen, &tpad));
+    // jobs -> (job, query) pairs with at least one target, grouped by register class, in query order within a class
+    // (a workgroup rebuilds the Peq table only when the query changes)
+    std::vector<smx::MineJobDev> djobs(n_jobs);
+    std::vector<smx::MinePair> pairs[6];
+    size_t lds_max[6] = {0, 0, 0, 0, 0, 0};
+    int words_max0 = 0;
+    uint64_t dist_off = 0, best_off = 0;
+    for (uint32_t j = 0; j < n_jobs; j++) {
+        const smx_mine_job &J = jobs[j];
+        if ((uint64_t)J.q0 + J.nq > n_queries || (uint64_t)J.t0 + J.nt > n_targets)
+            return fail(SMX_ERR_ARG, "job %u: query or target range out of bounds", j);
+        djobs[j] = smx::MineJobDev{J.q0, J.nq, J.t0, J.nt, dist_off, best_off, J.min_identity};
+        dist_off += (uint64_t)J.nq * J.nt;
+        best_off += J.nt;
+        if (J.nt == 0) continue;
+        for (uint32_t i = 0; i < J.nq; i++) {
+            const uint32_t q = J.q0 + i;
+            const int c = qclass[q];
+            lds_max[c] = std::max(lds_max[c], qlds[q]);
+            if (c == 0) words_max0 = std::max(words_max0, (int)((qoff[q + 1] - qoff[q] + 63) / 64));
+            pairs[c].push_back(smx::MinePair{j, q, k[q], 0});
+        }
+    }
+    const uint64_t n_out = distances ? dist_off : best_off;
+    if (n_out == 0) {
+        if (kernel_ms) *kernel_ms = 0.0f;
+        return SMX_OK;
+    }
+    const size_t out_bytes = n_out * (distances ? sizeof(int32_t) : sizeof(double));
+    std::vector<uint64_t> chunk_start;            // per class: n + 1 prefix entries, one after the other
+    uint64_t chunks[6] = {0, 0, 0, 0, 0, 0};
+    for (int c = 0; c < 6; c++) {
+        std::stable_sort(pairs[c].begin(), pairs[c].end(),
+                         [](const smx::MinePair &a, const smx::MinePair &b) { return a.q < b.q; });
+        if (pairs[c].empty()) continue;
+        chunk_start.push_back(0);
+        for (const smx::MinePair &P : pairs[c]) {
+            chunks[c] += (djobs[P.job].nt + MINE_THREADS - 1) / MINE_THREADS;
+            chunk_start.push_back(chunks[c]);
+        }
+    }
+    // a workgroup takes MINE_BLOCK_CHUNKS chunks in a row (more where the grid is capped): the pair search and the
+    // Peq build of a query's run of chunks are paid once.  Measured on MI355X: one chunk per
+    // workgroup loses 1.5x on runs of cheap (decoy) chunks, runs of 8 lose ~11 % to balance on costly chunks
+    constexpr uint64_t MINE_BLOCK_CHUNKS = 8;
+    const uint64_t grid_cap = (uint64_t)INT32_MAX;
+    // the generic class keeps its per-lane state in a global slice per workgroup: bound its grid to ~256 MiB of it
+    const size_t slice = (size_t)3 * words_max0 * MINE_THREADS * 8;
+    const uint64_t grid0_cap = std::max<size_t>(1, ((size_t)256 << 20) / std::max<size_t>(slice, 1));
+    auto &W = g_mine;
+    std::vector<smx::MinePair> all_pairs;   // class after class
+    for (int c = 0; c < 6; c++) all_pairs.insert(all_pairs.end(), pairs[c].begin(), pairs[c].end());
+    const size_t jobs_bytes = n_jobs * sizeof(smx::MineJobDev);
+    HIP_TRY(W.queries.upload(queries, (size_t)qoff[n_queries]));
+    HIP_TRY(W.qoff.upload(qoff, ((size_t)n_queries + 1) * 8));
+    HIP_TRY(W.targets.upload(tpad));
+    HIP_TRY(W.tdoff.upload(tdoff));
+    HIP_TRY(W.tlen.upload(tlen));
+    HIP_TRY(W.pairs.upload(all_pairs));
+    HIP_TRY(W.chunk_start.upload(chunk_start));
+    if (!pairs[0].empty()) HIP_TRY(W.scratch.ensure((size_t)std::min(chunks[0], grid0_cap) * slice));
+    HIP_TRY(W.jobs_out.upload(djobs.data(), jobs_bytes, out_bytes));
+    void *d_out = W.jobs_out.as<char>() + jobs_bytes;
+    if (!distances) HIP_TRY(hipMemset(d_out, 0, out_bytes));       // +0.0: "no pair counts"
+    KernelTimer timer;
+    if (kernel_ms) HIP_TRY(timer.start());
+    static const int kWords[6] = {0, 1, 2, 4, 8, 16};
+    size_t pat = 0, cat = 0;
+    int e = 0;
+    for (int c = 0; c < 6 && e == 0; c++) {
+        const uint32_t n = (uint32_t)pairs[c].size();
+        if (!n) continue;
+        const uint64_t cap = c == 0 ? std::min(grid_cap, grid0_cap) : grid_cap;
+        const uint64_t per_block = std::max(MINE_BLOCK_CHUNKS, (chunks[c] + cap - 1) / cap);
+        const uint64_t grid = (chunks[c] + per_block - 1) / per_block;
+        e = smx_launch_mine(nullptr, kWords[c], distances, W.queries.as<unsigned char>(), W.qoff.as<uint64_t>(),
+                            W.targets.as<unsigned char>(), W.tdoff.as<uint64_t>(), W.tlen.as<int32_t>(),
+                            W.pairs.as<smx::MinePair>() + pat, W.chunk_start.as<uint64_t>() + cat, n, W.jobs_out.p, (int)grid,
+                            per_block, lds_max[c], d_out, W.scratch.as<unsigned long long>(), words_max0);
+        pat += n;
+        cat += (size_t)n + 1;
+    }
+    if (e != 0) return fail(SMX_ERR_DEVICE, "mining kernel launch failed: %s", hipGetErrorString((hipError_t)e));
+    if (kernel_ms) HIP_TRY(timer.stop(kernel_ms));
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(out, d_out, out_bytes, hipMemcpyDeviceToHost));
+    return SMX_OK;
+}
+}  // namespace
+
+int smx_mine_distances(const char *queries, const uint64_t *qoff, uint32_t n_queries, const int32_t *k, const char *targets,
+                       const uint64_t *toff, uint32_t n_targets, const smx_mine_job *jobs, uint32_t n_jobs, int32_t *dist,
+                       float *kernel_ms) {
+    return mine_call(true, queries, qoff, n_queries, k, targets, toff, n_targets, jobs, n_jobs, dist, kernel_ms);
+}
+
+int smx_mine_best_identity(const char *queries, const uint64_t *qoff, uint32_t n_queries, const int32_t *k,
+                           const char *targets, const uint64_t *toff, uint32_t n_targets, const smx_mine_job *jobs,
+                           uint32_t n_jobs, double *best, float *kernel_ms) {
+    return mine_call(false, queries, qoff, n_queries, k, targets, toff, n_targets, jobs, n_jobs, best, kernel_ms);
+}
+
+// ---- inner scan: every pattern against the whole read, hits on the internal columns (smx_inner.hip)
+extern "C" int smx_batch_seq_view(const smx_batch *b, const char **seq, uint32_t *len);   // smx_io.cpp
+
+namespace {
+struct {
+    std::mutex mutex;
+    DevBuf bases, roff, ustart, unit_read, recs, out, tables;
+} g_inner;
+
+struct InnerClass {      // the patterns of one word width, in passes of G
+    int w64 = 0, G = 4, npass = 0;
+    std::vector<uint32_t> idx;        // pattern indices of the call
+    size_t peq_at = 0, tab_at = 0;    // offsets into the table blob: match words; pm, pk, jmap (npass * G ints each)
+};
+
+constexpr uint64_t INNER_DEFAULT_BUDGET = (uint64_t)1 << 30;
+
+// The reads are seq[i][0 .. len[i]); with `flat` they also lie back to back from flat (seq[i] = flat + flat_off[i]).
+int inner_call(const char *patterns, const uint32_t *poff, uint32_t Q, const int32_t *k, const char *const *seq,
+               const uint32_t *len, const uint8_t *flat, uint32_t n_reads, int32_t margin, uint32_t H,
+               uint64_t budget, uint8_t *nhit, int8_t *hit_dist, int32_t *hit_end, float *kernel_ms) {
+    if (!patterns || !poff || !k) return fail(SMX_ERR_ARG, "null argument");
+    if (n_reads && (!seq || !len || !nhit || !hit_dist || !hit_end)) return fail(SMX_ERR_ARG, "null argument");
+    if (Q < 1 || Q > INNER_MAX_PATTERNS) return fail(SMX_ERR_ARG, "n_patterns %u outside 1..%d", Q, INNER_MAX_PATTERNS);
+    if (H < 1 || H > INNER_MAX_HITS) return fail(SMX_ERR_ARG, "max_hits %u outside 1..%d", H, INNER_MAX_HITS);
+    if (margin < 0) return fail(SMX_ERR_ARG, "margin %d is negative", margin);
+    std::vector<unsigned long long> peq((size_t)Q * 16);
+    std::vector<int> pm(Q);
+    InnerClass cls[2];
+    cls[1].w64 = 1;
+    int lead = 1;
+    for (uint32_t j = 0; j < Q; j++) {
+        if (poff[j + 1] <= poff[j] || poff[j + 1] - poff[j] > 64)
+            return fail(SMX_ERR_ARG, "pattern %u: length outside 1..64", j);
+        const int m = (int)(poff[j + 1] - poff[j]);
+        if (k[j] < 0 || k[j] >= m) return fail(SMX_ERR_ARG, "pattern %u: threshold %d outside 0..%d", j, k[j], m - 1);
+        std::string bad;
+        if (!build_peq(patterns + poff[j], m, &peq[(size_t)j * 16], &bad)) return fail(SMX_ERR_ARG, "pattern %u: %s", j, bad.c_str());
+        pm[j] = m;
+        lead = std::max(lead, m + k[j]);
+        cls[m > 32 ? 1 : 0].idx.push_back(j);
+    }
+    const int PL = smx::inner_piece_len(lead), RW = smx::inner_rec_words((int)H);
+    std::lock_guard<std::mutex> guard(g_inner.mutex);
+    SMX_TRY(require_device());
+    if (kernel_ms) *kernel_ms = 0.0f;
+    if (n_reads == 0) return SMX_OK;
+    // pattern tables: byte -> code map, then per class the match words [pass][code][G] and pm / pk / jmap
+    std::vector<unsigned char> blob(256);
+    for (int c = 0; c < 256; c++) blob[c] = (unsigned char)code_of((unsigned char)c);
+    for (InnerClass &C : cls) {
+        if (C.idx.empty()) continue;
+        C.G = C.idx.size() <= 4 ? 4 : 8;
+        C.npass = (int)((C.idx.size() + C.G - 1) / C.G);
+        const size_t slots = (size_t)C.npass * C.G;
+        std::vector<int> tab(3 * slots);
+        for (size_t s = 0; s < slots; s++) {
+            const bool real = s < C.idx.size();
+            tab[s] = real ? pm[C.idx[s]] : 1;
+            tab[slots + s] = real ? k[C.idx[s]] : -1;
+            tab[2 * slots + s] = real ? (int)C.idx[s] : -1;
+        }
+        if (C.w64) {
+            std::vector<uint64_t> w(slots * 16, 0);
+            for (size_t s = 0; s < C.idx.size(); s++)
+                for (int c = 0; c < 16; c++) w[((s / C.G) * 16 + c) * C.G + s % C.G] = peq[(size_t)C.idx[s] * 16 + c];
+            C.peq_at = blob_add(blob, w);
+        } else {
+            std::vector<uint32_t> w(slots * 16, 0);
+            for (size_t s = 0; s < C.idx.size(); s++)
+                for (int c = 0; c < 16; c++) w[((s / C.G) * 16 + c) * C.G + s % C.G] = (uint32_t)peq[(size_t)C.idx[s] * 16 + c];
+            C.peq_at = blob_add(blob, w);
+        }
+        C.tab_at = blob_add(blob, tab);
+    }
+    auto &W = g_inner;
+    HIP_TRY(W.tables.upload(blob));
+    if (budget == 0) budget = INNER_DEFAULT_BUDGET;
+    auto pieces_of = [&](uint32_t n) -> uint64_t {
+        return (uint64_t)n > 2 * (uint64_t)margin ? ((uint64_t)n - 2 * (uint64_t)margin + PL - 1) / PL : 0;
+    };
+    const uint64_t out_per_read = (uint64_t)Q * (1 + 5 * (uint64_t)H);
+    KernelTimer timer;
+    std::vector<uint64_t> roff;
+    std::vector<uint32_t> ustart, unit_read;
+    std::vector<unsigned char> stage, out;
+    // chunks of whole reads: everything one launch group keeps on the device fits the budget (one read always goes)
+    for (uint32_t r0 = 0; r0 < n_reads;) {
+        uint64_t bytes = 64, units = 0, nb = 0;
+        uint32_t r1 = r0;
+        while (r1 < n_reads) {
+            if (len[r1] > (uint32_t)INT32_MAX) return fail(SMX_ERR_ARG, "read %u: longer than 2^31 - 1 bases", r1);
+            const uint64_t np = pieces_of(len[r1]);
+            const uint64_t cost = (uint64_t)len[r1] + 12 + np * (4 + (uint64_t)Q * RW * 4) + out_per_read;
+            if (r1 > r0 && (bytes + cost > budget || units + np > 0x7fffffffull)) break;
+            bytes += cost;
+            units += np;
+            nb += len[r1];
+            r1++;
+        }
+        if (units > 0xffffffffull) return fail(SMX_ERR_UNSUPPORTED, "read %u: too many pieces for one launch", r0);
+        const uint32_t nr = r1 - r0;
+        roff.resize((size_t)nr + 1);
+        ustart.resize((size_t)nr + 1);
+        unit_read.resize((size_t)units);
+        roff[0] = 0;
+        ustart[0] = 0;
+        for (uint32_t i = 0; i < nr; i++) {
+            const uint32_t np = (uint32_t)pieces_of(len[r0 + i]);
+            roff[i + 1] = roff[i] + len[r0 + i];
+            for (uint32_t p = 0; p < np; p++) unit_read[(size_t)ustart[i] + p] = i;
+            ustart[i + 1] = ustart[i] + np;
+        }
+        const unsigned char *src;
+        if (flat) {
+            src = (const unsigned char *)seq[r0];
+        } else {
+            stage.resize((size_t)nb);
+            for (uint32_t i = 0; i < nr; i++)
+                if (len[r0 + i]) memcpy(stage.data() + roff[i], seq[r0 + i], len[r0 + i]);
+            src = stage.data();
+        }
+        const size_t he_bytes = (size_t)nr * Q * H * 4, hd_bytes = (size_t)nr * Q * H, nh_bytes = (size_t)nr * Q;
+        HIP_TRY(W.bases.upload(src, (size_t)nb, 32));
+        HIP_TRY(W.roff.upload(roff));
+        HIP_TRY(W.ustart.upload(ustart));
+        HIP_TRY(W.unit_read.upload(unit_read));
+        HIP_TRY(W.recs.ensure((size_t)units * Q * RW * 4));
+        HIP_TRY(W.out.ensure(he_bytes + hd_bytes + nh_bytes));
+        smx::InnerArgs A{};
+        A.lut = W.tables.as<unsigned char>();
+        A.bases = W.bases.as<smx::mine_u4>();
+        A.roff = W.roff.as<uint64_t>();
+        A.ustart = W.ustart.as<uint32_t>();
+        A.unit_read = W.unit_read.as<uint32_t>();
+        A.n_units = (uint32_t)units;
+        A.Q = (int)Q;
+        A.H = (int)H;
+        A.margin = margin;
+        A.PL = PL;
+        A.lead = lead;
+        A.recs = W.recs.as<uint32_t>();
+        int32_t *d_he = W.out.as<int32_t>();
+        int8_t *d_hd = W.out.as<int8_t>() + he_bytes;
+        uint8_t *d_nh = W.out.as<uint8_t>() + he_bytes + hd_bytes;
+        if (kernel_ms) HIP_TRY(timer.start());
+        int e = 0;
+        for (const InnerClass &C : cls) {
+            if (C.idx.empty() || units == 0 || e != 0) continue;
+            const size_t slots = (size_t)C.npass * C.G;
+            A.peq = W.tables.as<char>() + C.peq_at;
+            A.pm = (const int *)(W.tables.as<char>() + C.tab_at);
+            A.pk = A.pm + slots;
+            A.jmap = A.pm + 2 * slots;
+            e = smx_launch_inner_scan(nullptr, C.w64, C.G, C.npass, &A);
+        }
+        if (e == 0) e = smx_launch_inner_merge(nullptr, &A, nr, d_nh, d_hd, d_he);
+        if (e != 0) return fail(SMX_ERR_DEVICE, "inner scan launch failed: %s", hipGetErrorString((hipError_t)e));
+        if (kernel_ms) {
+            float ms = 0.0f;
+            HIP_TRY(timer.stop(&ms));
+            *kernel_ms += ms;
+        }
+        HIP_TRY(hipDeviceSynchronize());
+        out.resize(he_bytes + hd_bytes + nh_bytes);
+        HIP_TRY(hipMemcpy(out.data(), W.out.p, out.size(), hipMemcpyDeviceToHost));
+        memcpy(hit_end + (size_t)r0 * Q * H, out.data(), he_bytes);
+        memcpy(hit_dist + (size_t)r0 * Q * H, out.data() + he_bytes, hd_bytes);
+        memcpy(nhit + (size_t)r0 * Q, out.data() + he_bytes + hd_bytes, nh_bytes);
+        r0 = r1;
+    }
+    return SMX_OK;
+}
+}  // namespace
+
+int smx_inner_scan(const char *patterns, const uint32_t *poff, uint32_t n_patterns, const int32_t *k, const uint8_t *bases,
+                   const uint64_t *off, uint32_t n_reads, int32_t margin, uint32_t max_hits, uint64_t budget_bytes,
+                   uint8_t *nhit, int8_t *hit_dist, int32_t *hit_end, float *kernel_ms) {
+    if (n_reads && (!bases || !off)) return fail(SMX_ERR_ARG, "null argument");
+    std::vector<const char *> seq(n_reads);
+    std::vector<uint32_t> len(n_reads);
+    for (uint32_t i = 0; i < n_reads; i++) {
+        if (off[i + 1] < off[i] || off[i + 1] - off[i] > (uint64_t)INT32_MAX) return fail(SMX_ERR_ARG, "read %u: bad offsets", i);
+        seq[i] = (const char *)bases + off[i];
+        len[i] = (uint32_t)(off[i + 1] - off[i]);
+    }
+    return inner_call(patterns, poff, n_patterns, k, seq.data(), len.data(), bases, n_reads, margin, max_hits, budget_bytes,
+                      nhit, hit_dist, hit_end, kernel_ms);
+}
+
+int smx_inner_scan_batch(const smx_batch *batch, const char *patterns, const uint32_t *poff, uint32_t n_patterns,
+                         const int32_t *k, int32_t margin, uint32_t max_hits, uint64_t budget_bytes, uint8_t *nhit,
+                         int8_t *hit_dist, int32_t *hit_end, float *kernel_ms) {
+    if (!batch) return fail(SMX_ERR_ARG, "null argument");
+    const uint32_t n_reads = smx_batch_size(batch);
+    std::vector<const char *> seq(n_reads);
+    std::vector<uint32_t> len(n_reads);
+    SMX_TRY(smx_batch_seq_view(batch, seq.data(), len.data()));
+    return inner_call(patterns, poff, n_patterns, k, seq.data(), len.data(), nullptr, n_reads, margin, max_hits, budget_bytes,
+                      nhit, hit_dist, hit_end, kernel_ms);
+}

@@ -1,4 +1,4 @@
-// smx_internal.h -- device-side view of the panel, shared by smx_kernels.hip and smx_api.cpp.
+// smx_internal.h -- device-side view of the panel, shared by the .hip files and the host files (smx_host.h).
 #ifndef SMX_INTERNAL_H
 #define SMX_INTERNAL_H
 #include <stddef.h>
@@ -14,7 +14,7 @@
 namespace smx {
 
 // Text alphabet of the kernels: 16 codes.  Code 15 ("other") never matches any pattern character.
-// Order matters only for the LUTs built in smx_api.cpp.
+// Order matters only for the LUTs built in smx_panel.cpp.
 static const char kCodeChars[16] = {'A', 'C', 'G', 'T', 'N', 'R', 'Y', 'K', 'M', 'S', 'W', 'B', 'D', 'H', 'V', 0};
 
 // One specimen as the scorer needs it, 32 bytes: two of these tables -- per (b1, b2) barcode pair the FIRST specimen in
@@ -24,7 +24,7 @@ struct SpecRec {
     int spec, next, pool, pad;     // specimen index, next specimen with the same barcode pair (-1: none), its pool
 };
 
-// All pointers are DEVICE pointers (one allocation, see smx_api.cpp).  Passed to kernels by value.
+// All pointers are DEVICE pointers (one allocation, see smx_panel.cpp).  Passed to kernels by value.
 struct DevPanel {
     int NP, NB, NS, NPAIR;
     int n_pbc;        // total length of the per-primer barcode lists

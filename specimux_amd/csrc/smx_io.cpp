@@ -1050,7 +1050,7 @@ int smx_batch_write_split(const smx_batch *b, const uint8_t *flags, const char *
     return SMX_OK;
 }
 
-// internal (smx_api.cpp, smx_inner_scan_batch): where every record's sequence lies, in batch order; the pointers are
+// internal (smx_calls.cpp, smx_inner_scan_batch): where every record's sequence lies, in batch order; the pointers are
 // valid as long as smx_batch_record's are
 extern "C" int smx_batch_seq_view(const smx_batch *b, const char **seq, uint32_t *len) {
     if (!b || (b->n && (!seq || !len))) return smx_set_error(SMX_ERR_ARG, "null argument");

@@ -2101,7 +2101,7 @@ __global__ __launch_bounds__(64) void align_batch_kernel(const unsigned long lon
 }  // namespace smx
 
 // ------------------------------------------------------------------------------------------------
-// launch glue used by smx_api.cpp
+// launch glue used by smx_panel.cpp and smx_calls.cpp
 // The kernel's instantiations, 20 of them at half a minute of compile time each, one row per (part, primer word bits,
 // barcode scan variant BSV, dense / compact / redo mode CM, default-flags specialisation SP).  This file is compiled three
 // times (-DSMX_PART=1 / 2 / 3, in parallel); each part instantiates the rows that name it, part 1 also holds the alignment

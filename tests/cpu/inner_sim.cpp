@@ -1,5 +1,5 @@
 // CPU simulation of the inner scan's per-lane code (specimux_amd/csrc/smx_inner_core.h): the same host/device
-// inner_scan_piece and inner_merge the gfx950 kernels of smx_inner.hip run, over tables built the way smx_api.cpp's
+// inner_scan_piece and inner_merge the gfx950 kernels of smx_inner.hip run, over tables built the way smx_calls.cpp's
 // inner_call builds them (byte -> code map, match words [pass][code][G], 32-bit words for patterns up to 32 letters and
 // 64-bit words above), checked against a plain last-row DP and the definition of a hit applied to the whole read.
 // Built and run by tests/test_inner_cpu.py (g++, no GPU).

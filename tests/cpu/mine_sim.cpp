@@ -65,7 +65,7 @@ struct Query {
     }
 };
 
-// the register class smx_api.cpp's mine_call picks: words of per-lane state, 0 = generic (global scratch)
+// the register class smx_calls.cpp's mine_call picks: words of per-lane state, 0 = generic (global scratch)
 static int reg_class(int W) { return W <= 1 ? 1 : W <= 2 ? 2 : W <= 4 ? 4 : W <= 8 ? 8 : W <= 16 ? 16 : 0; }
 
 struct Sim {

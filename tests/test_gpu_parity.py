@@ -1090,3 +1090,45 @@ def test_batches_in_flight_on_two_streams(lib, c2, c3):
                     assert np.array_equal(counts, 2 * alone[k][2]), (name, rep, k)   # (two launches per batch and round)
         finally:
             cp.set_streams(1)
+
+
+def test_lane_fetches_extra_records_beyond_the_prefix(lib, c3):
+    """A lane ships a fixed prefix of the extra records with the batch (max(4096, n // 64) of them) and smx_lane_wait fetches
+    the rest.  One batch with more extra records than the prefix, but no more than the lane's buffer of n holds: primary
+    records, extra records and counts equal those of the host-buffer path over the same windows."""
+    from specimux_amd import synth
+    from specimux_amd.demultiplex import compiled_panel
+    from specimux_amd.native_io import Lane
+    pan, (pf, sf) = c3
+    both = Both(pf, sf, dereplicate="none", index_edit_distance=4, disable_prefilter=True)   # many multi-record reads
+    cp = compiled_panel(both.specimens, both.parameters, both.args, both.prefilter)
+    rs = synth.make_reads(pan, 4096, 4242, insert_mean=900, insert_sd=250)
+    w0, l0 = rs.windows(cp.window_stride), rs.lens
+    per = np.bincount(cp.run(w0, l0)[1]["read"], minlength=len(l0))   # extra records of each read, whatever batch it is in
+    # every generated read once, then the reads with extra records over and over until the batch's extra records pass the
+    # prefix of 4096 by a margin, then reads without any until there is a read for every extra record (a lane's extra
+    # buffer holds one record per read)
+    multi = np.flatnonzero(per > 0)
+    assert len(multi) > 0
+    pick = np.concatenate([np.arange(len(l0)), np.tile(multi, 5000 // int(per.sum()) + 1)])
+    short = int(per[pick].sum()) - len(pick)
+    if short > 0:
+        pick = np.concatenate([pick, np.resize(np.flatnonzero(per == 0), short)])
+    w, l = np.ascontiguousarray(w0[pick]), np.ascontiguousarray(l0[pick])
+    n = len(l)
+    ops, extra, counts = cp.run(w, l)
+    print(f"lane extra records: {n} reads ({len(l0)} generated, {int((per > 0).sum())} of them with extra records), {len(extra)} extra records")
+    assert n <= 65536 and max(4096, n // 64) < len(extra) <= n, (n, len(extra))
+    order = ["read", "sample", "trim_start", "p1", "p2", "barcode", "rtype"]
+    lane = Lane(cp, n)
+    try:
+        lane.windows[:n] = w
+        lane.lens[:n] = l
+        lane.submit(n)
+        lane_counts = np.zeros(cp.counts_len, dtype=np.uint64)
+        lane_ops, lane_extra = lane.wait(lane_counts)
+        assert np.array_equal(lane_ops, ops)
+        assert np.array_equal(np.sort(lane_extra, order=order), np.sort(extra, order=order))
+        assert np.array_equal(lane_counts, counts)
+    finally:
+        lane.close()

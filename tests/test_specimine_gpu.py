@@ -214,7 +214,7 @@ def test_generic_class_grid_stride():
     runs: each one rebuilds its LDS Peq for queries of other lengths and reuses its scratch slice."""
     rng = random.Random(22)
     long_q = rand_seq(rng, 130972)
-    # smx_api.cpp, mine_call: cap = 256 MiB / slice, slice = 3 * W_max * MINE_THREADS * 8 bytes;
+    # smx_calls.cpp, mine_call: cap = 256 MiB / slice, slice = 3 * W_max * MINE_THREADS * 8 bytes;
     # per_block = max(MINE_BLOCK_CHUNKS, ceil(chunks / cap)), one chunk per query here (1-3 targets each)
     w_max = (len(long_q) + 63) // 64
     cap = (256 << 20) // (3 * w_max * 128 * 8)
@@ -249,7 +249,7 @@ def test_generic_class_grid_stride():
 
 
 def lds_table_bytes(m, rows):
-    """LDS bytes of a query's Peq table (smx_api.cpp, mine_call): MINE_LDS_HEAD words + (rows + 1) x (W | 1) words."""
+    """LDS bytes of a query's Peq table (smx_calls.cpp, mine_call): MINE_LDS_HEAD words + (rows + 1) x (W | 1) words."""
     return (192 + (rows + 1) * (((m + 63) // 64) | 1)) * 8
 
 
