@@ -39,14 +39,14 @@
 extern "C" {
 #endif
 
-#define SMX_ABI_VERSION 7
+#define SMX_ABI_VERSION 8
 
 typedef enum {
     SMX_OK = 0,
     SMX_ERR_ARG = -1,      /* bad argument / inconsistent descriptor */
     SMX_ERR_UNSUPPORTED = -2, /* panel outside the kernel's limits (pattern > 64 nt, ...) */
     SMX_ERR_DEVICE = -3,   /* HIP error or no device */
-    SMX_ERR_OVERFLOW = -4  /* the extra-record buffer was too small (retry with the reported size), or one read produced more than 65535 write operations (n_ops is 16 bits), or the statistics table filled up (smx_stats_read) */
+    SMX_ERR_OVERFLOW = -4  /* the extra-record buffer was too small (retry with the reported size), or one read produced more than 65535 write operations (n_ops is 16 bits), or the statistics table filled up (smx_stats_read, smx_flank_read) */
 } smx_status;
 
 /* trim modes (constants.py:40-45) and dereplication strategies (:48-51) */
@@ -470,6 +470,72 @@ int smx_inner_scan(const char *patterns, const uint32_t *poff, uint32_t n_patter
 int smx_inner_scan_batch(const smx_batch *batch, const char *patterns, const uint32_t *poff, uint32_t n_patterns,
                          const int32_t *k, int32_t margin, uint32_t max_hits, uint64_t budget_bytes, uint8_t *nhit,
                          int8_t *hit_dist, int32_t *hit_end, float *kernel_ms);
+
+/*
+ * Barcode survey (specimux-barcodes): which sequences sit on the reads where a barcode should be, next to a primer that was
+ * recognised -- counted on the device from what smx_batch_run_device was given and left there (the ASCII windows, the
+ * lengths, the hit dump), then explained by candidate barcodes.  With S = search_len, Lb = barcode_len_max, k = k_index and
+ * W = Lb + k; smx_flank_create refuses (SMX_ERR_UNSUPPORTED) W > SMX_FLANK_MAX_W and panels whose barcodes are not all
+ * Lb long.
+ *
+ * Flank of a hit h = hits[i][2 * p + e] with h.pdist >= 0 (end e: 0 = A, 1 = B, as in smx_hit).  The end string's stored
+ * window is the tail window for B and the reverse complement of the head window for A (window position j = complement of
+ * head[S - 1 - j]); only reads with lens[i] >= S are taken, and for them reference coordinate c is window position
+ * c - (lens[i] - S).  The flank is the flen = min(W, S - 1 - j_end) bases behind j_end = h.first_end - (lens[i] - S): the
+ * prefix of the string the demultiplexer searches for barcode_rc (SHW from first_end + 1).  It lies inside the window,
+ * because the window ends where the string ends.
+ *
+ * Every hit goes to exactly one counter of its primer, counters[p * SMX_FLANK_N_COUNTERS + ...] (uint64), tested in this order:
+ *   SMX_FLANK_PRUNED       h.bbest == -2 (the barcode search was not run: orientation pruned, or a length-filtered read)
+ *   SMX_FLANK_SHORT_READ   lens[i] < S
+ *   SMX_FLANK_SHORT_FLANK  flen < Lb - k: no barcode can be within k of it
+ *   SMX_FLANK_AMBIGUOUS    a flank byte other than upper-case A, C, G, T
+ *   SMX_FLANK_COUNTED      everything else: the hit's key is counted in the table
+ *   SMX_FLANK_HITS         (slot 0) the sum of the five
+ *
+ * Key of a counted hit (bit 0 = least significant; ~0 = empty slot, which no key equals because flen <= 26):
+ *   [0, 52)   the flank, 2 bits per base, A C G T = 0 1 2 3, base t at bits [2 t, 2 t + 2), unused bits 0
+ *   [52, 57)  flen
+ *   57        matched: h.bbest >= 0, a panel barcode was found at this end
+ *   [58, 64)  primer index p (a panel has at most 64 primers: the specimen masks are 64-bit)
+ * Ends A and B of a primer share keys: the end string is orientation-normalised, so a read and its reverse complement give
+ * the same keys.
+ *
+ *   smx_flank_create            capacity = number of slots, rounded up to a power of two (>= 8)
+ *   smx_flank_accumulate_device asynchronous, ordered on `stream` behind the batch: d_windows / d_lens are what
+ *                               smx_batch_run_device was given, d_hits what it dumped (all DEVICE pointers)
+ *   smx_flank_read              waits for the device, then copies the occupied slots out (any order) and the counters
+ *                               (n_primers * SMX_FLANK_N_COUNTERS uint64, may be NULL).  *n = number of distinct keys;
+ *                               SMX_ERR_ARG when cap < *n.  If any increment found the table full, the call fails with
+ *                               SMX_ERR_OVERFLOW, *dropped = the lost increments, and nothing is copied.
+ *   smx_flank_clear             empty table and counters (asynchronous on `stream`)
+ *
+ * smx_flank_assign: stand-alone (host buffers in and out, no panel handle).  A candidate is a string of 1..26 IUPAC letters
+ * as it would stand in the end string (barcode_rc) with the primer it belongs to: cands / cand_off (n_cands + 1 offsets) /
+ * cand_primer.  d(c, key) = min over 0 <= j <= flen of NW(c, flank[:j]) -- edlib's SHW distance, IUPAC equalities as in
+ * the demux kernels.  Per key, over the candidates of the key's primer only: best[i] = the least d that is <= k, else -1;
+ * first[i] = index (caller's order) of the first candidate that attains it, else -1; ntied[i] = how many attain it.  Keys
+ * may come in any order; grouped by primer (sorted, say) a wavefront walks one candidate list.  kernel_ms (may be NULL)
+ * receives the device time of the kernel (HIP events).
+ */
+enum { SMX_FLANK_HITS = 0, SMX_FLANK_PRUNED = 1, SMX_FLANK_SHORT_READ = 2, SMX_FLANK_SHORT_FLANK = 3,
+       SMX_FLANK_AMBIGUOUS = 4, SMX_FLANK_COUNTED = 5, SMX_FLANK_N_COUNTERS = 6 };
+#define SMX_FLANK_MAX_W 26
+#define SMX_FLANK_LEN_SHIFT 52
+#define SMX_FLANK_MATCHED_SHIFT 57
+#define SMX_FLANK_PRIMER_SHIFT 58
+
+typedef struct smx_flank smx_flank;
+int smx_flank_create(const smx_panel *panel, uint32_t capacity, smx_flank **out);
+void smx_flank_destroy(smx_flank *flank);
+int smx_flank_clear(smx_flank *flank, void *stream);
+int smx_flank_accumulate_device(smx_flank *flank, void *stream, const uint8_t *d_windows, const int32_t *d_lens,
+                                const smx_hit *d_hits, uint32_t n_reads);
+int smx_flank_read(smx_flank *flank, uint64_t *keys, uint64_t *counts, uint32_t cap, uint32_t *n, uint64_t *counters,
+                   uint64_t *dropped);
+int smx_flank_assign(const uint64_t *keys, uint32_t n_keys, const char *cands, const uint32_t *cand_off,
+                     const uint8_t *cand_primer, uint32_t n_cands, int32_t k, int32_t *best, int32_t *first, int32_t *ntied,
+                     float *kernel_ms);
 
 /* ---- run setup helper (host only)
  * Minimum global edit distance (exact character equality) over all pairs of the n strings seqs[off[i]..off[i+1]):

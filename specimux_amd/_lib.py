@@ -9,7 +9,7 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SMX_LIB") or os.path.join(_HERE, "libsmx.so")   # SMX_LIB: A/B builds (tools/tune.sh)
 
-ABI_VERSION = 7
+ABI_VERSION = 8
 OK, ERR_ARG, ERR_UNSUPPORTED, ERR_DEVICE, ERR_OVERFLOW = 0, -1, -2, -3, -4
 TRIM = {"none": 0, "tails": 1, "barcodes": 2, "primers": 3}
 DEREP = {"none": 0, "best": 1}
@@ -90,6 +90,13 @@ SYMBOLS = [
     ("smx_stats_clear", C.c_int, [_P, _P]),
     ("smx_lane_attach_stats", C.c_int, [_P, _P]),
     ("smx_lane_fallback", C.c_int, [_P, C.POINTER(_P), C.POINTER(C.c_uint32)]),
+    ("smx_flank_create", C.c_int, [_P, C.c_uint32, C.POINTER(_P)]),
+    ("smx_flank_destroy", None, [_P]),
+    ("smx_flank_clear", C.c_int, [_P, _P]),
+    ("smx_flank_accumulate_device", C.c_int, [_P, _P, _P, _P, _P, C.c_uint32]),
+    ("smx_flank_read", C.c_int, [_P, _P, _P, C.c_uint32, C.POINTER(C.c_uint32), _P, C.POINTER(C.c_uint64)]),
+    ("smx_flank_assign", C.c_int, [_P, C.c_uint32, C.c_char_p, _P, _P, C.c_uint32, C.c_int32, _P, _P, _P,
+                                   C.POINTER(C.c_float)]),
     ("smx_comm_unique_id", C.c_int, [_P]),
     ("smx_comm_init", C.c_int, [_P, C.c_int, C.c_int, C.POINTER(_P)]),
     ("smx_counts_allreduce", C.c_int, [_P, C.c_size_t, _P, _P]),

@@ -164,5 +164,12 @@ def chimera_main(argv=None):
     return chimera.main(argv)
 
 
+def barcodes_main(argv=None):
+    """Entry point of the barcode survey (not in the reference: specimux_amd/barcodes.py, `specimux-barcodes`); also
+    `python -m specimux_amd.barcodes`.  argv without the program name; returns the exit status."""
+    from . import barcodes
+    return barcodes.main(argv)
+
+
 if __name__ == "__main__":
     main()

@@ -128,6 +128,12 @@ class Specimens:
         return [sid for sid, _pool, b1, p1s, b2, p2s in self._specimens
                 if p1_matched in p1s and p2_matched in p2s and b1.upper() in b1_list and b2.upper() in b2_list]
 
+    def specimens_using_barcode(self, barcode: str, primer: PrimerInfo) -> List[str]:
+        """Ids of the specimens that list `barcode` as the index of `primer` (on the primer's own side of the sheet)."""
+        fwd = primer.direction == Primer.FWD
+        return [sid for sid, _pool, b1, p1s, b2, p2s in self._specimens
+                if (b1 if fwd else b2).upper() == barcode.upper() and any(info is primer for info in (p1s if fwd else p2s))]
+
     def specimen_for_exact_match(self, b1: str, b2: str, p1: PrimerInfo, p2: PrimerInfo) -> Optional[str]:
         hits = self.specimens_for_barcodes_and_primers([b1.upper()], [b2.upper()], p1, p2)
         return hits[0] if hits else None

@@ -546,13 +546,15 @@ class _Slot:
         self.batch, self.n = None, 0
 
 
-def accumulate_batches(panel, stats, batches, replay=None, table=None, n_slots=2, extra_cap=None, max_reads=None):
-    """Run window batches -- an iterable of (windows uint8 [n, stride], lens int32 [n], sequences by index or None) -- through
-    the demux kernel with the lean hit dump and the statistics kernel, everything resident on the device, `n_slots`
-    batches in flight on as many streams.  max_reads: the largest batch (None: `batches` is a list and is measured).
-    Only the two counters and the fallback indices of a batch come back; an extra-record buffer that overflows is no
-    reason to rerun a batch, counting needs the primary records only.  Rows of host-replayed reads go to `table`.
-    Returns the device counts vector (numpy uint64)."""
+def stream_batches(panel, batches, enqueue, retired=None, n_slots=2, extra_cap=None, max_reads=None, fallback_cap=0):
+    """Run window batches -- an iterable of (windows uint8 [n, stride], lens int32 [n], anything) -- through the demux kernel
+    with the lean hit dump, everything resident on the device, `n_slots` batches in flight on as many streams.
+    enqueue(slot, stream pointer, n) is called inside the slot's stream right behind the demux launch, for the kernel that
+    consumes what the launch left in the slot (its windows, lengths, records and hits); retired(slot) when the slot's
+    batch is complete and slot.h_small holds its counters.  max_reads: the largest batch (None: `batches` is a list and is
+    measured); fallback_cap: int32 words behind the two counters of slot.d_small (None: one per read).  Only the small
+    counters of a batch come back; an extra-record buffer that overflows is no reason to rerun a batch, counting needs
+    the primary records only.  Returns the device counts vector (numpy uint64)."""
     import numpy as np
     import torch
     from . import _lib
@@ -560,8 +562,8 @@ def accumulate_batches(panel, stats, batches, replay=None, table=None, n_slots=2
     if max_reads is None:
         batches = list(batches)
         max_reads = max([len(b[1]) for b in batches] + [1])
-    slots = [_Slot(torch, panel, max_reads, extra_cap if extra_cap is not None else max(64, max_reads // 4), max_reads)
-             for _ in range(max(1, n_slots))]
+    slots = [_Slot(torch, panel, max_reads, extra_cap if extra_cap is not None else max(64, max_reads // 4),
+                   max_reads if fallback_cap is None else fallback_cap) for _ in range(max(1, n_slots))]
     d_counts = torch.zeros(panel.counts_len, dtype=torch.int64, device=slots[0].d_ops.device)
     torch.cuda.synchronize()
     panel.set_streams(len(slots))
@@ -570,18 +572,13 @@ def accumulate_batches(panel, stats, batches, replay=None, table=None, n_slots=2
         if s.batch is None:
             return
         s.stream.synchronize()
-        n_fb = int(s.h_small[1])
-        if n_fb:
-            if replay is None or table is None:
-                raise RuntimeError(f"{n_fb} read(s) need the host replay (trim-to-empty primary record) and no replayer was given")
-            idx = np.sort(s.h_small[2:2 + n_fb].numpy().astype(np.int64))
-            windows, lens, seqs = s.batch
-            seqs = [seqs[i] for i in idx] if seqs is not None else ["N" * int(lens[i]) for i in idx]
-            replay.add_rows(table, windows[idx], lens[idx], seqs)
+        if retired is not None:
+            retired(s)
         s.batch = None
 
     try:
-        for bi, (windows, lens, seqs) in enumerate(batches):
+        for bi, batch in enumerate(batches):
+            windows, lens = batch[0], batch[1]
             s = slots[bi % len(slots)]
             retire(s)
             n = len(lens)
@@ -596,16 +593,39 @@ def accumulate_batches(panel, stats, batches, replay=None, table=None, n_slots=2
                 _lib.check(lib.smx_batch_run_device(panel.handle, sp, s.d_windows.data_ptr(), s.d_lens.data_ptr(), n,
                                                     s.d_ops.data_ptr(), s.d_extra.data_ptr(), s.extra_cap,
                                                     s.d_small.data_ptr(), d_counts.data_ptr(), s.d_hits.data_ptr(), None))
-                stats.accumulate(sp, s.d_hits.data_ptr(), s.d_ops.data_ptr(), n, s.d_small.data_ptr() + 8, s.fallback_cap,
-                                 s.d_small.data_ptr() + 4)
+                enqueue(s, sp, n)
                 s.h_small.copy_(s.d_small, non_blocking=True)
-            s.batch = (windows, lens, seqs)
+            s.batch = batch
         for s in slots:
             retire(s)
         torch.cuda.synchronize()
     finally:
         panel.set_streams(1)
     return d_counts.cpu().numpy().astype(np.uint64)
+
+
+def accumulate_batches(panel, stats, batches, replay=None, table=None, n_slots=2, extra_cap=None, max_reads=None):
+    """stream_batches with the statistics kernel behind every demux launch: batches of (windows, lens, sequences by index
+    or None).  Only the two counters and the fallback indices of a batch come back.  Rows of host-replayed reads go to
+    `table`.  Returns the device counts vector (numpy uint64)."""
+    import numpy as np
+
+    def enqueue(s, sp, n):
+        stats.accumulate(sp, s.d_hits.data_ptr(), s.d_ops.data_ptr(), n, s.d_small.data_ptr() + 8, s.fallback_cap,
+                         s.d_small.data_ptr() + 4)
+
+    def retired(s):
+        n_fb = int(s.h_small[1])
+        if n_fb:
+            if replay is None or table is None:
+                raise RuntimeError(f"{n_fb} read(s) need the host replay (trim-to-empty primary record) and no replayer was given")
+            idx = np.sort(s.h_small[2:2 + n_fb].numpy().astype(np.int64))
+            windows, lens, seqs = s.batch
+            seqs = [seqs[i] for i in idx] if seqs is not None else ["N" * int(lens[i]) for i in idx]
+            replay.add_rows(table, windows[idx], lens[idx], seqs)
+
+    return stream_batches(panel, batches, enqueue, retired, n_slots=n_slots, extra_cap=extra_cap, max_reads=max_reads,
+                          fallback_cap=None)
 
 
 DEFAULT_TABLE_CAPACITY = 1 << 16
@@ -616,19 +636,18 @@ _RUN_FLAGS = {"--min-length", "--max-length", "--num-seqs", "--index-edit-distan
               "--trim", "--dereplicate", "--disable-prefilter", "--disable-preorient"}
 
 
-def collect_run_table(primers, specimens, sequence_file, args, capacity=DEFAULT_TABLE_CAPACITY, batch_reads=RUN_BATCH_READS,
-                      info=None) -> StatsTable:
-    """Demultiplex `sequence_file` on the GPU for counting only and return its stats table.  `args`: a namespace with the
-    matching flags of specimux_amd.cli (-e -E -l --trim --dereplicate --disable-prefilter --disable-preorient
-    --min-length --max-length, start_seq / num_seqs).  `info` (dict) receives reads, distinct_keys, host_replayed, counts."""
+def refuse_distributed(tool):
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:
-        raise RuntimeError("specimux-stats --from-run counts in a single process; it cannot run under torch.distributed.run "
+        raise RuntimeError(f"{tool} counts in a single process; it cannot run under torch.distributed.run "
                            f"(WORLD_SIZE={os.environ['WORLD_SIZE']}): merging tables of several ranks is not implemented")
-    import time
-    t0 = time.perf_counter()
+
+
+def load_run_panel(primers, specimens, sequence_file, args):
+    """The panel of a counting run: `args` = a namespace with the matching flags of specimux_amd.cli (-e -E -l --trim
+    --dereplicate --disable-prefilter --disable-preorient --min-length --max-length, start_seq / num_seqs); what it lacks
+    takes specimux's default.  Returns (namespace, specimens, parameters, prefilter, CompiledPanel)."""
     from . import orchestration
     from .demultiplex import compiled_panel
-    from .native_io import Reader
     ns = argparse.Namespace(primer_file=primers, specimen_file=specimens, sequence_file=sequence_file, index_edit_distance=-1,
                             primer_edit_distance=-1, search_len=80, trim="barcodes", dereplicate="best", disable_prefilter=False,
                             disable_preorient=False, min_length=-1, max_length=-1, start_seq=1, num_seqs=-1, diagnostics=None)
@@ -636,32 +655,45 @@ def collect_run_table(primers, specimens, sequence_file, args, capacity=DEFAULT_
         if k in vars(ns) and k not in ("primer_file", "specimen_file", "sequence_file"):
             setattr(ns, k, v)
     specs, parameters, prefilter = orchestration._load(ns)
-    panel = compiled_panel(specs, parameters, ns, prefilter)
+    return ns, specs, parameters, prefilter, compiled_panel(specs, parameters, ns, prefilter)
+
+
+def file_batches(reader, panel, ns, batch_reads):
+    """The window batches (windows, lens, sequences by index) of the reads ns.start_seq / ns.num_seqs select from `reader`."""
+    to_skip, left = max(0, ns.start_seq - 1), (ns.num_seqs if ns.num_seqs >= 0 else None)
+    while to_skip > 0:
+        b = reader.next_batch(min(to_skip, batch_reads))
+        if b is None:
+            return
+        to_skip -= len(b)
+        b.close()
+    while left is None or left > 0:
+        b = reader.next_batch(batch_reads if left is None else min(batch_reads, left))
+        if b is None:
+            return
+        if left is not None:
+            left -= len(b)
+        windows, lens = b.pack_windows(panel.search_len, panel.window_stride)
+        yield windows, lens, _BatchSeqs(b)
+
+
+def collect_run_table(primers, specimens, sequence_file, args, capacity=DEFAULT_TABLE_CAPACITY, batch_reads=RUN_BATCH_READS,
+                      info=None) -> StatsTable:
+    """Demultiplex `sequence_file` on the GPU for counting only and return its stats table.  `args`: as for load_run_panel.
+    `info` (dict) receives reads, distinct_keys, host_replayed, counts."""
+    refuse_distributed("specimux-stats --from-run")
+    import time
+    t0 = time.perf_counter()
+    from .native_io import Reader
+    ns, specs, parameters, prefilter, panel = load_run_panel(primers, specimens, sequence_file, args)
     stats = DeviceStats(panel, capacity)
     replay = HostReplay(panel, parameters, specs, ns, prefilter is not None)
     table = StatsTable()
     reader = Reader(sequence_file)
-
-    def batches():
-        to_skip, left = max(0, ns.start_seq - 1), (ns.num_seqs if ns.num_seqs >= 0 else None)
-        while to_skip > 0:
-            b = reader.next_batch(min(to_skip, batch_reads))
-            if b is None:
-                return
-            to_skip -= len(b)
-            b.close()
-        while left is None or left > 0:
-            b = reader.next_batch(batch_reads if left is None else min(batch_reads, left))
-            if b is None:
-                return
-            if left is not None:
-                left -= len(b)
-            windows, lens = b.pack_windows(panel.search_len, panel.window_stride)
-            yield windows, lens, _BatchSeqs(b)
-
     t1 = time.perf_counter()
     try:
-        counts = accumulate_batches(panel, stats, batches(), replay, table, n_slots=3, max_reads=batch_reads)
+        counts = accumulate_batches(panel, stats, file_batches(reader, panel, ns, batch_reads), replay, table, n_slots=3,
+                                    max_reads=batch_reads)
         keys, cnts = stats.read()
     finally:
         reader.close()
