@@ -12,6 +12,8 @@
 #ifndef SMX_BARCODE_CORE_H
 #define SMX_BARCODE_CORE_H
 
+#include "smx_bitslice_core.h"
+
 #ifndef SMX_HD
 #if defined(__HIPCC__)
 #define SMX_HD __host__ __device__ __forceinline__
@@ -76,23 +78,14 @@ SMX_HD void bitsliced_shw(const unsigned *re, const unsigned char *cw, int ncol,
                 Zb = Z;   // the last executed row's Z (rhi)
             }
         }
-        unsigned inc, dec;
-        if (c + kidx <= m - 1) { inc = ~Zb; dec = 0u; }   // bottom edge still descending: +1 unless the diagonal is free
-        else { inc = Ph; dec = Mh; }                      // on the last row: horizontal delta of row m
-        {   // score += inc - dec (disjoint masks), ripple through the five planes
-            unsigned cy = inc, t;
+        if (c + kidx <= m - 1) {   // bottom edge still descending: +1 unless the diagonal is free; an increment ripple alone
+            unsigned cy = ~Zb, t;
             t = s0 & cy; s0 ^= cy; cy = t;
             t = s1 & cy; s1 ^= cy; cy = t;
             t = s2 & cy; s2 ^= cy; cy = t;
             t = s3 & cy; s3 ^= cy; cy = t;
             s4 ^= cy;
-            unsigned bw = dec;
-            t = ~s0 & bw; s0 ^= bw; bw = t;
-            t = ~s1 & bw; s1 ^= bw; bw = t;
-            t = ~s2 & bw; s2 ^= bw; bw = t;
-            t = ~s3 & bw; s3 ^= bw; bw = t;
-            s4 ^= bw;
-        }
+        } else bs_updown5(s0, s1, s2, s3, s4, Ph, Mh);   // on the last row: score += horizontal delta of row m (disjoint masks)
         if (c >= m - kidx - 1) {   // the tracked cell is on the last row from here on
             const unsigned live = c < ncol ? ~0u : 0u;
             const unsigned hi = ~(s4 | s3) & live;
@@ -154,22 +147,14 @@ SMX_HD void bitsliced_shw_pad(const unsigned *re, const unsigned char *cw, int n
             }
         }
         const bool descending = c + KB <= M - 1;
-        {
-            unsigned cy = descending ? ~Zb : Ph, t;
+        if (descending) {   // +1 unless the diagonal is free: an increment ripple alone
+            unsigned cy = ~Zb, t;
             t = s0 & cy; s0 ^= cy; cy = t;
             t = s1 & cy; s1 ^= cy; cy = t;
             t = s2 & cy; s2 ^= cy; cy = t;
             t = s3 & cy; s3 ^= cy; cy = t;
             s4 ^= cy;
-        }
-        if (!descending) {
-            unsigned bw = Mh, t;
-            t = ~s0 & bw; s0 ^= bw; bw = t;
-            t = ~s1 & bw; s1 ^= bw; bw = t;
-            t = ~s2 & bw; s2 ^= bw; bw = t;
-            t = ~s3 & bw; s3 ^= bw; bw = t;
-            s4 ^= bw;
-        }
+        } else bs_updown5(s0, s1, s2, s3, s4, Ph, Mh);   // score += Ph - Mh (disjoint masks) in one ripple
         if (c >= M - KB - 1) {   // the tracked cell sits on the last row from here on
             const unsigned live = c < nlive ? ~0u : 0u;
             const unsigned hi = ~(s4 | s3) & live;
@@ -228,22 +213,14 @@ SMX_HD void bitsliced_shw_pad_tails(const unsigned *re, const unsigned char *cw,
             }
         }
         const bool descending = c + KB <= M - 1;
-        {
-            unsigned cy = descending ? ~Zb : Ph, t;
+        if (descending) {   // +1 unless the diagonal is free: an increment ripple alone
+            unsigned cy = ~Zb, t;
             t = s0 & cy; s0 ^= cy; cy = t;
             t = s1 & cy; s1 ^= cy; cy = t;
             t = s2 & cy; s2 ^= cy; cy = t;
             t = s3 & cy; s3 ^= cy; cy = t;
             s4 ^= cy;
-        }
-        if (!descending) {
-            unsigned bw = Mh, t;
-            t = ~s0 & bw; s0 ^= bw; bw = t;
-            t = ~s1 & bw; s1 ^= bw; bw = t;
-            t = ~s2 & bw; s2 ^= bw; bw = t;
-            t = ~s3 & bw; s3 ^= bw; bw = t;
-            s4 ^= bw;
-        }
+        } else bs_updown5(s0, s1, s2, s3, s4, Ph, Mh);   // score += Ph - Mh (disjoint masks) in one ripple
         if (c >= M - KB - 1) {   // the tracked cell sits on the last row from here on
             const unsigned live = c < nlive ? ~0u : 0u;
             const unsigned hi = ~(s4 | s3) & live;

@@ -36,10 +36,14 @@
 #define SMX_PRESCAN_CORE_H
 #include <stdint.h>
 
+#include "smx_bitslice_core.h"
+
+#if !defined(SMX_HD)
 #if defined(__HIPCC__)
 #define SMX_HD __host__ __device__ __forceinline__
 #else
 #define SMX_HD inline
+#endif
 #endif
 
 namespace smx {
@@ -66,8 +70,60 @@ struct PreDesc {
     uint8_t sym[64][32];           // pattern letter of row i of primer p, as an index into its symbol table
 };
 
-// out[r] bit q = in[q] bit r
+// v_perm_b32: byte i of the result = the byte that selector byte i names: 0..3 = byte of `b`, 4..7 = byte of `a`
+SMX_HD unsigned perm_b32(unsigned a, unsigned b, unsigned sel) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_amdgcn_perm(a, b, sel);
+#else
+    unsigned r = 0;
+    for (int i = 0; i < 4; i++) {
+        const unsigned q = (sel >> (8 * i)) & 7u;
+        r |= (((q & 4u) ? a : b) >> (8 * (q & 3u)) & 0xFFu) << (8 * i);
+    }
+    return r;
+#endif
+}
+
+// v_bfi_b32: mask ? a : b, bit by bit (written out, the compiler splits it into two ands and an or)
+SMX_HD unsigned bfi_b32(unsigned mask, unsigned a, unsigned b) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    unsigned r;
+    asm("v_bfi_b32 %0, %1, %2, %3" : "=v"(r) : "s"(mask), "v"(a), "v"(b));
+    return r;
+#else
+    return (a & mask) | (b & ~mask);
+#endif
+}
+
+// out[r] bit q = in[q] bit r.  Five stages J = 16 .. 1; stage J exchanges, in every register pair (k, k + J), the bit fields
+// of width J: lo' = lo's even fields | hi's even fields << J, hi' = lo's odd fields >> J | hi's odd fields.
+// transpose32_fields: the two stages that move whole half-words and bytes are one v_perm_b32 per output, the three others
+// one shift and one v_bfi_b32 per output: 256 instructions per call.  The device runs this form; the host runs the plain
+// xor-swap form below (which compiled to ~450 instructions on the device) and the CPU test compares the two.
+template <int J>
+SMX_HD void transpose32_pair(unsigned &lo, unsigned &hi) {
+    const unsigned l = lo, h = hi;
+    if (J == 16) {
+        lo = perm_b32(h, l, 0x05040100u);
+        hi = perm_b32(h, l, 0x07060302u);
+    } else if (J == 8) {
+        lo = perm_b32(h, l, 0x06020400u);
+        hi = perm_b32(h, l, 0x07030501u);
+    } else {
+        constexpr unsigned M = J == 4 ? 0x0F0F0F0Fu : (J == 2 ? 0x33333333u : 0x55555555u);
+        lo = bfi_b32(M, l, h << J);
+        hi = bfi_b32(M, l >> J, h);
+    }
+}
+SMX_HD void transpose32_fields(unsigned (&a)[32]) {
+#define SMX_TSTAGE(J) _Pragma("unroll") for (int k_ = 0; k_ < 32; k_++) if ((k_ & J) == 0) transpose32_pair<J>(a[k_], a[k_ + J]);
+    SMX_TSTAGE(16) SMX_TSTAGE(8) SMX_TSTAGE(4) SMX_TSTAGE(2) SMX_TSTAGE(1)
+#undef SMX_TSTAGE
+}
 SMX_HD void transpose32(unsigned (&a)[32]) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    transpose32_fields(a);
+#else
 #define SMX_TSTAGE(J, MASK)                                                                    \
     _Pragma("unroll") for (int k_ = 0; k_ < 32; k_++) if ((k_ & J) == 0) {                     \
         const unsigned t_ = ((a[k_] >> J) ^ a[k_ + J]) & MASK;                                 \
@@ -80,6 +136,7 @@ SMX_HD void transpose32(unsigned (&a)[32]) {
     SMX_TSTAGE(2, 0x33333333u)
     SMX_TSTAGE(1, 0x55555555u)
 #undef SMX_TSTAGE
+#endif
 }
 
 // 16 ASCII bases (four little-endian dwords) -> 32 bits: byte i, bit pair kq <-> base 4 * kq + i; code = (ch >> 1) & 3
@@ -363,20 +420,10 @@ SMX_HD void prescan_dp(const unsigned *gpl, unsigned *scratch, int lane, int CH,
             }
             // last row: score += Ph - Mh; gap = score - running minimum
             const unsigned lt = zero & Mh;        // at the minimum and going down: a new minimum, the gap stays 0
-            unsigned cy = Ph, bw = Mh ^ lt, tt;
-            tt = g0 & cy; g0 ^= cy; cy = tt;
-            tt = g1 & cy; g1 ^= cy; cy = tt;
-            tt = g2 & cy; g2 ^= cy; cy = tt;
-            tt = g3 & cy; g3 ^= cy; cy = tt;
-            g4 ^= cy;
-            tt = ~g0 & bw; g0 ^= bw; bw = tt;
-            tt = ~g1 & bw; g1 ^= bw; bw = tt;
-            tt = ~g2 & bw; g2 ^= bw; bw = tt;
-            tt = ~g3 & bw; g3 ^= bw; bw = tt;
-            g4 ^= bw;
+            bs_updown5(g0, g1, g2, g3, g4, Ph, Mh ^ lt);   // Ph and Mh are disjoint: one ripple
             zero = ~(g0 | g1 | g2 | g3 | g4);
             if (MT) {
-                cy = lt;
+                unsigned cy = lt, tt;
                 tt = n0 & cy; n0 ^= cy; cy = tt;
                 tt = n1 & cy; n1 ^= cy; cy = tt;
                 tt = n2 & cy; n2 ^= cy; cy = tt;
