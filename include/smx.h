@@ -21,6 +21,8 @@
  *           (demultiplex.py:757-766, :612-624): the only bases the hot path ever reads.
  *   smx_mine_*        <- specimine.py's mine_sequences (the separate specimine tool, :197-257): batched long-read
  *           HW distances and the per-partial-read best identity.
+ *   smx_pairs_*       <- nothing: the reference leaves "is this specimen one organism?" to the tools after it
+ *           (DESIGN.md section 14).
  *   smx_inner_scan    <- nothing: the reference never looks between the two end windows.
  *   smx_counts_*      <- the parent summing (batch_total, batch_matched) (orchestration.py:203-207).
  *
@@ -304,6 +306,34 @@ int smx_mine_distances(const char *queries, const uint64_t *qoff, uint32_t n_que
 int smx_mine_best_identity(const char *queries, const uint64_t *qoff, uint32_t n_queries, const int32_t *k,
                            const char *targets, const uint64_t *toff, uint32_t n_targets, const smx_mine_job *jobs,
                            uint32_t n_jobs, double *best, float *kernel_ms);
+
+/*
+ * clusters: NW (global) edit distances of all pairs of reads within one specimen, in batches -- nothing in the reference
+ * does this; edlib.align(a, b, mode="NW", k) is the definition.  Exact byte equality, no IUPAC
+ * equalities.  Distance only.
+ *   reads / roff       n_reads reads (concatenated, n_reads + 1 offsets), any length (an empty read is at distance
+ *                      len(other) from any other); every read's Peq table must fit the LDS, as a specimine query's
+ *   k                  per read: its max distance (< 0: no limit).  The limit of the pair (i, j) is max(k[i], k[j]), no
+ *                      limit if either read has none: integers only, the device decides no pair in floating point
+ *   jobs               each job is the reads [r0, r0 + n) of one specimen, its pairs the i < j among them.  Jobs of 0 or
+ *                      1 reads are legal.  The ranges of two jobs may not overlap (SMX_ERR_ARG)
+ * smx_pairs_neighbours: per job its symmetric adjacency bit matrix, n rows x ceil(n / 32) uint32 words, bit j of row i
+ * (word j / 32, bit j % 32) set iff i != j and the pair's distance is within its limit; the diagonal and the bits >= n
+ * are zero.  Job j's matrix follows the matrices of the earlier jobs (n = 1: one zero word, n = 0: nothing).  The kernel
+ * writes whole words of the upper triangle (one wave ballot per 64 pairs), the library mirrors them: device and host
+ * memory are bounded by the reads and sum(n * ceil(n / 32)) words; nothing is sized by n^2 integers.
+ * smx_pairs_distances, kept for tests and inspection, writes job j's packed upper triangle, row-major over i < j (n (n - 1)
+ * / 2 int32, -1 above the limit), after the triangles of the earlier jobs.
+ * kernel_ms (may be NULL) receives the device time of the kernels (HIP events).
+ */
+typedef struct smx_pairs_job {
+    uint32_t r0, n;
+} smx_pairs_job;
+
+int smx_pairs_distances(const char *reads, const uint64_t *roff, uint32_t n_reads, const int32_t *k,
+                        const smx_pairs_job *jobs, uint32_t n_jobs, int32_t *dist, float *kernel_ms);
+int smx_pairs_neighbours(const char *reads, const uint64_t *roff, uint32_t n_reads, const int32_t *k,
+                         const smx_pairs_job *jobs, uint32_t n_jobs, uint32_t *adj, float *kernel_ms);
 
 /*
  * Match statistics (specimux-stats; reference trace_stats.py): the "pool -> primer pair -> outcome" tables counted on the

@@ -1,5 +1,5 @@
 // smx_calls.cpp -- the one-shot calls of libsmx.so over host buffers: alignments (smx_align, smx_align_batch), specimine
-// (smx_mine.hip) and the inner scan (smx_inner.hip).  Each keeps one grow-only device workspace; its calls are serialised.
+// (smx_mine.hip), clusters (smx_pairs.hip) and the inner scan (smx_inner.hip).  Each keeps one grow-only device workspace; its calls are serialised.
 #include "smx_host.h"
 
 int smx_align(const char *query, int qlen, const char *target, int tlen, int k, int mode, int *dist, int *starts,
@@ -114,13 +114,13 @@ struct {
 
 // per query: LDS bytes of its Peq table ((distinct bytes + 1) x padded words) and the register class of its per-lane state
 int mine_queries(const char *queries, const uint64_t *qoff, uint32_t n_queries, std::vector<size_t> *qlds_out,
-                 std::vector<int> *qclass_out) {
+                 std::vector<int> *qclass_out, bool allow_empty = false) {
     std::vector<size_t> &qlds = *qlds_out;
     std::vector<int> &qclass = *qclass_out;
     qlds.assign(n_queries, 0);
     qclass.assign(n_queries, 0);
     for (uint32_t q = 0; q < n_queries; q++) {
-        if (qoff[q + 1] <= qoff[q]) return fail(SMX_ERR_ARG, "query %u is empty", q);
+        if (qoff[q + 1] < qoff[q] || (qoff[q + 1] == qoff[q] && !allow_empty)) return fail(SMX_ERR_ARG, "query %u is empty", q);
         const uint64_t m = qoff[q + 1] - qoff[q];
         if (m > (uint64_t)INT32_MAX) return fail(SMX_ERR_UNSUPPORTED, "query %u: length %llu", q, (unsigned long long)m);
         bool seen[256] = {false};
@@ -276,6 +276,145 @@ int smx_mine_best_identity(const char *queries, const uint64_t *qoff, uint32_t n
                            const char *targets, const uint64_t *toff, uint32_t n_targets, const smx_mine_job *jobs,
                            uint32_t n_jobs, double *best, float *kernel_ms) {
     return mine_call(false, queries, qoff, n_queries, k, targets, toff, n_targets, jobs, n_jobs, best, kernel_ms);
+}
+
+// ---- clusters: all-pairs NW distances within each job's reads (smx_pairs.hip); the workspace is specimine's own
+// shape (padded reads, row list, chunk prefix, scratch, jobs + output), kept apart so that the two never wait for each other
+namespace {
+struct {
+    std::mutex mutex;
+    DevBuf reads, doff, len, k, rows, chunk_start;
+    DevBuf scratch;     // per-lane state of the generic class, one slice per workgroup
+    DevBuf jobs_out;    // the jobs, then the output
+} g_pairs;
+
+// One smx_pairs_* call.  distances: job j's n (n - 1) / 2 distances (int32); else its n x ceil(n / 32) adjacency words,
+// the upper triangle from the kernel, mirrored here.  Either way job j's output follows the earlier jobs'.
+int pairs_call(bool distances, const char *reads, const uint64_t *roff, uint32_t n_reads, const int32_t *k,
+               const smx_pairs_job *jobs, uint32_t n_jobs, uint32_t *out, float *kernel_ms) {
+    if (!reads || !roff || !k || (n_jobs && (!jobs || !out))) return fail(SMX_ERR_ARG, "null argument");
+    std::lock_guard<std::mutex> guard(g_pairs.mutex);
+    SMX_TRY(require_device());
+    std::vector<size_t> qlds;
+    std::vector<int> qclass;
+    SMX_TRY(mine_queries(reads, roff, n_reads, &qlds, &qclass, true));
+    std::vector<uint64_t> doff;
+    std::vector<int32_t> len;
+    std::vector<unsigned char> pad;
+    SMX_TRY(mine_targets(reads, roff, n_reads, &doff, &len, &pad));
+    // the jobs' ranges may not overlap: every read is a row of at most one matrix
+    std::vector<uint32_t> order;
+    for (uint32_t j = 0; j < n_jobs; j++) {
+        if ((uint64_t)jobs[j].r0 + jobs[j].n > n_reads) return fail(SMX_ERR_ARG, "job %u: read range out of bounds", j);
+        if (jobs[j].n) order.push_back(j);
+    }
+    std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return jobs[a].r0 < jobs[b].r0; });
+    for (size_t i = 1; i < order.size(); i++)
+        if (jobs[order[i - 1]].r0 + jobs[order[i - 1]].n > jobs[order[i]].r0)
+            return fail(SMX_ERR_ARG, "jobs %u and %u overlap", order[i - 1], order[i]);
+    // jobs -> rows with at least one j > i, grouped by the register class of the row's read, in read order
+    std::vector<smx::PairsJobDev> djobs(n_jobs);
+    std::vector<smx::PairsRow> rows[6];
+    std::vector<uint64_t> chunk_start;            // per class: n + 1 prefix entries, one after the other
+    uint64_t chunks[6] = {0, 0, 0, 0, 0, 0};
+    size_t lds_max[6] = {0, 0, 0, 0, 0, 0};
+    int words_max0 = 0;
+    uint64_t n_out = 0;
+    for (uint32_t j = 0; j < n_jobs; j++) {
+        const uint64_t n = jobs[j].n;
+        djobs[j] = smx::PairsJobDev{jobs[j].r0, jobs[j].n, n_out};
+        n_out += distances ? n * (n - (n ? 1 : 0)) / 2 : n * ((n + 31) / 32);
+        for (uint32_t i = 0; i + 1 < n; i++) {
+            const uint32_t r = jobs[j].r0 + i;
+            const int c = qclass[r];
+            lds_max[c] = std::max(lds_max[c], qlds[r]);
+            if (c == 0) words_max0 = std::max(words_max0, (len[r] + 63) / 64);
+            rows[c].push_back(smx::PairsRow{j, r});
+        }
+    }
+    if (kernel_ms) *kernel_ms = 0.0f;
+    if (n_out == 0) return SMX_OK;
+    const size_t out_bytes = n_out * 4;
+    uint64_t n_rows = 0;
+    for (int c = 0; c < 6; c++) {
+        if (rows[c].empty()) continue;
+        n_rows += rows[c].size();
+        chunk_start.push_back(0);
+        for (const smx::PairsRow &R : rows[c]) {
+            const uint32_t n = djobs[R.job].n, i = R.read - djobs[R.job].r0;
+            chunks[c] += (n + MINE_THREADS - 1) / MINE_THREADS - (i + 1) / MINE_THREADS;
+            chunk_start.push_back(chunks[c]);
+        }
+    }
+    if (n_rows == 0) {                            // only jobs of one read: a zero word each
+        memset(out, 0, out_bytes);
+        return SMX_OK;
+    }
+    // runs of chunks per workgroup and the generic class's grid bound: as mine_call
+    constexpr uint64_t PAIRS_BLOCK_CHUNKS = 8;
+    const uint64_t grid_cap = (uint64_t)INT32_MAX;
+    const size_t slice = (size_t)3 * words_max0 * MINE_THREADS * 8;
+    const uint64_t grid0_cap = std::max<size_t>(1, ((size_t)256 << 20) / std::max<size_t>(slice, 1));
+    auto &W = g_pairs;
+    std::vector<smx::PairsRow> all_rows;          // class after class
+    for (int c = 0; c < 6; c++) all_rows.insert(all_rows.end(), rows[c].begin(), rows[c].end());
+    const size_t jobs_bytes = (n_jobs * sizeof(smx::PairsJobDev) + 15) & ~(size_t)15;
+    HIP_TRY(W.reads.upload(pad));
+    HIP_TRY(W.doff.upload(doff));
+    HIP_TRY(W.len.upload(len));
+    HIP_TRY(W.k.upload(k, (size_t)n_reads * 4));
+    HIP_TRY(W.rows.upload(all_rows));
+    HIP_TRY(W.chunk_start.upload(chunk_start));
+    if (!rows[0].empty()) HIP_TRY(W.scratch.ensure((size_t)std::min(chunks[0], grid0_cap) * slice));
+    HIP_TRY(W.jobs_out.upload(djobs.data(), n_jobs * sizeof(smx::PairsJobDev), jobs_bytes - n_jobs * sizeof(smx::PairsJobDev) + out_bytes));
+    void *d_out = W.jobs_out.as<char>() + jobs_bytes;
+    if (!distances) HIP_TRY(hipMemset(d_out, 0, out_bytes));
+    KernelTimer timer;
+    if (kernel_ms) HIP_TRY(timer.start());
+    static const int kWords[6] = {0, 1, 2, 4, 8, 16};
+    size_t rat = 0, cat = 0;
+    int e = 0;
+    for (int c = 0; c < 6 && e == 0; c++) {
+        const uint32_t n = (uint32_t)rows[c].size();
+        if (!n) continue;
+        const uint64_t cap = c == 0 ? std::min(grid_cap, grid0_cap) : grid_cap;
+        const uint64_t per_block = std::max(PAIRS_BLOCK_CHUNKS, (chunks[c] + cap - 1) / cap);
+        const uint64_t grid = (chunks[c] + per_block - 1) / per_block;
+        e = smx_launch_pairs(nullptr, kWords[c], distances, W.reads.as<unsigned char>(), W.doff.as<uint64_t>(),
+                             W.len.as<int32_t>(), W.k.as<int32_t>(), W.rows.as<smx::PairsRow>() + rat,
+                             W.chunk_start.as<uint64_t>() + cat, n, W.jobs_out.p, (int)grid, per_block, lds_max[c], d_out,
+                             W.scratch.as<unsigned long long>(), words_max0);
+        rat += n;
+        cat += (size_t)n + 1;
+    }
+    if (e != 0) return fail(SMX_ERR_DEVICE, "pairs kernel launch failed: %s", hipGetErrorString((hipError_t)e));
+    if (kernel_ms) HIP_TRY(timer.stop(kernel_ms));
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(out, d_out, out_bytes, hipMemcpyDeviceToHost));
+    if (!distances)                               // mirror the triangle: bit i of row j for every bit j > i of row i
+        for (const smx::PairsJobDev &J : djobs) {
+            const uint32_t nw = (J.n + 31) / 32;
+            uint32_t *adj = out + J.out_off;
+            for (uint32_t i = 0; i < J.n; i++)
+                for (uint32_t w = i / 32; w < nw; w++) {
+                    uint32_t bits = adj[(size_t)i * nw + w];
+                    if (w == i / 32) bits &= i % 32 == 31 ? 0u : ~0u << (i % 32 + 1);   // the bits right of the diagonal
+                    for (; bits; bits &= bits - 1)
+                        adj[(size_t)(w * 32 + (uint32_t)__builtin_ctz(bits)) * nw + i / 32] |= 1u << (i % 32);
+                }
+        }
+    return SMX_OK;
+}
+}  // namespace
+
+int smx_pairs_distances(const char *reads, const uint64_t *roff, uint32_t n_reads, const int32_t *k,
+                        const smx_pairs_job *jobs, uint32_t n_jobs, int32_t *dist, float *kernel_ms) {
+    return pairs_call(true, reads, roff, n_reads, k, jobs, n_jobs, reinterpret_cast<uint32_t *>(dist), kernel_ms);
+}
+
+int smx_pairs_neighbours(const char *reads, const uint64_t *roff, uint32_t n_reads, const int32_t *k,
+                         const smx_pairs_job *jobs, uint32_t n_jobs, uint32_t *adj, float *kernel_ms) {
+    return pairs_call(false, reads, roff, n_reads, k, jobs, n_jobs, adj, kernel_ms);
 }
 
 // ---- inner scan: every pattern against the whole read, hits on the internal columns (smx_inner.hip)

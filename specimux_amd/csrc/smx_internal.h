@@ -98,6 +98,17 @@ struct MinePair {     // one (job, query) pair, ceil(nt / MINE_THREADS) target c
     uint32_t pad;
 };
 
+// clusters (smx_pairs.hip): all pairs i < j of a job's reads; chunks as in specimine, aligned in j
+struct PairsJobDev {  // one smx_pairs_job with its output offset (int32 distances or uint32 adjacency words)
+    uint32_t r0, n;
+    uint64_t out_off;
+};
+
+struct PairsRow {     // row i of a job's triangle: ceil(n / MINE_THREADS) - (i + 1) / MINE_THREADS target chunks
+    uint32_t job;     // index into the PairsJobDev array
+    uint32_t read;    // the query: read r0 + i
+};
+
 // inner scan (smx_inner.hip): one chunk of whole reads and one word-width class of patterns.  Device pointers.
 struct InnerArgs {
     const void *peq;               // [pass][16 codes][G] match words, 32 or 64 bits wide
@@ -146,6 +157,14 @@ int smx_launch_mine(void *stream, int wr, int dist, const unsigned char *d_q, co
                     const uint64_t *d_toff, const int32_t *d_tlen, const void *d_pairs, const uint64_t *d_chunk_start,
                     uint32_t n_pairs, const void *d_jobs, int grid, uint64_t per_block, size_t lds_bytes, void *d_out,
                     unsigned long long *d_scratch, int scratch_words);
+// clusters (smx_pairs.hip); wr, grid, per_block, d_scratch as for smx_launch_mine.  d_bytes / d_off / d_len: the reads
+// as 16-byte aligned padded copies; d_k: the limit per read; rows[0..n_rows) with chunk_start[0..n_rows] (nonzero
+// each).  dist = 1: d_out holds int32 distances, job j's packed upper triangle at its out_off; dist = 0: d_out holds
+// the adjacency words (zeroed by the caller), the kernel writes the upper triangle of job j's n x ceil(n / 32) matrix
+int smx_launch_pairs(void *stream, int wr, int dist, const unsigned char *d_bytes, const uint64_t *d_off, const int32_t *d_len,
+                     const int32_t *d_k, const void *d_rows, const uint64_t *d_chunk_start, uint32_t n_rows,
+                     const void *d_jobs, int grid, uint64_t per_block, size_t lds_bytes, void *d_out,
+                     unsigned long long *d_scratch, int scratch_words);
 // inner scan (smx_inner.hip): the scan over A->n_units units x npass passes of G (4 or 8) patterns, w64 = 64-bit words;
 // then one merge launch over n_reads x A->Q (read, pattern) pairs once every class has left its records
 int smx_launch_inner_scan(void *stream, int w64, int G, int npass, const smx::InnerArgs *A);
