@@ -23,6 +23,8 @@
  *           HW distances and the per-partial-read best identity.
  *   smx_pairs_*       <- nothing: the reference leaves "is this specimen one organism?" to the tools after it
  *           (DESIGN.md section 14).
+ *   smx_cons_*        <- nothing: the reference hands the consensus of a specimen to an external tool (DESIGN.md
+ *           section 15).
  *   smx_inner_scan    <- nothing: the reference never looks between the two end windows.
  *   smx_counts_*      <- the parent summing (batch_total, batch_matched) (orchestration.py:203-207).
  *
@@ -334,6 +336,40 @@ int smx_pairs_distances(const char *reads, const uint64_t *roff, uint32_t n_read
                         const smx_pairs_job *jobs, uint32_t n_jobs, int32_t *dist, float *kernel_ms);
 int smx_pairs_neighbours(const char *reads, const uint64_t *roff, uint32_t n_reads, const int32_t *k,
                          const smx_pairs_job *jobs, uint32_t n_jobs, uint32_t *adj, float *kernel_ms);
+
+/*
+ * consensus: every member read of a cluster aligned globally (NW) to the cluster's draft, with traceback, and the
+ * alignments reduced to per-position votes -- nothing in the reference does this; it hands the step to an external
+ * consensus tool.  Exact byte equality, as in clusters.
+ *   reads / roff / k   as for smx_pairs_*.  The limit of a (draft, member) pair is max(k[draft], k[member]), no limit if
+ *                      either has none.  A draft's Peq table must fit the LDS, as a read's in smx_pairs_*
+ *   jobs               each job aligns the reads [r0, r0 + n) to the read `draft`, which may be one of them.  Jobs of
+ *                      n = 0 are legal.  SMX_ERR_ARG, before anything is launched: an empty draft, an index out of range,
+ *                      member ranges of two jobs that overlap
+ * The pileup row of a member over a draft of m bases is m + 1 uint32 words.  Word p < m: bits 0-2 what the member has at
+ * draft position p (0-3 = the bytes A C G T, 4 = any other byte, 5 = deletion), bits 3-10 the length of its insertion before
+ * position p, clipped to 255, bits 11-22 the codes of the first SMX_CONS_MAX_INS inserted bytes, 3 bits each, in read
+ * order.  Word m: bits 0-2 are 7, the rest is the insertion after the last base.  Of the optimal alignments the row is
+ * the one the fixed walk from the end takes: diagonal if it is optimal, else up (deletion), else left (insertion).
+ * smx_cons_pileup, kept for tests and inspection: job after job its n rows (n x (m + 1) words) and its n distances (-1
+ * above the limit, and then a row of 0xFFFFFFFF).
+ * smx_cons_votes, the production entry (the rows never leave the device): job after job its (m + 1) x
+ * SMX_CONS_VOTE_WORDS table -- per position sym[6] (A, C, G, T, other, deletion), then ins[slot][code] for slot < 4 and
+ * code < 5 (a member whose insertion before p has length L votes in slots 0 .. min(L, 4) - 1) -- over the members within
+ * their limit, and aligned[j], the number of those.  No atomics: the table is the same from run to run.  n = 0: a zero table.
+ * kernel_ms (may be NULL) receives the device time of the kernels (HIP events).
+ */
+#define SMX_CONS_MAX_INS 4
+#define SMX_CONS_VOTE_WORDS (6 + 5 * SMX_CONS_MAX_INS)
+
+typedef struct smx_cons_job {
+    uint32_t draft, r0, n;   /* draft: an index into reads; members: reads [r0, r0 + n) */
+} smx_cons_job;
+
+int smx_cons_pileup(const char *reads, const uint64_t *roff, uint32_t n_reads, const int32_t *k,
+                    const smx_cons_job *jobs, uint32_t n_jobs, uint32_t *rows, int32_t *dist, float *kernel_ms);
+int smx_cons_votes(const char *reads, const uint64_t *roff, uint32_t n_reads, const int32_t *k,
+                   const smx_cons_job *jobs, uint32_t n_jobs, uint32_t *votes, uint32_t *aligned, float *kernel_ms);
 
 /*
  * Match statistics (specimux-stats; reference trace_stats.py): the "pool -> primer pair -> outcome" tables counted on the

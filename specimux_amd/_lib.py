@@ -27,7 +27,9 @@ HIT_DTYPE = np.dtype([("first_start", "<i4"), ("first_end", "<i4"), ("tail_end",
 MINE_JOB_DTYPE = np.dtype([("q0", "<u4"), ("nq", "<u4"), ("t0", "<u4"), ("nt", "<u4"), ("min_identity", "<f8")])
 PAIRS_JOB_DTYPE = np.dtype([("r0", "<u4"), ("n", "<u4")])
 assert OP_DTYPE.itemsize == 32 and HIT_DTYPE.itemsize == 24 and MINE_JOB_DTYPE.itemsize == 24
-assert PAIRS_JOB_DTYPE.itemsize == 8
+CONS_JOB_DTYPE = np.dtype([("draft", "<u4"), ("r0", "<u4"), ("n", "<u4")])
+CONS_MAX_INS, CONS_VOTE_WORDS = 4, 26
+assert PAIRS_JOB_DTYPE.itemsize == 8 and CONS_JOB_DTYPE.itemsize == 12
 
 
 class PanelDesc(C.Structure):
@@ -83,6 +85,8 @@ SYMBOLS = [
                                          C.POINTER(C.c_float)]),
     ("smx_pairs_distances", C.c_int, [C.c_char_p, _P, C.c_uint32, _P, _P, C.c_uint32, _P, C.POINTER(C.c_float)]),
     ("smx_pairs_neighbours", C.c_int, [C.c_char_p, _P, C.c_uint32, _P, _P, C.c_uint32, _P, C.POINTER(C.c_float)]),
+    ("smx_cons_pileup", C.c_int, [C.c_char_p, _P, C.c_uint32, _P, _P, C.c_uint32, _P, _P, C.POINTER(C.c_float)]),
+    ("smx_cons_votes", C.c_int, [C.c_char_p, _P, C.c_uint32, _P, _P, C.c_uint32, _P, _P, C.POINTER(C.c_float)]),
     ("smx_inner_scan", C.c_int, [C.c_char_p, _P, C.c_uint32, _P, _P, _P, C.c_uint32, C.c_int32, C.c_uint32, C.c_uint64,
                                  _P, _P, _P, C.POINTER(C.c_float)]),
     ("smx_inner_scan_batch", C.c_int, [_P, C.c_char_p, _P, C.c_uint32, _P, C.c_int32, C.c_uint32, C.c_uint64, _P, _P, _P,

@@ -1,6 +1,7 @@
 // smx_calls.cpp -- the one-shot calls of libsmx.so over host buffers: alignments (smx_align, smx_align_batch), specimine
-// (smx_mine.hip), clusters (smx_pairs.hip) and the inner scan (smx_inner.hip).  Each keeps one grow-only device workspace; its calls are serialised.
+// (smx_mine.hip), clusters (smx_pairs.hip), consensus (smx_cons.hip) and the inner scan (smx_inner.hip).  Each keeps one grow-only device workspace; its calls are serialised.
 #include "smx_host.h"
+#include "smx_cons_plan.h"
 
 int smx_align(const char *query, int qlen, const char *target, int tlen, int k, int mode, int *dist, int *starts,
               int *ends, int cap, int *nloc) {
@@ -415,6 +416,114 @@ int smx_pairs_distances(const char *reads, const uint64_t *roff, uint32_t n_read
 int smx_pairs_neighbours(const char *reads, const uint64_t *roff, uint32_t n_reads, const int32_t *k,
                          const smx_pairs_job *jobs, uint32_t n_jobs, uint32_t *adj, float *kernel_ms) {
     return pairs_call(false, reads, roff, n_reads, k, jobs, n_jobs, adj, kernel_ms);
+}
+
+// ---- consensus: every member read of a job aligned to the job's draft with traceback, the rows reduced to votes
+// (smx_cons.hip); a workspace of its own, like g_pairs, with the history of the workgroups in flight
+namespace {
+struct {
+    std::mutex mutex;
+    DevBuf reads, doff, len, k, jobs, align, chunk_start;
+    DevBuf scratch;             // per-lane state of the generic class, one slice per workgroup
+    DevBuf hist_pm, hist_s;     // the alignment history, one slice per workgroup
+    DevBuf rows, dist, votes, aligned;
+} g_cons;
+
+// One smx_cons_* call.  rows / dist (pileup) or votes / aligned (votes) receive the result, the others are null.
+int cons_call(const char *reads, const uint64_t *roff, uint32_t n_reads, const int32_t *k, const smx_cons_job *jobs,
+              uint32_t n_jobs, uint32_t *rows, int32_t *dist, uint32_t *votes, uint32_t *aligned, float *kernel_ms) {
+    const bool pileup = rows || dist;
+    if (!reads || !roff || !k || (n_jobs && (!jobs || (pileup ? !rows || !dist : !votes || !aligned))))
+        return fail(SMX_ERR_ARG, "null argument");
+    // every check of the arguments comes before the device is touched
+    uint64_t hist_budget = smx::CONS_HIST_BYTES;
+    if (const char *env = getenv("SMX_CONS_HIST_BYTES")) hist_budget = strtoull(env, nullptr, 10);   // test hook: few workgroups in flight
+    smx::ConsPlan P;
+    std::string why;
+    const int rc = smx::cons_plan(reads, roff, n_reads, k, jobs, n_jobs, hist_budget, &P, &why);
+    if (rc != SMX_OK) return fail(rc, "%s", why.c_str());
+    if (kernel_ms) *kernel_ms = 0.0f;
+    if (n_jobs == 0) return SMX_OK;
+    std::lock_guard<std::mutex> guard(g_cons.mutex);
+    SMX_TRY(require_device());
+    std::vector<uint64_t> doff;
+    std::vector<int32_t> len;
+    std::vector<unsigned char> pad;
+    SMX_TRY(mine_targets(reads, roff, n_reads, &doff, &len, &pad));
+    auto &W = g_cons;
+    HIP_TRY(W.reads.upload(pad));
+    HIP_TRY(W.doff.upload(doff));
+    HIP_TRY(W.len.upload(len));
+    HIP_TRY(W.k.upload(k, (size_t)n_reads * 4));
+    HIP_TRY(W.jobs.upload(P.jobs));
+    HIP_TRY(W.align.upload(P.align));
+    HIP_TRY(W.chunk_start.upload(P.chunk_start));
+    HIP_TRY(W.rows.ensure((size_t)P.rows_words * 4));
+    HIP_TRY(W.dist.ensure((size_t)P.n_dist * 4));
+    // runs of chunks per workgroup only where the history bounds the grid: a chunk is 128 alignments with traceback,
+    // and a call has few of them by the standards of the device
+    uint64_t grids[6], per_block[6], grid_max = 0;
+    for (int c = 0; c < 6; c++) {
+        const uint64_t cap = std::min<uint64_t>(P.grid_cap, (uint64_t)INT32_MAX);
+        per_block[c] = std::max<uint64_t>(1, (P.chunks[c] + cap - 1) / cap);
+        grids[c] = (P.chunks[c] + per_block[c] - 1) / per_block[c];
+        grid_max = std::max(grid_max, grids[c]);
+    }
+    HIP_TRY(W.hist_pm.ensure((size_t)(grid_max * P.hist_slice * MINE_THREADS * sizeof(smx::cons_pm))));
+    HIP_TRY(W.hist_s.ensure((size_t)(grid_max * P.hist_slice * MINE_THREADS * sizeof(int))));
+    if (P.n_align[0]) HIP_TRY(W.scratch.ensure((size_t)grids[0] * 3 * P.words_max0 * MINE_THREADS * 8));
+    if (!pileup) {
+        HIP_TRY(W.votes.ensure((size_t)P.votes_words * 4));
+        HIP_TRY(W.aligned.ensure((size_t)n_jobs * 4));
+    }
+    KernelTimer timer;
+    if (kernel_ms) HIP_TRY(timer.start());
+    static const int kWords[6] = {0, 1, 2, 4, 8, 16};
+    size_t jat = 0, cat = 0;
+    int e = 0;
+    for (int c = 0; c < 6 && e == 0; c++) {
+        const uint32_t n = P.n_align[c];
+        if (!n) continue;
+        e = smx_launch_cons_align(nullptr, kWords[c], W.reads.as<unsigned char>(), W.doff.as<uint64_t>(), W.len.as<int32_t>(),
+                                  W.k.as<int32_t>(), W.align.as<smx::ConsJobDev>() + jat, W.chunk_start.as<uint64_t>() + cat, n,
+                                  (int)grids[c], per_block[c], P.lds_max[c], W.rows.as<uint32_t>(), W.dist.as<int32_t>(),
+                                  W.hist_pm.p, W.hist_s.as<int>(), P.hist_slice, W.scratch.as<unsigned long long>(),
+                                  P.words_max0);
+        jat += n;
+        cat += (size_t)n + 1;
+    }
+    if (e == 0 && !pileup)
+        e = smx_launch_cons_vote(nullptr, W.len.as<int32_t>(), W.jobs.p, n_jobs, P.max_words, W.rows.as<uint32_t>(),
+                                 W.dist.as<int32_t>(), W.votes.as<uint32_t>(), W.aligned.as<uint32_t>());
+    if (e != 0) return fail(SMX_ERR_DEVICE, "consensus kernel launch failed: %s", hipGetErrorString((hipError_t)e));
+    if (kernel_ms) HIP_TRY(timer.stop(kernel_ms));
+    HIP_TRY(hipDeviceSynchronize());
+    if (pileup) {
+        if (P.n_dist) HIP_TRY(hipMemcpy(dist, W.dist.p, (size_t)P.n_dist * 4, hipMemcpyDeviceToHost));
+        if (P.rows_words) HIP_TRY(hipMemcpy(rows, W.rows.p, (size_t)P.rows_words * 4, hipMemcpyDeviceToHost));
+        for (const smx::ConsJobDev &J : P.jobs) {     // a member above the limit has no row
+            const size_t words = (size_t)P.len[J.draft] + 1;
+            for (uint32_t i = 0; i < J.n; i++)
+                if (dist[J.dist_off + i] < 0) memset(rows + J.rows_off + i * words, 0xff, words * 4);
+        }
+    } else {
+        HIP_TRY(hipMemcpy(votes, W.votes.p, (size_t)P.votes_words * 4, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(aligned, W.aligned.p, (size_t)n_jobs * 4, hipMemcpyDeviceToHost));
+    }
+    return SMX_OK;
+}
+}  // namespace
+
+int smx_cons_pileup(const char *reads, const uint64_t *roff, uint32_t n_reads, const int32_t *k, const smx_cons_job *jobs,
+                    uint32_t n_jobs, uint32_t *rows, int32_t *dist, float *kernel_ms) {
+    if (n_jobs && (!rows || !dist)) return fail(SMX_ERR_ARG, "null argument");
+    return cons_call(reads, roff, n_reads, k, jobs, n_jobs, rows, dist, nullptr, nullptr, kernel_ms);
+}
+
+int smx_cons_votes(const char *reads, const uint64_t *roff, uint32_t n_reads, const int32_t *k, const smx_cons_job *jobs,
+                   uint32_t n_jobs, uint32_t *votes, uint32_t *aligned, float *kernel_ms) {
+    if (n_jobs && (!votes || !aligned)) return fail(SMX_ERR_ARG, "null argument");
+    return cons_call(reads, roff, n_reads, k, jobs, n_jobs, nullptr, nullptr, votes, aligned, kernel_ms);
 }
 
 // ---- inner scan: every pattern against the whole read, hits on the internal columns (smx_inner.hip)

@@ -1,0 +1,128 @@
+// smx_cons_plan.h -- the host-side plan of one smx_cons_* call (smx_calls.cpp): argument checks, the jobs with their
+// offsets, the alignment's job list by register class with its chunk prefix, and the size of the history workspace.
+// Host only and free of HIP calls, so that the sanitizer driver (tests/asan/cons_driver.cpp) runs it as it is.
+#ifndef SMX_CONS_PLAN_H
+#define SMX_CONS_PLAN_H
+#include <algorithm>
+#include <string>
+#include <vector>
+
+#include "smx_internal.h"
+#include "smx_cons_core.h"
+
+namespace smx {
+
+constexpr uint64_t CONS_HIST_BYTES = (uint64_t)2 << 30;      // the history workspace of the workgroups in flight, at most
+constexpr uint64_t CONS_HIST_ENTRY = sizeof(cons_pm) + sizeof(int);   // one block of one column of one lane
+
+struct ConsPlan {
+    std::vector<ConsJobDev> jobs;          // the caller's jobs in the caller's order: what the vote kernel walks
+    std::vector<ConsJobDev> align;         // the jobs with members, class after class (0 = generic, 1..5 = 1..16 words)
+    std::vector<uint64_t> chunk_start;     // per class with jobs: its jobs' chunk prefix, n + 1 entries
+    uint32_t n_align[6] = {0, 0, 0, 0, 0, 0};
+    uint64_t chunks[6] = {0, 0, 0, 0, 0, 0};
+    size_t lds_max[6] = {0, 0, 0, 0, 0, 0};
+    int words_max0 = 0;                    // the generic class's longest draft, in words
+    uint64_t hist_slice = 0;               // history entries per lane of one workgroup
+    uint64_t grid_cap = 1;                 // workgroups whose slices fit hist_budget
+    uint64_t rows_words = 0, n_dist = 0, votes_words = 0;
+    uint32_t max_words = 0;                // the longest draft's m + 1
+    std::vector<int32_t> len;              // per read
+};
+
+// Returns SMX_OK, or the status to fail with and why.  hist_budget: CONS_HIST_BYTES, or a test's smaller figure.
+inline int cons_plan(const char *reads, const uint64_t *roff, uint32_t n_reads, const int32_t *k, const smx_cons_job *jobs,
+                     uint32_t n_jobs, uint64_t hist_budget, ConsPlan *plan, std::string *why) {
+    ConsPlan &P = *plan;
+    P = ConsPlan();
+    P.len.assign(n_reads, 0);
+    for (uint32_t r = 0; r < n_reads; r++) {
+        if (roff[r + 1] < roff[r] || roff[r + 1] - roff[r] > (uint64_t)INT32_MAX) {
+            *why = "read " + std::to_string(r) + ": bad offsets";
+            return SMX_ERR_ARG;
+        }
+        P.len[r] = (int32_t)(roff[r + 1] - roff[r]);
+    }
+    std::vector<uint32_t> order;
+    for (uint32_t j = 0; j < n_jobs; j++) {
+        if (jobs[j].draft >= n_reads || (uint64_t)jobs[j].r0 + jobs[j].n > n_reads) {
+            *why = "job " + std::to_string(j) + ": draft or member range out of bounds";
+            return SMX_ERR_ARG;
+        }
+        if (P.len[jobs[j].draft] == 0) {
+            *why = "job " + std::to_string(j) + ": empty draft";
+            return SMX_ERR_ARG;
+        }
+        if (jobs[j].n) order.push_back(j);
+    }
+    // the member ranges may not overlap: every read has at most one row
+    std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return jobs[a].r0 < jobs[b].r0; });
+    for (size_t i = 1; i < order.size(); i++)
+        if (jobs[order[i - 1]].r0 + jobs[order[i - 1]].n > jobs[order[i]].r0) {
+            *why = "jobs " + std::to_string(order[i - 1]) + " and " + std::to_string(order[i]) + " overlap";
+            return SMX_ERR_ARG;
+        }
+    P.jobs.resize(n_jobs);
+    std::vector<uint32_t> by_class[6];
+    for (uint32_t j = 0; j < n_jobs; j++) {
+        const smx_cons_job &J = jobs[j];
+        const int m = P.len[J.draft];
+        // the draft's Peq table in LDS and its register class: as a specimine query's (mine_queries)
+        bool seen[256] = {false};
+        int nrows = 0;
+        for (uint64_t i = roff[J.draft]; i < roff[J.draft + 1]; i++) {
+            const unsigned char c = (unsigned char)reads[i];
+            if (!seen[c]) { seen[c] = true; nrows++; }
+        }
+        const size_t W = ((size_t)m + 63) / 64, Wp = W | 1;
+        const size_t lds = (MINE_LDS_HEAD + (size_t)(nrows + 1) * Wp) * 8;
+        if (lds > SMX_LDS_POOL) {
+            *why = "job " + std::to_string(j) + ": the draft's " + std::to_string(nrows) + " distinct bytes x " + std::to_string(W) +
+                   " words do not fit the LDS (" + std::to_string(lds) + " > " + std::to_string((size_t)SMX_LDS_POOL) + " bytes)";
+            return SMX_ERR_UNSUPPORTED;
+        }
+        const int c = W <= 1 ? 1 : W <= 2 ? 2 : W <= 4 ? 3 : W <= 8 ? 4 : W <= 16 ? 5 : 0;
+        // the history of the job's widest band over its longest banded read
+        int B = 0, cols = 0;
+        for (uint32_t i = 0; i < J.n; i++) {
+            const uint32_t r = J.r0 + i;
+            const int kp = (k[J.draft] < 0 || k[r] < 0) ? -1 : std::max(k[J.draft], k[r]);
+            const int b = cons_band_blocks(m, P.len[r], kp);
+            if (b > 0) { B = std::max(B, b); cols = std::max(cols, P.len[r]); }
+        }
+        P.jobs[j] = ConsJobDev{J.draft, J.r0, J.n, (uint32_t)B, P.rows_words, P.n_dist, P.votes_words};
+        P.rows_words += (uint64_t)J.n * ((uint64_t)m + 1);
+        P.n_dist += J.n;
+        P.votes_words += ((uint64_t)m + 1) * SMX_CONS_VOTE_WORDS;
+        P.max_words = std::max(P.max_words, (uint32_t)m + 1);
+        if (J.n == 0) continue;
+        P.hist_slice = std::max(P.hist_slice, (uint64_t)B * (uint64_t)cols);
+        P.lds_max[c] = std::max(P.lds_max[c], lds);
+        if (c == 0) P.words_max0 = std::max(P.words_max0, (int)W);
+        by_class[c].push_back(j);
+    }
+    const uint64_t slice_bytes = P.hist_slice * MINE_THREADS * CONS_HIST_ENTRY;
+    if (slice_bytes > hist_budget) {
+        *why = "one workgroup's alignment history needs " + std::to_string(slice_bytes) + " bytes, more than the " +
+               std::to_string(hist_budget) + " of the workspace: lower the limits k or shorten the reads";
+        return SMX_ERR_UNSUPPORTED;
+    }
+    P.grid_cap = std::max<uint64_t>(1, hist_budget / std::max<uint64_t>(slice_bytes, 1));
+    for (int c = 0; c < 6; c++) {
+        if (by_class[c].empty()) continue;
+        // in draft order: a workgroup rebuilds the Peq table only when the draft changes
+        std::stable_sort(by_class[c].begin(), by_class[c].end(), [&](uint32_t a, uint32_t b) { return jobs[a].draft < jobs[b].draft; });
+        P.n_align[c] = (uint32_t)by_class[c].size();
+        P.chunk_start.push_back(0);
+        for (uint32_t j : by_class[c]) {
+            P.align.push_back(P.jobs[j]);
+            P.chunks[c] += (P.jobs[j].n + MINE_THREADS - 1) / MINE_THREADS;
+            P.chunk_start.push_back(P.chunks[c]);
+        }
+    }
+    return SMX_OK;
+}
+
+}  // namespace smx
+
+#endif  // SMX_CONS_PLAN_H

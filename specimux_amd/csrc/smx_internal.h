@@ -109,6 +109,15 @@ struct PairsRow {     // row i of a job's triangle: ceil(n / MINE_THREADS) - (i 
     uint32_t read;    // the query: read r0 + i
 };
 
+// consensus (smx_cons.hip): a job's draft against its member reads [r0, r0 + n); chunks of MINE_THREADS members
+struct ConsJobDev {
+    uint32_t draft, r0, n;
+    uint32_t B;           // history slots per column: the most any member's band needs (smx_cons_core.h cons_band_blocks)
+    uint64_t rows_off;    // the job's n x (m + 1) row words
+    uint64_t dist_off;    // its n distances
+    uint64_t votes_off;   // its (m + 1) x SMX_CONS_VOTE_WORDS vote words
+};
+
 // inner scan (smx_inner.hip): one chunk of whole reads and one word-width class of patterns.  Device pointers.
 struct InnerArgs {
     const void *peq;               // [pass][16 codes][G] match words, 32 or 64 bits wide
@@ -165,6 +174,16 @@ int smx_launch_pairs(void *stream, int wr, int dist, const unsigned char *d_byte
                      const int32_t *d_k, const void *d_rows, const uint64_t *d_chunk_start, uint32_t n_rows,
                      const void *d_jobs, int grid, uint64_t per_block, size_t lds_bytes, void *d_out,
                      unsigned long long *d_scratch, int scratch_words);
+// consensus (smx_cons.hip); wr, grid, per_block, d_scratch, d_bytes / d_off / d_len / d_k as for smx_launch_pairs.
+// jobs[0..n_jobs) (ConsJobDev, n > 0 each) with chunk_start[0..n_jobs]; workgroup b keeps its history in entries
+// [b * hist_slice * MINE_THREADS, (b + 1) * hist_slice * MINE_THREADS) of d_hist_pm (16 bytes each) and d_hist_s.
+int smx_launch_cons_align(void *stream, int wr, const unsigned char *d_bytes, const uint64_t *d_off, const int32_t *d_len,
+                          const int32_t *d_k, const void *d_jobs, const uint64_t *d_chunk_start, uint32_t n_jobs, int grid,
+                          uint64_t per_block, size_t lds_bytes, uint32_t *d_rows, int32_t *d_dist, void *d_hist_pm,
+                          int *d_hist_s, uint64_t hist_slice, unsigned long long *d_scratch, int scratch_words);
+// the votes of jobs[0..n_jobs) (any n) from the rows and distances the alignment left; max_words = the largest m + 1
+int smx_launch_cons_vote(void *stream, const int32_t *d_len, const void *d_jobs, uint32_t n_jobs, uint32_t max_words,
+                         const uint32_t *d_rows, const int32_t *d_dist, uint32_t *d_votes, uint32_t *d_aligned);
 // inner scan (smx_inner.hip): the scan over A->n_units units x npass passes of G (4 or 8) patterns, w64 = 64-bit words;
 // then one merge launch over n_reads x A->Q (read, pattern) pairs once every class has left its records
 int smx_launch_inner_scan(void *stream, int w64, int G, int npass, const smx::InnerArgs *A);
