@@ -23,6 +23,7 @@
  *           HW distances and the per-partial-read best identity.
  *   smx_pairs_*       <- nothing: the reference leaves "is this specimen one organism?" to the tools after it
  *           (DESIGN.md section 14).
+ *   smx_nearest*      <- nothing: nor does it ask where a well's foreign reads came from.
  *   smx_cons_*        <- nothing: the reference hands the consensus of a specimen to an external tool (DESIGN.md
  *           section 15).
  *   smx_inner_scan    <- nothing: the reference never looks between the two end windows.
@@ -43,7 +44,7 @@
 extern "C" {
 #endif
 
-#define SMX_ABI_VERSION 8
+#define SMX_ABI_VERSION 9
 
 typedef enum {
     SMX_OK = 0,
@@ -370,6 +371,40 @@ int smx_cons_pileup(const char *reads, const uint64_t *roff, uint32_t n_reads, c
                     const smx_cons_job *jobs, uint32_t n_jobs, uint32_t *rows, int32_t *dist, float *kernel_ms);
 int smx_cons_votes(const char *reads, const uint64_t *roff, uint32_t n_reads, const int32_t *k,
                    const smx_cons_job *jobs, uint32_t n_jobs, uint32_t *votes, uint32_t *aligned, float *kernel_ms);
+
+/*
+ * crosstalk: NW (global) edit distances of every read of a run to every consensus (ref) of the run, reduced on the device
+ * to each read's nearest ref of its own group and its nearest ref of any other group -- nothing in the reference does
+ * this.  The pair code is clusters': exact byte equality, distance only.
+ *   seqs / off         n_seqs sequences (concatenated, n_seqs + 1 offsets): the reads and the refs share one array, as
+ *                      the drafts and members of smx_cons_* do.  A read may have any length (an empty read is at distance
+ *                      len(ref) from a ref); a ref is not empty and its Peq table must fit the LDS, as a read's in
+ *                      smx_pairs_* (SMX_ERR_UNSUPPORTED)
+ *   k                  per sequence: its max distance (< 0: no limit).  The limit of a (ref, read) pair is
+ *                      max(k[ref], k[read]), no limit if either has none: the smx_pairs_* rule
+ *   group              per sequence: a ref is "own" to a read iff their groups are equal
+ *   jobs               each job compares the refs [q0, q0 + nq) with the reads [t0, t0 + nt).  nq = 0 and nt = 0 are
+ *                      legal.  Ref ranges of different jobs may overlap (many jobs over one ref set).  SMX_ERR_ARG, before
+ *                      anything is launched: an empty ref, an index out of range, read ranges of two jobs that overlap
+ * smx_nearest: job after job, nt entries of best_own and of best_other: ((uint64_t)d << 32) | ref for the ref (its index
+ * in seqs) at the smallest distance d within the pair's limit among the job's refs of the read's group (best_own) and
+ * among all its other refs (best_other); of refs at equal distance the lowest index; UINT64_MAX where there is none.
+ * The device keeps one 64-bit minimum per read and array (atomicMin over a total order): the arrays are the same from
+ * run to run, and device and host memory are bounded by the sequences and sum(nt) -- nothing is sized by sum(nq * nt).
+ * SMX_NEAREST_MIN_CHUNKS (environment) overrides the number of chunks the plan keeps the call above when it chooses how
+ * many refs a workgroup takes in a row; it changes the speed, never the result.
+ * smx_nearest_distances, kept for tests and inspection, writes job after job its nq x nt distances, one row per ref
+ * (int32, -1 above the limit).
+ * kernel_ms (may be NULL) receives the device time of the kernels (HIP events).
+ */
+typedef struct smx_nearest_job {
+    uint32_t q0, nq, t0, nt;   /* refs [q0, q0 + nq), reads [t0, t0 + nt): indices into seqs */
+} smx_nearest_job;
+
+int smx_nearest(const char *seqs, const uint64_t *off, uint32_t n_seqs, const int32_t *k, const uint32_t *group,
+                const smx_nearest_job *jobs, uint32_t n_jobs, uint64_t *best_own, uint64_t *best_other, float *kernel_ms);
+int smx_nearest_distances(const char *seqs, const uint64_t *off, uint32_t n_seqs, const int32_t *k, const uint32_t *group,
+                          const smx_nearest_job *jobs, uint32_t n_jobs, int32_t *dist, float *kernel_ms);
 
 /*
  * Match statistics (specimux-stats; reference trace_stats.py): the "pool -> primer pair -> outcome" tables counted on the

@@ -2,6 +2,7 @@
 // (smx_mine.hip), clusters (smx_pairs.hip), consensus (smx_cons.hip) and the inner scan (smx_inner.hip).  Each keeps one grow-only device workspace; its calls are serialised.
 #include "smx_host.h"
 #include "smx_cons_plan.h"
+#include "smx_nearest_plan.h"
 
 int smx_align(const char *query, int qlen, const char *target, int tlen, int k, int mode, int *dist, int *starts,
               int *ends, int cap, int *nloc) {
@@ -416,6 +417,106 @@ int smx_pairs_distances(const char *reads, const uint64_t *roff, uint32_t n_read
 int smx_pairs_neighbours(const char *reads, const uint64_t *roff, uint32_t n_reads, const int32_t *k,
                          const smx_pairs_job *jobs, uint32_t n_jobs, uint32_t *adj, float *kernel_ms) {
     return pairs_call(false, reads, roff, n_reads, k, jobs, n_jobs, adj, kernel_ms);
+}
+
+// ---- crosstalk: every read of a job against every ref of the job, reduced to the nearest own and the nearest other
+// ref (smx_nearest.hip); a workspace of its own, like g_pairs
+namespace {
+struct {
+    std::mutex mutex;
+    DevBuf seqs, doff, len, k, group, refs, runs, chunk_start, jobs;
+    DevBuf scratch;     // per-lane state of the generic class, one slice per workgroup
+    DevBuf out;         // best_own then best_other, or the distances
+} g_nearest;
+
+// One smx_nearest* call.  distances: dist receives job after job its nq x nt distances; else own / other receive
+// sum(nt) keys each.
+int nearest_call(bool distances, const char *seqs, const uint64_t *off, uint32_t n_seqs, const int32_t *k,
+                 const uint32_t *group, const smx_nearest_job *jobs, uint32_t n_jobs, uint64_t *own, uint64_t *other,
+                 int32_t *dist, float *kernel_ms) {
+    if (!seqs || !off || !k || !group || (n_jobs && (!jobs || (distances ? !dist : !own || !other))))
+        return fail(SMX_ERR_ARG, "null argument");
+    // every check of the arguments comes before the device is touched
+    smx::NearestPlan P;
+    std::string why;
+    const int rc = smx::nearest_plan(seqs, off, n_seqs, jobs, n_jobs, &P, &why);
+    if (rc != SMX_OK) return fail(rc, "%s", why.c_str());
+    std::lock_guard<std::mutex> guard(g_nearest.mutex);
+    SMX_TRY(require_device());
+    // G: the chunks a call should keep the device busy with, 32 per CU, or the test hook's figure
+    uint64_t min_chunks = 0;
+    if (const char *env = getenv("SMX_NEAREST_MIN_CHUNKS")) {
+        min_chunks = strtoull(env, nullptr, 10);
+    } else {
+        int dev = 0, n_cu = 0;
+        HIP_TRY(hipGetDevice(&dev));
+        HIP_TRY(hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev));
+        min_chunks = smx::NEAREST_CHUNKS_PER_CU * (uint64_t)std::max(n_cu, 1);
+    }
+    smx::nearest_plan_runs(&P, min_chunks);
+    if (kernel_ms) *kernel_ms = 0.0f;
+    if ((distances ? P.n_dist : P.n_best) == 0) return SMX_OK;
+    const size_t out_bytes = distances ? (size_t)P.n_dist * 4 : (size_t)P.n_best * 16;
+    if (P.runs.empty()) {                         // reads, but no job has a ref: no key, no distance
+        if (!distances) { memset(own, 0xff, (size_t)P.n_best * 8); memset(other, 0xff, (size_t)P.n_best * 8); }
+        return SMX_OK;
+    }
+    std::vector<uint64_t> doff;
+    std::vector<int32_t> len;
+    std::vector<unsigned char> pad;
+    SMX_TRY(mine_targets(seqs, off, n_seqs, &doff, &len, &pad));
+    auto &W = g_nearest;
+    HIP_TRY(W.seqs.upload(pad));
+    HIP_TRY(W.doff.upload(doff));
+    HIP_TRY(W.len.upload(len));
+    HIP_TRY(W.k.upload(k, (size_t)n_seqs * 4));
+    HIP_TRY(W.group.upload(group, (size_t)n_seqs * 4));
+    HIP_TRY(W.refs.upload(P.refs));
+    HIP_TRY(W.runs.upload(P.runs));
+    HIP_TRY(W.chunk_start.upload(P.chunk_start));
+    HIP_TRY(W.jobs.upload(P.jobs));
+    if (P.n_runs[0]) HIP_TRY(W.scratch.ensure((size_t)P.scratch_words * 8));
+    HIP_TRY(W.out.ensure(out_bytes));
+    // nearest: "no ref" until a lane says otherwise.  distances: every pair is written (nt > 0 and nq > 0 make runs)
+    if (!distances) HIP_TRY(hipMemset(W.out.p, 0xff, out_bytes));
+    unsigned long long *d_own = W.out.as<unsigned long long>(), *d_other = d_own + (distances ? 0 : P.n_best);
+    KernelTimer timer;
+    if (kernel_ms) HIP_TRY(timer.start());
+    static const int kWords[6] = {0, 1, 2, 4, 8, 16};
+    size_t qat = 0, rat = 0, cat = 0;
+    int e = 0;
+    for (int c = 0; c < 6 && e == 0; c++) {
+        const uint32_t n = P.n_runs[c];
+        if (n)
+            e = smx_launch_nearest(nullptr, kWords[c], distances, W.seqs.as<unsigned char>(), W.doff.as<uint64_t>(),
+                                   W.len.as<int32_t>(), W.k.as<int32_t>(), W.group.as<uint32_t>(), W.refs.as<uint32_t>() + qat,
+                                   W.runs.as<smx::NearestRun>() + rat, W.chunk_start.as<uint64_t>() + cat, n, W.jobs.p,
+                                   (int)P.grid[c], P.per_block[c], P.lds_max[c], d_own, d_other, W.out.as<int32_t>(),
+                                   W.scratch.as<unsigned long long>(), P.words_max0);
+        qat += P.n_refs[c];
+        if (n) { rat += n; cat += (size_t)n + 1; }
+    }
+    if (e != 0) return fail(SMX_ERR_DEVICE, "nearest kernel launch failed: %s", hipGetErrorString((hipError_t)e));
+    if (kernel_ms) HIP_TRY(timer.stop(kernel_ms));
+    HIP_TRY(hipDeviceSynchronize());
+    if (distances) {
+        HIP_TRY(hipMemcpy(dist, W.out.p, out_bytes, hipMemcpyDeviceToHost));
+    } else {
+        HIP_TRY(hipMemcpy(own, d_own, (size_t)P.n_best * 8, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(other, d_other, (size_t)P.n_best * 8, hipMemcpyDeviceToHost));
+    }
+    return SMX_OK;
+}
+}  // namespace
+
+int smx_nearest(const char *seqs, const uint64_t *off, uint32_t n_seqs, const int32_t *k, const uint32_t *group,
+                const smx_nearest_job *jobs, uint32_t n_jobs, uint64_t *best_own, uint64_t *best_other, float *kernel_ms) {
+    return nearest_call(false, seqs, off, n_seqs, k, group, jobs, n_jobs, best_own, best_other, nullptr, kernel_ms);
+}
+
+int smx_nearest_distances(const char *seqs, const uint64_t *off, uint32_t n_seqs, const int32_t *k, const uint32_t *group,
+                          const smx_nearest_job *jobs, uint32_t n_jobs, int32_t *dist, float *kernel_ms) {
+    return nearest_call(true, seqs, off, n_seqs, k, group, jobs, n_jobs, nullptr, nullptr, dist, kernel_ms);
 }
 
 // ---- consensus: every member read of a job aligned to the job's draft with traceback, the rows reduced to votes

@@ -184,6 +184,15 @@ int smx_launch_cons_align(void *stream, int wr, const unsigned char *d_bytes, co
 // the votes of jobs[0..n_jobs) (any n) from the rows and distances the alignment left; max_words = the largest m + 1
 int smx_launch_cons_vote(void *stream, const int32_t *d_len, const void *d_jobs, uint32_t n_jobs, uint32_t max_words,
                          const uint32_t *d_rows, const int32_t *d_dist, uint32_t *d_votes, uint32_t *d_aligned);
+// crosstalk (smx_nearest.hip); wr, grid, per_block, d_scratch, d_bytes / d_off / d_len / d_k as for smx_launch_pairs;
+// d_group: the group per sequence.  runs[0..n_runs) (NearestRun over the class's ref list d_refs) with
+// chunk_start[0..n_runs] (nonzero each).  dist = 1: d_dist holds int32 distances, job j's nq x nt at its dist_off;
+// dist = 0: d_best_own / d_best_other hold the keys (filled with 0xFF bytes by the caller), job j's nt at its best_off
+int smx_launch_nearest(void *stream, int wr, int dist, const unsigned char *d_bytes, const uint64_t *d_off, const int32_t *d_len,
+                       const int32_t *d_k, const uint32_t *d_group, const uint32_t *d_refs, const void *d_runs,
+                       const uint64_t *d_chunk_start, uint32_t n_runs, const void *d_jobs, int grid, uint64_t per_block,
+                       size_t lds_bytes, unsigned long long *d_best_own, unsigned long long *d_best_other, int32_t *d_dist,
+                       unsigned long long *d_scratch, int scratch_words);
 // inner scan (smx_inner.hip): the scan over A->n_units units x npass passes of G (4 or 8) patterns, w64 = 64-bit words;
 // then one merge launch over n_reads x A->Q (read, pattern) pairs once every class has left its records
 int smx_launch_inner_scan(void *stream, int w64, int G, int npass, const smx::InnerArgs *A);
