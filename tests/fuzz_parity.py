@@ -1,6 +1,9 @@
 #!/usr/bin/env python3
 """Manual, longer-running parity fuzz (not collected by pytest): GPU records vs the oracle over many seeds, panel
-shapes, flag sets and search lengths.  Run on a GPU box:  python tests/fuzz_parity.py [--seeds 8] [--reads 1200]"""
+shapes, flag sets and search lengths.  Run on a GPU box:  python tests/fuzz_parity.py [--seeds 8] [--reads 1200]
+The synthetic panels are full barcode grids with one primer pair per pool; the scorer's rarer branches are reached by the
+hand-written panels of tests/scorer_utils.py (multi, two_pairs, one_pair_sparse, wide, same_sequence): `--panel multi`
+runs such a panel's constructed reads under every fuzz flag set."""
 import argparse
 import itertools
 import os
@@ -26,7 +29,10 @@ def main():
     ap.add_argument("--reads", type=int, default=1200)
     ap.add_argument("--trim", default=None, help="force this trim mode onto every flag set (e.g. tails)")
     ap.add_argument("--index-k", type=int, default=None, help="force this index edit distance onto every flag set")
-    ap.add_argument("--panel", default=None, choices=["c1", "c2", "c3"], help="this panel only (default: all three in rotation)")
+    import scorer_utils as SU
+    ap.add_argument("--panel", default=None, choices=["c1", "c2", "c3"] + list(SU.PANELS),
+                    help="this panel only (default: c1, c2, c3 in rotation); a hand-written scorer panel of tests/scorer_utils.py "
+                         "runs its constructed reads (no seeds) under every flag set")
     a = ap.parse_args()
     from specimux_amd import synth
     from parity_utils import FUZZ_FLAG_SETS
@@ -36,6 +42,17 @@ def main():
     if a.index_k is not None:
         flag_sets = [dict(f, index_edit_distance=a.index_k) for f in flag_sets if "index_edit_distance" not in f]
     tmp = tempfile.mkdtemp(prefix="smx_fuzz_")
+    if a.panel in SU.PANELS:
+        pf, sf = SU.PANELS[a.panel].write(tmp)
+        reads = SU.make_reads(SU.PANELS[a.panel])
+        for flags in flag_sets:
+            flags = {k: v for k, v in flags.items() if k not in ("error_rate", "n_frac")}
+            both = Both(pf, sf, **flags)
+            both.assert_hits_equal(reads[::10], f"{a.panel} {flags}")
+            both.assert_ops_equal(reads, f"{a.panel} {flags}")
+            print(f"ok {a.panel} {flags}  ({len(reads)} reads)", flush=True)
+        print(f"fuzz parity OK: {a.panel}, {len(flag_sets)} flag sets")
+        return
     panels = {"c2": synth.panel_c2(), "c3": synth.panel_c3(), "c1": synth.panel_c1()}
     files = {}
     for name, pan in panels.items():
