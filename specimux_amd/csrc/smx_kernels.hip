@@ -1865,7 +1865,8 @@ struct DemuxTile {
             for (int ci = wid; ci < 2 * nhead; ci += nw) {
                 const bool tail = ci >= nhead;
                 const int k = tail ? ci - nhead : ci;
-                const int r = (int)__umulhi((unsigned)k, hcmagic), c = k - __mul24(r, hc);
+                // (one chunk per window, search_len 16: the reciprocal of 1 is 2^32, which hcmagic cannot hold)
+                const int r = hc == 1 ? k : (int)__umulhi((unsigned)k, hcmagic), c = k - __mul24(r, hc);
                 const uint4 v = *(const uint4 *)(windows + (size_t)(r0n + r) * stride + (tail ? S : 0) + 16 * c);
                 const int L = lens[r0n + r];
                 // ACGT fast path, four bases per dword without the LUT: (ch >> 1) & 3 maps A,C,T,G -> 0,1,2,3; swapping 2 and 3

@@ -3,7 +3,9 @@
 shapes, flag sets and search lengths.  Run on a GPU box:  python tests/fuzz_parity.py [--seeds 8] [--reads 1200]
 The synthetic panels are full barcode grids with one primer pair per pool; the scorer's rarer branches are reached by the
 hand-written panels of tests/scorer_utils.py (multi, two_pairs, one_pair_sparse, wide, same_sequence): `--panel multi`
-runs such a panel's constructed reads under every fuzz flag set."""
+runs such a panel's constructed reads under every fuzz flag set.  The primer-search panels of tests/primer_utils.py (m22,
+m31, m32, m33, m63, m64, m32_rev, m64_rev, deg5, c3_m33; c3 stays the synthetic panel) work the same way: `--panel m64`
+builds the constructed reads for each flag set's search length."""
 import argparse
 import itertools
 import os
@@ -30,9 +32,12 @@ def main():
     ap.add_argument("--trim", default=None, help="force this trim mode onto every flag set (e.g. tails)")
     ap.add_argument("--index-k", type=int, default=None, help="force this index edit distance onto every flag set")
     import scorer_utils as SU
-    ap.add_argument("--panel", default=None, choices=["c1", "c2", "c3"] + list(SU.PANELS),
+    import primer_utils as PU
+    primer_panels = [n for n in PU.PANELS if n != "c3"]
+    ap.add_argument("--panel", default=None, choices=["c1", "c2", "c3"] + list(SU.PANELS) + primer_panels,
                     help="this panel only (default: c1, c2, c3 in rotation); a hand-written scorer panel of tests/scorer_utils.py "
-                         "runs its constructed reads (no seeds) under every flag set")
+                         "or a primer-search panel of tests/primer_utils.py runs its constructed reads (no seeds) under every "
+                         "flag set")
     a = ap.parse_args()
     from specimux_amd import synth
     from parity_utils import FUZZ_FLAG_SETS
@@ -49,6 +54,17 @@ def main():
             flags = {k: v for k, v in flags.items() if k not in ("error_rate", "n_frac")}
             both = Both(pf, sf, **flags)
             both.assert_hits_equal(reads[::10], f"{a.panel} {flags}")
+            both.assert_ops_equal(reads, f"{a.panel} {flags}")
+            print(f"ok {a.panel} {flags}  ({len(reads)} reads)", flush=True)
+        print(f"fuzz parity OK: {a.panel}, {len(flag_sets)} flag sets")
+        return
+    if a.panel in primer_panels:
+        pf, sf = PU.PANELS[a.panel]().write(tmp)
+        for flags in flag_sets:
+            flags = {k: v for k, v in flags.items() if k not in ("error_rate", "n_frac")}
+            reads = PU.cell(a.panel, flags.get("search_len", 80)).reads
+            both = Both(pf, sf, **flags)
+            both.assert_hits_equal(reads, f"{a.panel} {flags}")
             both.assert_ops_equal(reads, f"{a.panel} {flags}")
             print(f"ok {a.panel} {flags}  ({len(reads)} reads)", flush=True)
         print(f"fuzz parity OK: {a.panel}, {len(flag_sets)} flag sets")
