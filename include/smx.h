@@ -24,6 +24,8 @@
  *   smx_pairs_*       <- nothing: the reference leaves "is this specimen one organism?" to the tools after it
  *           (DESIGN.md section 14).
  *   smx_nearest*      <- nothing: nor does it ask where a well's foreign reads came from.
+ *   smx_best_hits*    <- nothing: naming a consensus from a reference FASTA is left to BLAST or a web form (DESIGN.md
+ *           section 17).
  *   smx_cons_*        <- nothing: the reference hands the consensus of a specimen to an external tool (DESIGN.md
  *           section 15).
  *   smx_inner_scan    <- nothing: the reference never looks between the two end windows.
@@ -44,7 +46,7 @@
 extern "C" {
 #endif
 
-#define SMX_ABI_VERSION 9
+#define SMX_ABI_VERSION 10
 
 typedef enum {
     SMX_OK = 0,
@@ -405,6 +407,44 @@ int smx_nearest(const char *seqs, const uint64_t *off, uint32_t n_seqs, const in
                 const smx_nearest_job *jobs, uint32_t n_jobs, uint64_t *best_own, uint64_t *best_other, float *kernel_ms);
 int smx_nearest_distances(const char *seqs, const uint64_t *off, uint32_t n_seqs, const int32_t *k, const uint32_t *group,
                           const smx_nearest_job *jobs, uint32_t n_jobs, int32_t *dist, float *kernel_ms);
+
+/*
+ * identify: the best few records of a reference FASTA for every consensus sequence of a run -- nothing in the reference
+ * does this.  The pair code is specimine's (HW, infix edit distance, exact byte equality).
+ *   seqs / off         n_seqs sequences (concatenated, n_seqs + 1 offsets): queries and targets share one array.  No
+ *                      query or target may be empty (SMX_ERR_ARG)
+ *   k                  per sequence: its max distance (< 0: no limit).  The limit of a pair is its pattern's
+ *   jobs               each job compares the queries [q0, q0 + nq) with the targets [t0, t0 + nt).  nq = 0 and nt = 0 are
+ *                      legal.  Target ranges of different jobs may overlap (many jobs over one uploaded database); query
+ *                      ranges may not (SMX_ERR_ARG: every query has one output row).  nt <= 2^24 (SMX_ERR_UNSUPPORTED)
+ *   K                  hits kept per query, 1..SMX_HITS_MAX_K (SMX_ERR_ARG)
+ *   min_cov_permille   0..1000 (SMX_ERR_ARG)
+ * The pair rule: of a (query, target) pair the shorter sequence is the pattern, the other the text, the query at equal
+ * length; d = HW(pattern in text) within k[pattern], and the pair counts only if
+ * len(pattern) * 1000 >= min_cov_permille * len(text).  A pattern must be shorter than 2^19 bytes and its Peq table must
+ * fit the LDS (SMX_ERR_UNSUPPORTED).  Every refusal comes before anything is launched.
+ * smx_best_hits: job after job, per query K keys in ascending order, padded with UINT64_MAX:
+ *   bits 63-43  ((uint64_t)d << 20) / len(pattern), integer division
+ *   bits 42-24  d
+ *   bits 23-0   the target's index within the job, t - t0
+ * so that unsigned order is "lower edit fraction, then fewer edits, then lower target index".  The device keeps K 64-bit
+ * slots per query and inserts with atomicMin over this total order: the keys are the same from run to run, and device
+ * and host memory are bounded by the sequences and sum(nq) * K -- nothing is sized by sum(nq * nt).
+ * smx_best_hits_distances, kept for tests and inspection, writes job after job its nq x nt distances, one row per query
+ * (int32; -1 above the limit and for pairs that coverage excludes).
+ * kernel_ms (may be NULL) receives the device time of the kernels (HIP events).
+ */
+#define SMX_HITS_MAX_K 16
+
+typedef struct smx_hits_job {
+    uint32_t q0, nq, t0, nt;   /* queries [q0, q0 + nq), targets [t0, t0 + nt): indices into seqs */
+} smx_hits_job;
+
+int smx_best_hits(const char *seqs, const uint64_t *off, uint32_t n_seqs, const int32_t *k, const smx_hits_job *jobs,
+                  uint32_t n_jobs, uint32_t K, uint32_t min_cov_permille, uint64_t *keys, float *kernel_ms);
+int smx_best_hits_distances(const char *seqs, const uint64_t *off, uint32_t n_seqs, const int32_t *k,
+                            const smx_hits_job *jobs, uint32_t n_jobs, uint32_t K, uint32_t min_cov_permille, int32_t *dist,
+                            float *kernel_ms);
 
 /*
  * Match statistics (specimux-stats; reference trace_stats.py): the "pool -> primer pair -> outcome" tables counted on the

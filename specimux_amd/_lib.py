@@ -9,7 +9,7 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SMX_LIB") or os.path.join(_HERE, "libsmx.so")   # SMX_LIB: A/B builds (tools/tune.sh)
 
-ABI_VERSION = 9
+ABI_VERSION = 10
 OK, ERR_ARG, ERR_UNSUPPORTED, ERR_DEVICE, ERR_OVERFLOW = 0, -1, -2, -3, -4
 TRIM = {"none": 0, "tails": 1, "barcodes": 2, "primers": 3}
 DEREP = {"none": 0, "best": 1}
@@ -32,6 +32,9 @@ CONS_MAX_INS, CONS_VOTE_WORDS = 4, 26
 assert PAIRS_JOB_DTYPE.itemsize == 8 and CONS_JOB_DTYPE.itemsize == 12
 NEAREST_JOB_DTYPE = np.dtype([("q0", "<u4"), ("nq", "<u4"), ("t0", "<u4"), ("nt", "<u4")])
 assert NEAREST_JOB_DTYPE.itemsize == 16
+HITS_JOB_DTYPE = np.dtype([("q0", "<u4"), ("nq", "<u4"), ("t0", "<u4"), ("nt", "<u4")])
+HITS_MAX_K = 16
+assert HITS_JOB_DTYPE.itemsize == 16
 
 
 class PanelDesc(C.Structure):
@@ -89,6 +92,9 @@ SYMBOLS = [
     ("smx_pairs_neighbours", C.c_int, [C.c_char_p, _P, C.c_uint32, _P, _P, C.c_uint32, _P, C.POINTER(C.c_float)]),
     ("smx_nearest", C.c_int, [C.c_char_p, _P, C.c_uint32, _P, _P, _P, C.c_uint32, _P, _P, C.POINTER(C.c_float)]),
     ("smx_nearest_distances", C.c_int, [C.c_char_p, _P, C.c_uint32, _P, _P, _P, C.c_uint32, _P, C.POINTER(C.c_float)]),
+    ("smx_best_hits", C.c_int, [C.c_char_p, _P, C.c_uint32, _P, _P, C.c_uint32, C.c_uint32, C.c_uint32, _P, C.POINTER(C.c_float)]),
+    ("smx_best_hits_distances", C.c_int, [C.c_char_p, _P, C.c_uint32, _P, _P, C.c_uint32, C.c_uint32, C.c_uint32, _P,
+                                          C.POINTER(C.c_float)]),
     ("smx_cons_pileup", C.c_int, [C.c_char_p, _P, C.c_uint32, _P, _P, C.c_uint32, _P, _P, C.POINTER(C.c_float)]),
     ("smx_cons_votes", C.c_int, [C.c_char_p, _P, C.c_uint32, _P, _P, C.c_uint32, _P, _P, C.POINTER(C.c_float)]),
     ("smx_inner_scan", C.c_int, [C.c_char_p, _P, C.c_uint32, _P, _P, _P, C.c_uint32, C.c_int32, C.c_uint32, C.c_uint64,

@@ -1,8 +1,9 @@
 // smx_calls.cpp -- the one-shot calls of libsmx.so over host buffers: alignments (smx_align, smx_align_batch), specimine
-// (smx_mine.hip), clusters (smx_pairs.hip), consensus (smx_cons.hip) and the inner scan (smx_inner.hip).  Each keeps one grow-only device workspace; its calls are serialised.
+// (smx_mine.hip), clusters (smx_pairs.hip), consensus (smx_cons.hip), crosstalk (smx_nearest.hip), identify (smx_hits.hip) and the inner scan (smx_inner.hip).  Each keeps one grow-only device workspace; its calls are serialised.
 #include "smx_host.h"
 #include "smx_cons_plan.h"
 #include "smx_nearest_plan.h"
+#include "smx_hits_plan.h"
 
 int smx_align(const char *query, int qlen, const char *target, int tlen, int k, int mode, int *dist, int *starts,
               int *ends, int cap, int *nloc) {
@@ -517,6 +518,88 @@ int smx_nearest(const char *seqs, const uint64_t *off, uint32_t n_seqs, const in
 int smx_nearest_distances(const char *seqs, const uint64_t *off, uint32_t n_seqs, const int32_t *k, const uint32_t *group,
                           const smx_nearest_job *jobs, uint32_t n_jobs, int32_t *dist, float *kernel_ms) {
     return nearest_call(true, seqs, off, n_seqs, k, group, jobs, n_jobs, nullptr, nullptr, dist, kernel_ms);
+}
+
+// ---- identify: every query of a job against every target of the job, the shorter of a pair as the pattern, reduced to
+// the K best targets per query (smx_hits.hip); a workspace of its own, like g_nearest
+namespace {
+struct {
+    std::mutex mutex;
+    DevBuf seqs, doff, len, k, ord, recs, chunk_start, jobs;
+    DevBuf scratch;     // per-lane state of the generic class, one slice per workgroup
+    DevBuf out;         // the keys, or the distances
+} g_hits;
+
+// One smx_best_hits* call.  distances: dist receives job after job its nq x nt distances; else keys receives sum(nq) x K keys.
+int hits_call(bool distances, const char *seqs, const uint64_t *off, uint32_t n_seqs, const int32_t *k,
+              const smx_hits_job *jobs, uint32_t n_jobs, uint32_t K, uint32_t min_cov_permille, uint64_t *keys, int32_t *dist,
+              float *kernel_ms) {
+    if (!seqs || !off || !k || (n_jobs && (!jobs || (distances ? !dist : !keys)))) return fail(SMX_ERR_ARG, "null argument");
+    // every check of the arguments comes before the device is touched
+    smx::HitsPlan P;
+    std::string why;
+    const int rc = smx::hits_plan(seqs, off, n_seqs, jobs, n_jobs, K, min_cov_permille, &P, &why);
+    if (rc != SMX_OK) return fail(rc, "%s", why.c_str());
+    std::lock_guard<std::mutex> guard(g_hits.mutex);
+    SMX_TRY(require_device());
+    if (kernel_ms) *kernel_ms = 0.0f;
+    const uint64_t n_out = distances ? P.n_dist : P.n_rows * K;
+    if (n_out == 0) return SMX_OK;
+    const size_t out_bytes = (size_t)n_out * (distances ? 4 : 8);
+    // "empty slot" / "no hit" until a lane says otherwise: all-ones is UINT64_MAX as a key and -1 as a distance
+    if (P.recs.empty()) {
+        memset(distances ? (void *)dist : (void *)keys, 0xff, out_bytes);
+        return SMX_OK;
+    }
+    std::vector<uint64_t> doff;
+    std::vector<int32_t> len;
+    std::vector<unsigned char> pad;
+    SMX_TRY(mine_targets(seqs, off, n_seqs, &doff, &len, &pad));
+    auto &W = g_hits;
+    HIP_TRY(W.seqs.upload(pad));
+    HIP_TRY(W.doff.upload(doff));
+    HIP_TRY(W.len.upload(len));
+    HIP_TRY(W.k.upload(k, (size_t)n_seqs * 4));
+    HIP_TRY(W.ord.upload(P.ord));
+    HIP_TRY(W.recs.upload(P.recs));
+    HIP_TRY(W.chunk_start.upload(P.chunk_start));
+    HIP_TRY(W.jobs.upload(P.jobs));
+    if (P.n_recs[0]) HIP_TRY(W.scratch.ensure((size_t)P.scratch_words * 8));
+    HIP_TRY(W.out.ensure(out_bytes));
+    HIP_TRY(hipMemset(W.out.p, 0xff, out_bytes));
+    KernelTimer timer;
+    if (kernel_ms) HIP_TRY(timer.start());
+    static const int kWords[6] = {0, 1, 2, 4, 8, 16};
+    size_t rat = 0, cat = 0;
+    int e = 0;
+    for (int c = 0; c < 6 && e == 0; c++) {
+        const uint32_t n = P.n_recs[c];
+        if (!n) continue;
+        e = smx_launch_hits(nullptr, kWords[c], distances, W.seqs.as<unsigned char>(), W.doff.as<uint64_t>(),
+                            W.len.as<int32_t>(), W.k.as<int32_t>(), W.ord.as<uint32_t>(), W.recs.as<smx::HitsRec>() + rat,
+                            W.chunk_start.as<uint64_t>() + cat, n, W.jobs.p, (int)P.grid[c], P.per_block[c], P.lds_max[c],
+                            (int)K, W.out.as<unsigned long long>(), W.out.as<int32_t>(), W.scratch.as<unsigned long long>(),
+                            P.words_max0);
+        rat += n;
+        cat += (size_t)n + 1;
+    }
+    if (e != 0) return fail(SMX_ERR_DEVICE, "hits kernel launch failed: %s", hipGetErrorString((hipError_t)e));
+    if (kernel_ms) HIP_TRY(timer.stop(kernel_ms));
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(distances ? (void *)dist : (void *)keys, W.out.p, out_bytes, hipMemcpyDeviceToHost));
+    return SMX_OK;
+}
+}  // namespace
+
+int smx_best_hits(const char *seqs, const uint64_t *off, uint32_t n_seqs, const int32_t *k, const smx_hits_job *jobs,
+                  uint32_t n_jobs, uint32_t K, uint32_t min_cov_permille, uint64_t *keys, float *kernel_ms) {
+    return hits_call(false, seqs, off, n_seqs, k, jobs, n_jobs, K, min_cov_permille, keys, nullptr, kernel_ms);
+}
+
+int smx_best_hits_distances(const char *seqs, const uint64_t *off, uint32_t n_seqs, const int32_t *k,
+                            const smx_hits_job *jobs, uint32_t n_jobs, uint32_t K, uint32_t min_cov_permille, int32_t *dist,
+                            float *kernel_ms) {
+    return hits_call(true, seqs, off, n_seqs, k, jobs, n_jobs, K, min_cov_permille, nullptr, dist, kernel_ms);
 }
 
 // ---- consensus: every member read of a job aligned to the job's draft with traceback, the rows reduced to votes

@@ -193,6 +193,14 @@ int smx_launch_nearest(void *stream, int wr, int dist, const unsigned char *d_by
                        const uint64_t *d_chunk_start, uint32_t n_runs, const void *d_jobs, int grid, uint64_t per_block,
                        size_t lds_bytes, unsigned long long *d_best_own, unsigned long long *d_best_other, int32_t *d_dist,
                        unsigned long long *d_scratch, int scratch_words);
+// identify (smx_hits.hip); wr, grid, per_block, d_scratch, d_bytes / d_off / d_len / d_k as for smx_launch_pairs.
+// recs[0..n_recs) (HitsRec, smx_hits_core.h, windows of the order array d_ord) with chunk_start[0..n_recs] (nonzero
+// each).  dist = 1: d_dist holds int32 distances (filled with -1 by the caller), job j's nq x nt at its dist_off;
+// dist = 0: d_keys holds K keys per query (filled with 0xFF bytes by the caller), job j's rows from its row_off
+int smx_launch_hits(void *stream, int wr, int dist, const unsigned char *d_bytes, const uint64_t *d_off, const int32_t *d_len,
+                    const int32_t *d_k, const uint32_t *d_ord, const void *d_recs, const uint64_t *d_chunk_start,
+                    uint32_t n_recs, const void *d_jobs, int grid, uint64_t per_block, size_t lds_bytes, int K,
+                    unsigned long long *d_keys, int32_t *d_dist, unsigned long long *d_scratch, int scratch_words);
 // inner scan (smx_inner.hip): the scan over A->n_units units x npass passes of G (4 or 8) patterns, w64 = 64-bit words;
 // then one merge launch over n_reads x A->Q (read, pattern) pairs once every class has left its records
 int smx_launch_inner_scan(void *stream, int w64, int G, int npass, const smx::InnerArgs *A);
