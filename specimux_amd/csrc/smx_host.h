@@ -119,6 +119,7 @@ struct KernelTimer : NoCopy {
 // environment on a panel's behalf.
 struct Switches {
     bool no_prescan = false;         // SMX_NO_PRESCAN: every primer alignment by the demux kernel's scalar scan
+    bool prescan_planes = false;     // SMX_PRESCAN_PLANES: the prescan keeps its plane buffer and row-major codes (A/B, parity)
     bool no_bitslice = false;        // SMX_NO_BITSLICE: per-barcode scan instead of the bit-sliced one
     bool no_table_sharing = false;   // SMX_NO_TABLE_SHARING: one barcode table per primer even when lists repeat
     int cap_hits = 0, cap_ents = 0;  // SMX_TEST_CAPS=h,e: small barcode rounds
@@ -172,11 +173,13 @@ struct smx_panel {
     bool pre_ok = false;
     smx::PreDesc pre;
     int pre_mr = 24, pre_nx = 0, pre_blocks_t = 1, pre_blocks_d = 8;   // longest primer, degenerate symbols, residency
-    size_t pre_lds = 0;                      // transpose kernel staging
-    DevBuf pre_planes[SMX_MAX_STREAMS];      // per stream slot: the 2-bit text planes of the batch (read-tile major)
+    size_t pre_lds = 0;                      // staging of the transpose / tile-codes kernel
+    bool pre_tile = false;                   // tile codes: one tile-major code buffer feeds the DP and the demux kernel, no planes
+    DevBuf pre_planes[SMX_MAX_STREAMS];      // per stream slot: the 2-bit text planes of the batch (read-tile major); unused with tile codes
     DevBuf pre_recs[SMX_MAX_STREAMS];        // per stream slot: [2 * NP][search_len / 16][n_reads rounded up to a tile] flag words
     DevBuf pre_match[SMX_MAX_STREAMS];       // per stream slot: match words [tile][2 * NP][32 groups] (bit = read reaches the threshold)
-    DevBuf pre_codes[SMX_MAX_STREAMS];       // per stream slot: row-major 2-bit codes [read][end][chunk] + one flag byte per read behind them
+    DevBuf pre_codes[SMX_MAX_STREAMS];       // per stream slot: 2-bit codes, row-major [read][end][chunk] or (tile codes) [tile][end][chunk][read],
+                                             // + one flag byte per read behind them
     int share = 1;      // smx_panel_set_streams: batches the caller keeps in flight on as many streams
     DevBuf ovf[SMX_MAX_STREAMS];             // per stream slot: overflow list, one entry per compact tile
     hipEvent_t kev[4] = {nullptr, nullptr, nullptr, nullptr};   // smx_debug_kernel_times: start, after transpose, after DP, end

@@ -53,6 +53,7 @@ struct DevPanel {
     const int *bs_tab;        // per primer: its table
     int cap_hits, cap_ents;   // test hook (SMX_TEST_CAPS=h,e): force small barcode rounds; 0 = default sizing
     int no_sp;                // SMX_NO_SPECIALISE (bit 0) / SMX_NO_SPECIALISE_NP (bit 1)
+    int tile_codes;           // the prescan hands tile-major codes on (DemuxAux::tiled of every launch): the two-primer kernel has that layout compiled in
     const unsigned *bs_re;
     unsigned long long *dbg_phase;        // SMX_PHASE_TIMING=1: [grid][16] cycle sums per phase (diagnostic build-in)
 };
@@ -65,8 +66,9 @@ struct DemuxAux {
     int redo;                // 1: this launch processes the reads of ovf_list's tiles (Rc reads each) and nothing else
     int Rc;                  // reads per tile of the compact launch
     int chain;               // 1: another launch of this batch follows: the extra-record and overflow counters stay
-    const unsigned *codes2;  // prescan: row-major 2-bit codes per read in DP order (smx_prescan_core.h codes2_word); nullptr: encode from ASCII
+    const unsigned *codes2;  // prescan: 2-bit codes per read in DP order (smx_prescan_core.h codes2_from_piece); nullptr: encode from ASCII
     const uint8_t *naflag;   // prescan: per read, 1 = a window holds something other than upper-case ACGT (ASCII path for that read)
+    int tiled;               // layout of codes2: 0 row-major per read (codes2_word), 1 tile-major (tilecodes_word)
 };
 
 // One launch mode's tile: reads per tile, its LDS image, and the resident workgroups per CU the grid counts on.
@@ -138,12 +140,12 @@ extern "C" {
 int smx_launch_demux(const smx::DevPanel *P, int use64, int use_slots, const smx::TilePlan *plan, int grid,
                      const smx::DemuxBatch *batch, const smx::DemuxAux *aux);
 // primer prescan (smx_prescan.hip)
-size_t smx_prescan_lds_bytes(int S);
+size_t smx_prescan_lds_bytes(int S, int tile);
 int smx_launch_prescan(const smx::PreDesc *D, int mr, int nx, int grid_t, size_t lds_t, int grid_d, void *stream,
                        const uint8_t *d_windows, const int32_t *d_lens, uint32_t n_reads, int stride, unsigned *d_planes,
                        unsigned *d_out, unsigned *d_match, void *ev_mid, unsigned *d_codes2, uint8_t *d_naflag);
 int smx_prescan_set_lds_limit(size_t bytes);
-int smx_prescan_occupancy(int S, int mr, int nx, size_t lds_t, int *blocks_t, int *blocks_d);
+int smx_prescan_occupancy(int S, int mr, int nx, int tile, size_t lds_t, int *blocks_t, int *blocks_d);
 int smx_prescan_transpose_threads(int S);
 size_t smx_demux_lds_bytes(const smx::DevPanel *P, int use64, int R, int slots, int nitems);
 int smx_set_demux_lds_limit(int use64, size_t bytes);

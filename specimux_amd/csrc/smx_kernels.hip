@@ -1,9 +1,10 @@
 // smx_kernels.hip -- gfx950 (MI355X / CDNA4) kernels of the specimux hot path.
 //
-// A read batch takes three kernels on one stream.  The two prescan kernels (smx_prescan.hip) come first: the transpose
-// kernel turns the windows into bit-sliced 2-bit planes, row-major 2-bit codes and one "not plain ACGT" flag byte per read;
-// the primer DP kernel aligns every primer over the planes and writes one flag word per (primer, end, 16-column chunk,
-// read), plus match words per 32-read group.  Planes, codes, flag words and match words go through HBM.  The demux kernel
+// A read batch takes three kernels on one stream.  The two prescan kernels (smx_prescan.hip) come first: the first turns
+// the windows into 2-bit codes and one "not plain ACGT" flag byte per read -- tile-major codes alone for panels of at most
+// two primers (tile-codes kernel), bit-sliced 2-bit planes and row-major codes otherwise (transpose kernel); the primer DP
+// kernel aligns every primer over the tile codes or the planes and writes one flag word per (primer, end, 16-column chunk,
+// read), plus match words per 32-read group.  Codes, planes, flag words and match words go through HBM.  The demux kernel
 // of this file comes last: it decodes the flag words instead of scanning for primers itself, and redoes only the alignments
 // the prescan cannot take (reads flagged by the byte; every alignment when a panel has no prescan: primers over 31 nt,
 // SMX_NO_PRESCAN).  A many-primer panel runs it twice, a compact launch and the dense redo launch for its overflow tiles.
@@ -1833,28 +1834,63 @@ struct DemuxTile {
         };
         // (the default-flags kernels are only launched behind the prescan: their ASCII fast path is compiled out)
         if ((S & 15) == 0 && (sp || aux.codes2 != nullptr)) {
-            // behind the prescan: the transpose kernel has already turned every pure-ACGT window into 2-bit codes, row-major
-            // per read and in DP order (end A reverse-complemented): one dword per (read, end, 16-column chunk), the tile's
-            // dwords contiguous.  Four shift/mask/swap steps spell the dword out as 16 code bytes.  Reads the transpose kernel
-            // flagged (a window with anything but upper-case ACGT) and reads shorter than the window take the ASCII path.
+            // behind the prescan: its first kernel has already turned every pure-ACGT window into 2-bit codes in DP order (end A
+            // reverse-complemented): one dword per (read, end, 16-column chunk).  Four shift/mask/swap steps spell the dword out
+            // as 16 code bytes.  Reads whose flag byte that kernel set (a window with anything but upper-case ACGT, or a read
+            // shorter than the window) take the ASCII path.
             const int hc = S >> 4, per = 2 * hc;
-            const unsigned *c2 = aux.codes2 + (size_t)r0n * per;
-            const unsigned permagic = (unsigned)((0x100000000ull + (unsigned)per - 1) / (unsigned)per);
-            for (int ci = wid; ci < nrn * per; ci += nw) {
-                const unsigned z = c2[ci];
-                const int r = (int)__umulhi((unsigned)ci, permagic), rem = ci - __mul24(r, per);
-                const int end = rem >= hc ? 1 : 0, c = rem - (end ? hc : 0);
-                const unsigned flagged = aux.naflag[r0n + r];   // 1: shorter than the window, or not pure upper-case ACGT
-                if (!flagged) {
-                    unsigned *dst = (unsigned *)(codes + __mul24(r * 2 + end, CS)) + 4 * c;
+            // Two layouts of the code buffer (aux.tiled, uniform; the two-primer kernel is launched on tile codes only and has
+            // the row-major loop compiled out): row-major (codes2_word: the tile's R * per dwords are
+            // contiguous) or tile-major (tilecodes_word: per (end, chunk) a run of the tile's reads).
+            const bool tiled = SP == 2 ? true : aux.tiled != 0;
+            auto fast = [&](int r, int end, int c, unsigned z) {
+                unsigned *dst = (unsigned *)(codes + __mul24(r * 2 + end, CS)) + 4 * c;
 #pragma unroll
-                    for (int q = 0; q < 4; q++) {
-                        const unsigned x = (z >> (2 * q)) & 0x03030303u;       // A 0, C 1, T 2, G 3 ...
-                        dst[q] = x ^ ((x >> 1) & 0x01010101u);               // ... -> the kernels' A 0, C 1, G 2, T 3
+                for (int q = 0; q < 4; q++) {
+                    const unsigned x = (z >> (2 * q)) & 0x03030303u;       // A 0, C 1, T 2, G 3 ...
+                    dst[q] = x ^ ((x >> 1) & 0x01010101u);               // ... -> the kernels' A 0, C 1, G 2, T 3
+                }
+            };
+            // a flagged read (shorter than the window, or not pure upper-case ACGT): the same 16 window bytes from the ASCII
+            // buffer (any 16-byte piece of that end: all get visited)
+            auto slow = [&](int r, int end, int c) {
+                const uint4 v = *(const uint4 *)(windows + (size_t)(r0n + r) * stride + (end ? S : 0) + 16 * c);
+                encode_bytes(r, lens[r0n + r], (end ? S : 0) + 16 * c, v);
+            };
+            if (tiled && ((r0n | (uint32_t)nrn) & 3u) == 0) {
+                // tile-major, the tile's first read and read count multiples of four (every tile of a 64-read plan but a batch's
+                // last): item = (run = end * hc + chunk, four consecutive reads) -- one 16-byte load of their dwords and one dword
+                // of their flag bytes, both requested before either is looked at; 16 lanes cover a 256-byte run, and a 64-read
+                // tile is one item per lane: one memory round trip per tile where the dword-per-lane loop takes three to four.
+                const int nq = nrn >> 2;
+                for (int ci = wid; ci < per * 16; ci += nw) {
+                    const int run = ci >> 4, r = (ci & 15) * 4;
+                    if ((ci & 15) >= nq) continue;
+                    const int end = run >= hc ? 1 : 0, c = run - (end ? hc : 0);
+                    const uint4 z4 = *(const uint4 *)(aux.codes2 + tilecodes_word((size_t)(r0n + r), hc, end, c));
+                    const unsigned f4 = *(const unsigned *)(aux.naflag + r0n + r);
+                    if (!(f4 & 0xFFu)) fast(r, end, c, z4.x);
+                    if (!(f4 & 0xFF00u)) fast(r + 1, end, c, z4.y);
+                    if (!(f4 & 0xFF0000u)) fast(r + 2, end, c, z4.z);
+                    if (!(f4 & 0xFF000000u)) fast(r + 3, end, c, z4.w);
+                    if (f4) {   // (rare)
+#pragma nounroll
+                        for (int j = 0; j < 4; j++)
+                            if ((f4 >> (8 * j)) & 0xFFu) slow(r + j, end, c);
                     }
-                } else {   // the same 16 window bytes from the ASCII buffer (any 16-byte piece of that end: all get visited)
-                    const uint4 v = *(const uint4 *)(windows + (size_t)(r0n + r) * stride + (end ? S : 0) + 16 * c);
-                    encode_bytes(r, lens[r0n + r], (end ? S : 0) + 16 * c, v);
+                }
+            } else {
+                // a dword per lane.  Tile-major: item = (run, read slot of 64), a wave loads one run's 4 nrn contiguous bytes; the
+                // address is per read, as a tile may straddle two 1024-read DP tiles.
+                const unsigned permagic = (unsigned)((0x100000000ull + (unsigned)per - 1) / (unsigned)per);
+                for (int ci = wid; ci < (tiled ? per * 64 : nrn * per); ci += nw) {
+                    int r, rem;
+                    if (tiled) { r = ci & 63; rem = ci >> 6; if (r >= nrn) continue; }
+                    else { r = (int)__umulhi((unsigned)ci, permagic); rem = ci - __mul24(r, per); }
+                    const int end = rem >= hc ? 1 : 0, c = rem - (end ? hc : 0);
+                    const unsigned z = aux.codes2[tiled ? tilecodes_word((size_t)(r0n + r), hc, end, c) : (size_t)r0n * per + ci];
+                    if (!aux.naflag[r0n + r]) fast(r, end, c, z);
+                    else slow(r, end, c);
                 }
             }
         } else if (!sp && (S & 15) == 0) {
@@ -2150,7 +2186,7 @@ DemuxVariant demux_variant(const smx::DevPanel *P, int use64, int use_slots, int
                        P->preorient && P->minlen == -1 && P->maxlen == -1 && !P->dbg_phase && !(P->no_sp & 1);
     if (!flags) return v;
     if (P->S == 160 && R == 32 && cm == 1) v.sp = 3;                       // wide windows, compact 32-read tiles
-    else if (P->S == 80 && R == SMX_SP2_R && cm == 0 && P->NP == 2 && P->NPAIR == 1 && !(P->no_sp & 2)) v.sp = 2;
+    else if (P->S == 80 && R == SMX_SP2_R && cm == 0 && P->NP == 2 && P->NPAIR == 1 && !(P->no_sp & 2) && P->tile_codes) v.sp = 2;
     else if (P->S == 80 && R == 64) v.sp = 1;
     return v;
 }
@@ -2171,6 +2207,7 @@ extern "C" int smx_launch_demux(const smx::DevPanel *P, int use64, int use_slots
     if ((aux.nitems > 0 || aux.redo) && use64) return (int)hipErrorInvalidValue;   // (the prescan serves primers of <= 31 nt only)
     if (aux.nitems > 0 && !aux.chain) return (int)hipErrorInvalidValue;              // a compact launch needs its redo launch
     if (R > 64) return (int)hipErrorInvalidValue;
+    if (aux.codes2 && (aux.tiled != 0) != (P->tile_codes != 0)) return (int)hipErrorInvalidValue;   // (the variant is chosen by the panel's layout)
     // tile_counter = {tile queue head, overflow tiles, finished workgroups, extra records}: zero at allocation, re-armed
     // by the last workgroup of every launch (of the last launch of a chain).
     const void *fn = demux_fn(demux_variant(P, use64, use_slots, aux.nitems > 0 ? 1 : (aux.redo ? 2 : 0), R, aux.nitems,

@@ -6,7 +6,7 @@
 static Switches read_switches() {
     Switches w;
     auto on = [](const char *name) { return getenv(name) != nullptr; };
-    w.no_prescan = on("SMX_NO_PRESCAN"); w.no_bitslice = on("SMX_NO_BITSLICE"); w.no_table_sharing = on("SMX_NO_TABLE_SHARING");
+    w.no_prescan = on("SMX_NO_PRESCAN"); w.prescan_planes = on("SMX_PRESCAN_PLANES"); w.no_bitslice = on("SMX_NO_BITSLICE"); w.no_table_sharing = on("SMX_NO_TABLE_SHARING");
     if (const char *e = getenv("SMX_TEST_CAPS")) sscanf(e, "%d,%d", &w.cap_hits, &w.cap_ents);
     w.no_sp = (on("SMX_NO_SPECIALISE") ? 1 : 0) | (on("SMX_NO_SPECIALISE_NP") ? 2 : 0);
     w.no_lean_tails = on("SMX_NO_LEAN_TAILS"); w.force_slots = on("SMX_FORCE_SLOTS");
@@ -148,7 +148,12 @@ int smx_panel_create(const smx_panel_desc *d, smx_panel **out) {
         if (P->pre_ok) {
             P->pre_mr = maxm;
             P->pre_nx = P->pre.nsym - 4;
-            P->pre_lds = smx_prescan_lds_bytes(h.S);
+            // Text of the DP kernel: tile codes for panels of at most two primers, where the transpose kernel's bit transposes
+            // cost more than the one per (tile, primer, chunk) the DP kernel does instead.  With more primers every primer's
+            // wave would repeat the tile's transposes: those panels keep the planes.
+            // (every DP instantiation fits its registers on tile codes without scratch: profiles/ab_tile_codes.txt)
+            P->pre_tile = NP <= 2 && !sw.prescan_planes;
+            P->pre_lds = smx_prescan_lds_bytes(h.S, P->pre_tile);
             if (P->pre_lds > 160 * 1024) P->pre_ok = false;
         }
     }
@@ -198,7 +203,7 @@ int smx_panel_create(const smx_panel_desc *d, smx_panel **out) {
         h.n_bstab = nt;
     }
     h.bs_ok = bs_ok ? 1 : 0;
-    h.cap_hits = sw.cap_hits; h.cap_ents = sw.cap_ents; h.no_sp = sw.no_sp;   // the switches the kernel and its glue look at
+    h.cap_hits = sw.cap_hits; h.cap_ents = sw.cap_ents; h.no_sp = sw.no_sp; h.tile_codes = P->pre_tile ? 1 : 0;   // the switches the kernel and its glue look at
     h.bs_m = bm[0];
     if (h.pfmin != 0 && h.pfmin < 2) return fail(SMX_ERR_UNSUPPORTED, "prefilter min length %d < 2: disable the prefilter", h.pfmin);
     if (h.bmax + h.kidx > 200) return fail(SMX_ERR_UNSUPPORTED, "barcode length + k too large");
@@ -371,13 +376,16 @@ int ensure_device(smx_panel *P) {
         P->plan[m].blocks_per_cu = occ;
     }
     if (P->pre_ok) {
-        if (P->pre_lds > 64 * 1024 && smx_prescan_set_lds_limit(P->pre_lds) != 0)
+        // (the tile-codes kernel stages 2 * S / 16 rows of 1040 bytes: 34 KB at the largest search_len, 256 -- below the 64 KB that
+        // need no attribute; should that limit ever grow, this is where its attribute would be raised too)
+        static_assert((2 * (256 / 16) * smx::PRE_TS + smx::PRE_SUBG * 32) * 4 <= 64 * 1024, "tile-codes staging at search_len 256");
+        if (!P->pre_tile && P->pre_lds > 64 * 1024 && smx_prescan_set_lds_limit(P->pre_lds) != 0)
             return fail(SMX_ERR_DEVICE, "cannot raise the prescan kernel's dynamic LDS limit to %zu bytes", P->pre_lds);
         int occ_t = 0, occ_d = 0;
-        if (smx_prescan_occupancy(P->hp.S, P->pre_mr, P->pre_nx, P->pre_lds, &occ_t, &occ_d) != 0 || occ_t < 1 || occ_d < 1) { occ_t = 1; occ_d = 8; }
+        if (smx_prescan_occupancy(P->hp.S, P->pre_mr, P->pre_nx, P->pre_tile, P->pre_lds, &occ_t, &occ_d) != 0 || occ_t < 1 || occ_d < 1) { occ_t = 1; occ_d = 8; }
         P->pre_blocks_t = occ_t;
         P->pre_blocks_d = occ_d;
-        if (P->sw.debug) fprintf(stderr, "[smx] prescan: transpose %d workgroups/CU (lds %zu), DP %d waves/CU\n", occ_t, P->pre_lds, occ_d);
+        if (P->sw.debug) fprintf(stderr, "[smx] prescan (%s): transpose %d workgroups/CU (lds %zu), DP %d waves/CU\n", P->pre_tile ? "tile codes" : "planes", occ_t, P->pre_lds, occ_d);
     }
     if (P->sw.blocks_per_cu)
         for (TilePlan &t : P->plan) t.blocks_per_cu = P->sw.blocks_per_cu;
@@ -434,7 +442,7 @@ int smx_batch_run_device(const smx_panel *Pc, void *stream, const uint8_t *d_win
         npad = (n_reads + smx::PRE_TILE - 1) / smx::PRE_TILE * smx::PRE_TILE;
         const size_t need = (size_t)2 * P->hp.NP * (P->hp.S >> 4) * npad * sizeof(unsigned);
         DevBuf &pb = P->pre_recs[slot], &pp = P->pre_planes[slot], &pm = P->pre_match[slot], &ov = P->ovf[slot];
-        const size_t need_planes = (size_t)(npad / smx::PRE_TILE) * (P->hp.S >> 4) * 8 * 64 * 4 * sizeof(unsigned);
+        const size_t need_planes = P->pre_tile ? 0 : (size_t)(npad / smx::PRE_TILE) * (P->hp.S >> 4) * 8 * 64 * 4 * sizeof(unsigned);
         const size_t need_match = P->nitems > 0 ? (size_t)(npad / smx::PRE_TILE) * 2 * P->hp.NP * smx::PRE_G * sizeof(unsigned) : 0;
         const size_t need_ovf = compact ? ((size_t)n_reads / comp.R + 2) * sizeof(unsigned) : 0;
         DevBuf &pc = P->pre_codes[slot];
@@ -443,7 +451,7 @@ int smx_batch_run_device(const smx_panel *Pc, void *stream, const uint8_t *d_win
         if (need > pb.cap || need_planes > pp.cap || need_match > pm.cap || need_ovf > ov.cap || need_codes > pc.cap) {
             if (pb.p || pp.p) (void)hipStreamSynchronize((hipStream_t)stream);   // earlier launches on this stream still use them
             hipError_t pe = pb.ensure(need);
-            if (pe == hipSuccess) pe = pp.ensure(need_planes);
+            if (pe == hipSuccess && need_planes) pe = pp.ensure(need_planes);
             if (pe == hipSuccess) pe = pc.ensure(need_codes);
             if (pe == hipSuccess && need_match) pe = pm.ensure(need_match);
             if (pe == hipSuccess && need_ovf) pe = ov.ensure(need_ovf);
@@ -458,7 +466,7 @@ int smx_batch_run_device(const smx_panel *Pc, void *stream, const uint8_t *d_win
         d_codes2 = (const unsigned *)pc.p;
         d_naflag = (const uint8_t *)pc.p + codes_bytes;
         int pe = smx_launch_prescan(&P->pre, P->pre_mr, P->pre_nx, grid_t, P->pre_lds, grid_d, stream, d_windows, d_lens, n_reads,
-                                    P->hp.wstride, (unsigned *)pp.p, (unsigned *)pb.p, P->nitems > 0 ? (unsigned *)pm.p : nullptr,
+                                    P->hp.wstride, P->pre_tile ? nullptr : (unsigned *)pp.p, (unsigned *)pb.p, P->nitems > 0 ? (unsigned *)pm.p : nullptr,
                                     P->kev_on ? (void *)P->kev[1] : nullptr, (unsigned *)pc.p, (uint8_t *)pc.p + codes_bytes);
         if (pe != 0) return fail(SMX_ERR_DEVICE, "prescan kernel launch failed: %s", hipGetErrorString((hipError_t)pe));
         d_pre = (const unsigned *)pb.p;
@@ -478,11 +486,12 @@ int smx_batch_run_device(const smx_panel *Pc, void *stream, const uint8_t *d_win
     auto launch = [&](const TilePlan &t, int grid, const smx::DemuxAux &ax) {
         return smx_launch_demux(&P->hp, P->use64, use_slots, &t, grid, &batch, &ax);
     };
+    const int tiled = P->pre_tile ? 1 : 0;
     int e;
     if (compact) {
         // compact launch over all reads, then the dense launch over the reads of the tiles it put on the overflow list
         // (usually none: its workgroups find an empty list and leave)
-        e = launch(comp, grid_of(comp), {(const unsigned *)P->pre_match[slot].p, (unsigned *)P->ovf[slot].p, P->nitems, 0, comp.R, 1, d_codes2, d_naflag});
+        e = launch(comp, grid_of(comp), {(const unsigned *)P->pre_match[slot].p, (unsigned *)P->ovf[slot].p, P->nitems, 0, comp.R, 1, d_codes2, d_naflag, tiled});
         if (e == 0 && P->sw.debug_overflow) {   // diagnostic: how many compact tiles went on the overflow list
             unsigned n_ovf = 0;
             (void)hipMemcpyAsync(&n_ovf, tc + 1, sizeof(unsigned), hipMemcpyDeviceToHost, (hipStream_t)stream);
@@ -491,9 +500,9 @@ int smx_batch_run_device(const smx_panel *Pc, void *stream, const uint8_t *d_win
         }
         // the redo launch usually finds an empty list: one workgroup per CU is enough to start with (its workgroups
         // loop over the list), and an empty 256-workgroup launch costs less than an empty full-residency one
-        if (e == 0) e = launch(dense, std::min(grid_of(dense), P->n_cu), {nullptr, (unsigned *)P->ovf[slot].p, 0, 1, comp.R, 0, d_codes2, d_naflag});
+        if (e == 0) e = launch(dense, std::min(grid_of(dense), P->n_cu), {nullptr, (unsigned *)P->ovf[slot].p, 0, 1, comp.R, 0, d_codes2, d_naflag, tiled});
     } else {
-        e = launch(dense, grid_of(dense), {nullptr, nullptr, 0, 0, 0, 0, d_codes2, d_naflag});
+        e = launch(dense, grid_of(dense), {nullptr, nullptr, 0, 0, 0, 0, d_codes2, d_naflag, tiled});
     }
     if (e != 0) return fail(SMX_ERR_DEVICE, "demux kernel launch failed: %s", hipGetErrorString((hipError_t)e));
     if (P->kev_on) (void)hipEventRecord(P->kev[3], (hipStream_t)stream);

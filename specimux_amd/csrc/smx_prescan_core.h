@@ -13,7 +13,8 @@
 // This header is host/device code: the kernel (smx_prescan.hip) and the CPU unit test (tests/cpu/prescan_sim.cpp) run
 // the same functions; on the host a "lane" is a loop index and LDS is a plain array.
 //
-// Two kernels, both over tiles of PRE_G x 32 reads:
+// Two kernels, both over tiles of PRE_G x 32 reads (as written here for panels with more than two primers; for the others
+// the first kernel writes tile-major 2-bit codes only and the DP kernel does the bit transpose: see tilecodes_word):
 //   transpose kernel (one workgroup per tile, memory bound)
 //     phase 1  coalesced 16-byte loads of the windows; 16 ASCII bases -> one dword of 2-bit codes ((ch >> 1) & 3:
 //              A 0, C 1, T 2, G 3; 8 VALU per 16 bases), staged in LDS as 32 x 32 bit blocks [group][16-column chunk][read]
@@ -186,6 +187,40 @@ SMX_HD unsigned codes2_from_piece(unsigned z, int c, int CH, int *end, int *chun
     return z;
 }
 
+// Tile-major 2-bit codes ("tile codes"): the same dwords as codes2 (codes2_from_piece: end A reverse-complemented, DP column
+// order), laid out per DP tile of PRE_TILE reads as [tile][end][chunk][read in tile].  One buffer serves both consumers: a DP
+// lane (group g, end) finds the 32 dwords of a chunk -- 32 reads x 16 columns x 2 bits -- in 128 contiguous bytes and
+// bit-transposes them in registers (prescan_dp, TS = 1); a demux tile of R reads finds its dwords in 2 * CH runs of 4 R bytes.
+SMX_HD size_t tilecodes_word(size_t read, int CH, int end, int chunk) {
+    return (((read / PRE_TILE) * 2 + (size_t)end) * (size_t)CH + (size_t)chunk) * PRE_TILE + read % PRE_TILE;
+}
+// transpose32 of a lane's 32 dwords of one chunk gives word q = bit q of every read's dword: DP column t of the chunk, code bit
+// pl sits at word tile_bit(t, pl) (the inverse of pack_t / pack_pl)
+SMX_HD constexpr int tile_bit(int t, int pl) { return 8 * (t & 3) + 2 * (t >> 2) + pl; }
+// The tile-codes kernel stages a sub-tile's dwords in LDS as [run = end * CH + chunk][read in sub-tile], PRE_TS dwords per run:
+// a multiple of 4 (the copy-out reads 16 bytes per lane) and 4 (mod 32): a phase-1 wave writes (run, read) = (10 runs, ~7 reads)
+// to banks 4 run + read, at most two lanes per bank.
+constexpr int PRE_TS = PRE_SUBG * 32 + 4;
+static_assert(PRE_TS % 4 == 0 && PRE_TS % 32 == 4, "staging stride of the tile-codes kernel");
+// Phase 1 of the tile-codes kernel, one 16-byte piece (as prescan_store_piece): pack, bring into DP order, stage
+SMX_HD void prescan_stage_code(unsigned *stage, int read_in_sub, int c, int CH, unsigned w0, unsigned w1, unsigned w2, unsigned w3) {
+    int end, chunk;
+    const unsigned zz = codes2_from_piece(pack16(w0, w1, w2, w3), c, CH, &end, &chunk);
+    stage[(end * CH + chunk) * PRE_TS + read_in_sub] = zz;
+}
+// Copy-out of the tile-codes kernel: item i < 2 * CH * (PRE_SUBG * 8) moves four dwords (reads 4 (i % 64) .. + 3 of run i / 64) to
+// the sub-tile's place in the buffer; dst = the buffer at tilecodes_word(first read of the sub-tile, CH, 0, 0).  The 64 lanes of
+// a wave write one run's 1 KB.
+SMX_HD void prescan_copy_codes(const unsigned *stage, unsigned *dst, int i) {
+    constexpr int per = PRE_SUBG * 8;
+    const int run = i / per, r4 = (i % per) * 4;
+#if defined(__HIP_DEVICE_COMPILE__)
+    *(uint4 *)(dst + (size_t)run * PRE_TILE + r4) = *(const uint4 *)(stage + run * PRE_TS + r4);
+#else
+    for (int j = 0; j < 4; j++) dst[(size_t)run * PRE_TILE + r4 + j] = stage[run * PRE_TS + r4 + j];
+#endif
+}
+
 // ---- consumer side: one alignment from its CH chunk words (w[c * cstride], c = 0 .. CH-1).  Returns the best distance
 // (> k: no match) and, for a match, jstar, the number of optimal ends and the S-bit mask of optimal end columns
 // (mrow: MW = ceil(S / 32) words, bits below jstar cleared).
@@ -320,7 +355,11 @@ SMX_HD void prescan_write_occ(unsigned *sc, unsigned b0, unsigned b1, const unsi
 // the unrolled rows instead cost hundreds of register copies per column).
 // MT = 1: also count the new minima per read and write the match word (the compact demux tiles read it; other panels
 // skip the nine bit-ops per column).
-template <int MR, int NX, int MT = 1>
+// TS = text source.  0: `gpl` = the tile's planes (prescan_plane_word), fetched four columns at a time.  1: `gpl` = the tile's
+// tile codes (tilecodes_word): per chunk the lane loads its 32 dwords (8 x 16 bytes, one per column during the first half of
+// the chunk before -- seven columns and more ahead of their use, into registers that the flag words of the running chunk
+// have not taken yet), bit-transposes them in the chunk's last column, and takes column t's plane words from tile_bit.
+template <int MR, int NX, int MT = 1, int TS = 0>
 SMX_HD void prescan_dp(const unsigned *gpl, unsigned *scratch, int lane, int CH, const PreDesc &D, int p, unsigned *wout,
                        size_t cstride, unsigned *mout) {
     const int m = D.m[p], skip = MR - m;
@@ -349,6 +388,16 @@ SMX_HD void prescan_dp(const unsigned *gpl, unsigned *scratch, int lane, int CH,
     // plane words of the current and the next four-column group (8 words each: column t of a group = words 2t, 2t + 1),
     // fetched one group ahead
     unsigned pw[2][8];
+    unsigned tc[32], tn[32];   // TS = 1: this chunk's plane words (after the transpose), the next chunk's dwords
+    auto tfetch = [&](int chunk, int q, unsigned (&dst)[32]) {   // piece q (16 bytes) of the lane's 32 dwords of `chunk`
+        const size_t at = ((size_t)((lane & 1) * CH + chunk)) * PRE_TILE + (size_t)(lane >> 1) * 32 + 4 * q;
+#if defined(__HIP_DEVICE_COMPILE__)
+        const uint4 u = *(const uint4 *)(gpl + at);
+        dst[4 * q] = u.x; dst[4 * q + 1] = u.y; dst[4 * q + 2] = u.z; dst[4 * q + 3] = u.w;
+#else
+        for (int j = 0; j < 4; j++) dst[4 * q + j] = gpl[at + j];
+#endif
+    };
     auto fetch = [&](int grp, unsigned (&dst)[8]) {   // grp = chunk * 4 + group in chunk; two 16-byte loads per lane
         const int chunk = grp >> 2, q = (grp & 3) * 2;
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -359,8 +408,17 @@ SMX_HD void prescan_dp(const unsigned *gpl, unsigned *scratch, int lane, int CH,
         for (int j = 0; j < 8; j++) dst[j] = gpl[prescan_plane_word(chunk, lane, 4 * q + j)];
 #endif
     };
-    fetch(0, pw[0]);
-    prescan_write_occ<NX>(sc0, pw[0][0], pw[0][1], xm);   // prologue: column 0
+    if (TS) {
+#pragma unroll
+        for (int q = 0; q < 8; q++) tfetch(0, q, tc);
+#pragma unroll
+        for (int i = 0; i < 32; i++) tn[i] = 0u;
+        transpose32(tc);
+        prescan_write_occ<NX>(sc0, tc[tile_bit(0, 0)], tc[tile_bit(0, 1)], xm);   // prologue: column 0
+    } else {
+        fetch(0, pw[0]);
+        prescan_write_occ<NX>(sc0, pw[0][0], pw[0][1], xm);   // prologue: column 0
+    }
     unsigned eqb[2][8];   // Eq words of the current / next row group
 #pragma unroll
     for (int u = 0; u < 8; u++) eqb[0][u] = scratch[aoff[u]];   // column 0, group 0 (16 * NG columns per chunk: even parity)
@@ -369,10 +427,18 @@ SMX_HD void prescan_dp(const unsigned *gpl, unsigned *scratch, int lane, int CH,
 #pragma unroll
         for (int t = 0; t < 16; t++) {
             const int gq = t >> 2, tq = t & 3, cur = gq & 1;   // four groups per chunk: the parity restarts with every chunk
-            if (tq == 0 && (ch * 4 + gq + 1 < CH * 4)) fetch(ch * 4 + gq + 1, pw[cur ^ 1]);
             // next column's occurrence words go to the other scratch buffer while this column's are read
-            if (tq < 3) prescan_write_occ<NX>((t & 1) ? sc0 : sc1, pw[cur][2 * tq + 2], pw[cur][2 * tq + 3], xm);
-            else if (ch * 4 + gq + 1 < CH * 4) prescan_write_occ<NX>((t & 1) ? sc0 : sc1, pw[cur ^ 1][0], pw[cur ^ 1][1], xm);
+            unsigned *scw = (t & 1) ? sc0 : sc1;
+            if (TS) {
+                if (t < 8 && ch + 1 < CH) tfetch(ch + 1, t, tn);
+                if (t == 15 && ch + 1 < CH) transpose32(tn);
+                if (t < 15) prescan_write_occ<NX>(scw, tc[tile_bit((t + 1) & 15, 0)], tc[tile_bit((t + 1) & 15, 1)], xm);
+                else if (ch + 1 < CH) prescan_write_occ<NX>(scw, tn[tile_bit(0, 0)], tn[tile_bit(0, 1)], xm);
+            } else {
+                if (tq == 0 && (ch * 4 + gq + 1 < CH * 4)) fetch(ch * 4 + gq + 1, pw[cur ^ 1]);
+                if (tq < 3) prescan_write_occ<NX>(scw, pw[cur][2 * tq + 2], pw[cur][2 * tq + 3], xm);
+                else if (ch * 4 + gq + 1 < CH * 4) prescan_write_occ<NX>(scw, pw[cur ^ 1][0], pw[cur ^ 1][1], xm);
+            }
             const unsigned *sc = ((t & 1) ? scratch + bufw : scratch);
             unsigned Ph = 0u, Mh = 0u;   // HW: the top row is free
             // rows in groups of eight.  The Eq words of the NEXT group (of the next column after the last group: its
@@ -444,6 +510,10 @@ SMX_HD void prescan_dp(const unsigned *gpl, unsigned *scratch, int lane, int CH,
 #else
         for (int r = 0; r < 32; r++) wout[(size_t)ch * cstride + r] = fl[r];
 #endif
+        if (TS) {
+#pragma unroll
+            for (int i = 0; i < 32; i++) tc[i] = tn[i];
+        }
     }
     // match word: bit r = read r reaches distance <= k somewhere in the S columns  <=>  new minima >= m - k (bit-sliced
     // compare against the uniform threshold).  For a read shorter than the window this is a superset of "matches within

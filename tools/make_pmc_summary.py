@@ -8,7 +8,7 @@ import sys
 
 root = sys.argv[1]
 names = {"demux_kernel": "summary.json", "prescan_transpose_kernel": "summary_prescan_transpose.json",
-         "prescan_dp_kernel": "summary_prescan_dp.json"}
+         "prescan_tilecodes_kernel": "summary_prescan_tilecodes.json", "prescan_dp_kernel": "summary_prescan_dp.json"}
 READS = int(os.environ.get("PROF_READS", "765000"))
 BYTES_PER_READ = int(os.environ.get("PROF_BYTES_PER_READ", "196"))   # 2 * search_len + 4 + 32: 196 at -l 80, 356 at -l 160
 out = {"root": root, "reads_per_launch": READS, "kernels": {}}
@@ -20,6 +20,8 @@ for k, f in names.items():
         continue
     d = json.load(open(path))
     c = d.get("counters_per_launch", {})
+    if "kernel_trace" not in d and not c:   # the kernel is not part of this build's step (planes / tile codes)
+        continue
     entry = {"avg_ns": d.get("kernel_trace", {}).get("avg_ns"), "dispatch": d.get("dispatch"),
              "counters_per_launch": c, "hbm": d.get("hbm")}
     out["kernels"][k] = entry

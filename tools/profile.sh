@@ -19,6 +19,7 @@ rocprofv3 --pmc SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_WAIT_INST_LDS
 rocprofv3 --pmc GRBM_GUI_ACTIVE TCC_HIT_sum TCC_MISS_sum --output-format csv -d "$OUT/misc" -- $BENCH > "$OUT/misc.log" 2>&1 || true
 python3 tools/summarize_prof.py "$OUT" demux_kernel > "$OUT/summary.json"
 python3 tools/summarize_prof.py "$OUT" prescan_transpose_kernel > "$OUT/summary_prescan_transpose.json"
+python3 tools/summarize_prof.py "$OUT" prescan_tilecodes_kernel > "$OUT/summary_prescan_tilecodes.json"
 python3 tools/summarize_prof.py "$OUT" prescan_dp_kernel > "$OUT/summary_prescan_dp.json"
 python3 tools/make_pmc_summary.py "$OUT" > "$OUT/pmc_summary.json"
 cat "$OUT/pmc_summary.json"

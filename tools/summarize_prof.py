@@ -13,7 +13,7 @@ root = sys.argv[1]
 KERNEL = sys.argv[2] if len(sys.argv) > 2 else "demux_kernel"   # kernel name substring (prescan_kernel for the primer prescan)
 
 
-STEP_KERNEL = "prescan_transpose_kernel"   # launched exactly once per step: its dispatch count = the number of steps
+STEP_KERNELS = ("prescan_transpose_kernel", "prescan_tilecodes_kernel")   # one of them is launched exactly once per step: its dispatch count = the number of steps
 READS = int(os.environ.get("PROF_READS", "765000"))
 BYTES_PER_READ = int(os.environ.get("PROF_BYTES_PER_READ", "196"))   # 2 * search_len + 4 + 32: 196 at -l 80, 356 at -l 160
 
@@ -26,7 +26,7 @@ def pmc(sub):
     for path in glob.glob(os.path.join(root, sub, "**", "*counter_collection.csv"), recursive=True):
         with open(path) as fh:
             for row in csv.DictReader(fh):
-                if STEP_KERNEL in row.get("Kernel_Name", ""):
+                if any(k in row.get("Kernel_Name", "") for k in STEP_KERNELS):
                     steps.add(row["Dispatch_Id"])
                 if KERNEL not in row.get("Kernel_Name", ""):
                     continue
@@ -39,7 +39,7 @@ out = {"root": root}
 for path in glob.glob(os.path.join(root, "kt", "**", "*kernel_stats.csv"), recursive=True):
     with open(path) as fh:
         rows = list(csv.DictReader(fh))
-    steps = sum(int(r["Calls"]) for r in rows if STEP_KERNEL in r["Name"])
+    steps = sum(int(r["Calls"]) for r in rows if any(k in r["Name"] for k in STEP_KERNELS))
     mine = [r for r in rows if KERNEL in r["Name"]]
     if mine:   # per step: the durations of all matching launches of a step added up
         calls = sum(int(r["Calls"]) for r in mine)
