@@ -115,7 +115,7 @@ struct {
     DevBuf jobs_out;    // the jobs, then the output
 } g_mine;
 
-// per query: LDS bytes of its Peq table ((distinct bytes + 1) x padded words) and the register class of its per-lane state
+// per query: LDS bytes of its Peq table and the state class of its per-lane state (smx_chunk_plan.h)
 int mine_queries(const char *queries, const uint64_t *qoff, uint32_t n_queries, std::vector<size_t> *qlds_out,
                  std::vector<int> *qclass_out, bool allow_empty = false) {
     std::vector<size_t> &qlds = *qlds_out;
@@ -126,40 +126,20 @@ int mine_queries(const char *queries, const uint64_t *qoff, uint32_t n_queries, 
         if (qoff[q + 1] < qoff[q] || (qoff[q + 1] == qoff[q] && !allow_empty)) return fail(SMX_ERR_ARG, "query %u is empty", q);
         const uint64_t m = qoff[q + 1] - qoff[q];
         if (m > (uint64_t)INT32_MAX) return fail(SMX_ERR_UNSUPPORTED, "query %u: length %llu", q, (unsigned long long)m);
-        bool seen[256] = {false};
-        int rows = 0;
-        for (uint64_t i = qoff[q]; i < qoff[q + 1]; i++) {
-            const unsigned char c = (unsigned char)queries[i];
-            if (!seen[c]) { seen[c] = true; rows++; }
-        }
-        const size_t W = (size_t)((m + 63) / 64), Wp = W | 1;
-        qlds[q] = (MINE_LDS_HEAD + (size_t)(rows + 1) * Wp) * 8;
-        if (qlds[q] > SMX_LDS_POOL)
-            return fail(SMX_ERR_UNSUPPORTED, "query %u: %d distinct bytes x %zu words do not fit the LDS (%zu > %zu bytes)", q,
-                        rows, W, qlds[q], (size_t)SMX_LDS_POOL);
-        qclass[q] = W <= 1 ? 1 : W <= 2 ? 2 : W <= 4 ? 3 : W <= 8 ? 4 : W <= 16 ? 5 : 0;
+        const smx::ChunkTable T = smx::chunk_table(queries + qoff[q], m);
+        if (!T.fits()) return fail(SMX_ERR_UNSUPPORTED, "%s", T.refusal("query " + std::to_string(q) + ": ").c_str());
+        qlds[q] = T.lds;
+        qclass[q] = T.cls;
     }
     return SMX_OK;
 }
 
-// targets: 16-byte aligned copies, 16 bytes of slack at the end (the kernel loads 16 bytes at a time)
-int mine_targets(const char *targets, const uint64_t *toff, uint32_t n_targets, std::vector<uint64_t> *tdoff_out,
-                 std::vector<int32_t> *tlen_out, std::vector<unsigned char> *tpad) {
-    std::vector<uint64_t> &tdoff = *tdoff_out;
-    std::vector<int32_t> &tlen = *tlen_out;
-    tdoff.assign(n_targets, 0);
-    tlen.assign(n_targets, 0);
-    uint64_t tbytes = 0;
-    for (uint32_t t = 0; t < n_targets; t++) {
-        if (toff[t + 1] < toff[t] || toff[t + 1] - toff[t] > (uint64_t)INT32_MAX) return fail(SMX_ERR_ARG, "target %u: bad offsets", t);
-        tdoff[t] = tbytes;
-        tlen[t] = (int32_t)(toff[t + 1] - toff[t]);
-        tbytes += ((uint64_t)tlen[t] + 15) & ~(uint64_t)15;
-    }
-    tbytes += 16;
-    tpad->assign(tbytes, 0);
-    for (uint32_t t = 0; t < n_targets; t++) memcpy(tpad->data() + tdoff[t], targets + toff[t], (size_t)tlen[t]);
-    return SMX_OK;
+// the padded copy of the targets (smx_chunk_plan.h), failing the call's way
+int mine_targets(const char *targets, const uint64_t *toff, uint32_t n_targets, std::vector<uint64_t> *tdoff,
+                 std::vector<int32_t> *tlen, std::vector<unsigned char> *tpad) {
+    std::string why;
+    const int rc = smx::mine_targets(targets, toff, n_targets, tdoff, tlen, tpad, &why);
+    return rc == SMX_OK ? SMX_OK : fail(rc, "%s", why.c_str());
 }
 
 // One smx_mine_* call.  distances: job j's nq x nt distances at out[sum over earlier jobs of nq * nt] (int32); else
@@ -224,10 +204,12 @@ int mine_call(bool distances, const char *queries, const uint64_t *qoff, uint32_
     // Peq build of a query's run of chunks are paid once.  Measured on MI355X: one chunk per
     // workgroup loses 1.5x on runs of cheap (decoy) chunks, runs of 8 lose ~11 % to balance on costly chunks
     constexpr uint64_t MINE_BLOCK_CHUNKS = 8;
-    const uint64_t grid_cap = (uint64_t)INT32_MAX;
-    // the generic class keeps its per-lane state in a global slice per workgroup: bound its grid to ~256 MiB of it
-    const size_t slice = (size_t)3 * words_max0 * MINE_THREADS * 8;
-    const uint64_t grid0_cap = std::max<size_t>(1, ((size_t)256 << 20) / std::max<size_t>(slice, 1));
+    smx::ChunkGrid G[6];
+    uint32_t n_pairs[6];
+    for (int c = 0; c < 6; c++) {
+        n_pairs[c] = (uint32_t)pairs[c].size();
+        G[c] = smx::chunk_class_grid(c, chunks[c], MINE_BLOCK_CHUNKS, words_max0);
+    }
     auto &W = g_mine;
     std::vector<smx::MinePair> all_pairs;   // class after class
     for (int c = 0; c < 6; c++) all_pairs.insert(all_pairs.end(), pairs[c].begin(), pairs[c].end());
@@ -239,28 +221,18 @@ int mine_call(bool distances, const char *queries, const uint64_t *qoff, uint32_
     HIP_TRY(W.tlen.upload(tlen));
     HIP_TRY(W.pairs.upload(all_pairs));
     HIP_TRY(W.chunk_start.upload(chunk_start));
-    if (!pairs[0].empty()) HIP_TRY(W.scratch.ensure((size_t)std::min(chunks[0], grid0_cap) * slice));
+    if (n_pairs[0]) HIP_TRY(W.scratch.ensure((size_t)smx::chunk_scratch_words(G[0].grid, words_max0) * 8));
     HIP_TRY(W.jobs_out.upload(djobs.data(), jobs_bytes, out_bytes));
     void *d_out = W.jobs_out.as<char>() + jobs_bytes;
     if (!distances) HIP_TRY(hipMemset(d_out, 0, out_bytes));       // +0.0: "no pair counts"
     KernelTimer timer;
     if (kernel_ms) HIP_TRY(timer.start());
-    static const int kWords[6] = {0, 1, 2, 4, 8, 16};
-    size_t pat = 0, cat = 0;
-    int e = 0;
-    for (int c = 0; c < 6 && e == 0; c++) {
-        const uint32_t n = (uint32_t)pairs[c].size();
-        if (!n) continue;
-        const uint64_t cap = c == 0 ? std::min(grid_cap, grid0_cap) : grid_cap;
-        const uint64_t per_block = std::max(MINE_BLOCK_CHUNKS, (chunks[c] + cap - 1) / cap);
-        const uint64_t grid = (chunks[c] + per_block - 1) / per_block;
-        e = smx_launch_mine(nullptr, kWords[c], distances, W.queries.as<unsigned char>(), W.qoff.as<uint64_t>(),
-                            W.targets.as<unsigned char>(), W.tdoff.as<uint64_t>(), W.tlen.as<int32_t>(),
-                            W.pairs.as<smx::MinePair>() + pat, W.chunk_start.as<uint64_t>() + cat, n, W.jobs_out.p, (int)grid,
-                            per_block, lds_max[c], d_out, W.scratch.as<unsigned long long>(), words_max0);
-        pat += n;
-        cat += (size_t)n + 1;
-    }
+    const int e = smx::chunk_for_each_class(n_pairs, [&](int c, int wr, uint32_t n, size_t pat, size_t cat) {
+        return smx_launch_mine(nullptr, wr, distances, W.queries.as<unsigned char>(), W.qoff.as<uint64_t>(),
+                               W.targets.as<unsigned char>(), W.tdoff.as<uint64_t>(), W.tlen.as<int32_t>(),
+                               W.pairs.as<smx::MinePair>() + pat, W.chunk_start.as<uint64_t>() + cat, n, W.jobs_out.p,
+                               (int)G[c].grid, G[c].per_block, lds_max[c], d_out, W.scratch.as<unsigned long long>(), words_max0);
+    });
     if (e != 0) return fail(SMX_ERR_DEVICE, "mining kernel launch failed: %s", hipGetErrorString((hipError_t)e));
     if (kernel_ms) HIP_TRY(timer.stop(kernel_ms));
     HIP_TRY(hipDeviceSynchronize());
@@ -355,9 +327,12 @@ int pairs_call(bool distances, const char *reads, const uint64_t *roff, uint32_t
     }
     // runs of chunks per workgroup and the generic class's grid bound: as mine_call
     constexpr uint64_t PAIRS_BLOCK_CHUNKS = 8;
-    const uint64_t grid_cap = (uint64_t)INT32_MAX;
-    const size_t slice = (size_t)3 * words_max0 * MINE_THREADS * 8;
-    const uint64_t grid0_cap = std::max<size_t>(1, ((size_t)256 << 20) / std::max<size_t>(slice, 1));
+    smx::ChunkGrid G[6];
+    uint32_t n_class[6];
+    for (int c = 0; c < 6; c++) {
+        n_class[c] = (uint32_t)rows[c].size();
+        G[c] = smx::chunk_class_grid(c, chunks[c], PAIRS_BLOCK_CHUNKS, words_max0);
+    }
     auto &W = g_pairs;
     std::vector<smx::PairsRow> all_rows;          // class after class
     for (int c = 0; c < 6; c++) all_rows.insert(all_rows.end(), rows[c].begin(), rows[c].end());
@@ -368,28 +343,18 @@ int pairs_call(bool distances, const char *reads, const uint64_t *roff, uint32_t
     HIP_TRY(W.k.upload(k, (size_t)n_reads * 4));
     HIP_TRY(W.rows.upload(all_rows));
     HIP_TRY(W.chunk_start.upload(chunk_start));
-    if (!rows[0].empty()) HIP_TRY(W.scratch.ensure((size_t)std::min(chunks[0], grid0_cap) * slice));
+    if (n_class[0]) HIP_TRY(W.scratch.ensure((size_t)smx::chunk_scratch_words(G[0].grid, words_max0) * 8));
     HIP_TRY(W.jobs_out.upload(djobs.data(), n_jobs * sizeof(smx::PairsJobDev), jobs_bytes - n_jobs * sizeof(smx::PairsJobDev) + out_bytes));
     void *d_out = W.jobs_out.as<char>() + jobs_bytes;
     if (!distances) HIP_TRY(hipMemset(d_out, 0, out_bytes));
     KernelTimer timer;
     if (kernel_ms) HIP_TRY(timer.start());
-    static const int kWords[6] = {0, 1, 2, 4, 8, 16};
-    size_t rat = 0, cat = 0;
-    int e = 0;
-    for (int c = 0; c < 6 && e == 0; c++) {
-        const uint32_t n = (uint32_t)rows[c].size();
-        if (!n) continue;
-        const uint64_t cap = c == 0 ? std::min(grid_cap, grid0_cap) : grid_cap;
-        const uint64_t per_block = std::max(PAIRS_BLOCK_CHUNKS, (chunks[c] + cap - 1) / cap);
-        const uint64_t grid = (chunks[c] + per_block - 1) / per_block;
-        e = smx_launch_pairs(nullptr, kWords[c], distances, W.reads.as<unsigned char>(), W.doff.as<uint64_t>(),
-                             W.len.as<int32_t>(), W.k.as<int32_t>(), W.rows.as<smx::PairsRow>() + rat,
-                             W.chunk_start.as<uint64_t>() + cat, n, W.jobs_out.p, (int)grid, per_block, lds_max[c], d_out,
-                             W.scratch.as<unsigned long long>(), words_max0);
-        rat += n;
-        cat += (size_t)n + 1;
-    }
+    const int e = smx::chunk_for_each_class(n_class, [&](int c, int wr, uint32_t n, size_t rat, size_t cat) {
+        return smx_launch_pairs(nullptr, wr, distances, W.reads.as<unsigned char>(), W.doff.as<uint64_t>(),
+                                W.len.as<int32_t>(), W.k.as<int32_t>(), W.rows.as<smx::PairsRow>() + rat,
+                                W.chunk_start.as<uint64_t>() + cat, n, W.jobs_out.p, (int)G[c].grid, G[c].per_block, lds_max[c],
+                                d_out, W.scratch.as<unsigned long long>(), words_max0);
+    });
     if (e != 0) return fail(SMX_ERR_DEVICE, "pairs kernel launch failed: %s", hipGetErrorString((hipError_t)e));
     if (kernel_ms) HIP_TRY(timer.stop(kernel_ms));
     HIP_TRY(hipDeviceSynchronize());
@@ -483,20 +448,15 @@ int nearest_call(bool distances, const char *seqs, const uint64_t *off, uint32_t
     unsigned long long *d_own = W.out.as<unsigned long long>(), *d_other = d_own + (distances ? 0 : P.n_best);
     KernelTimer timer;
     if (kernel_ms) HIP_TRY(timer.start());
-    static const int kWords[6] = {0, 1, 2, 4, 8, 16};
-    size_t qat = 0, rat = 0, cat = 0;
-    int e = 0;
-    for (int c = 0; c < 6 && e == 0; c++) {
-        const uint32_t n = P.n_runs[c];
-        if (n)
-            e = smx_launch_nearest(nullptr, kWords[c], distances, W.seqs.as<unsigned char>(), W.doff.as<uint64_t>(),
-                                   W.len.as<int32_t>(), W.k.as<int32_t>(), W.group.as<uint32_t>(), W.refs.as<uint32_t>() + qat,
-                                   W.runs.as<smx::NearestRun>() + rat, W.chunk_start.as<uint64_t>() + cat, n, W.jobs.p,
-                                   (int)P.grid[c], P.per_block[c], P.lds_max[c], d_own, d_other, W.out.as<int32_t>(),
-                                   W.scratch.as<unsigned long long>(), P.words_max0);
-        qat += P.n_refs[c];
-        if (n) { rat += n; cat += (size_t)n + 1; }
-    }
+    size_t ref_at[6] = {0, 0, 0, 0, 0, 0};             // every class's own ref list, one after the other
+    for (int c = 1; c < 6; c++) ref_at[c] = ref_at[c - 1] + P.n_refs[c - 1];
+    const int e = smx::chunk_for_each_class(P.n_runs, [&](int c, int wr, uint32_t n, size_t rat, size_t cat) {
+        return smx_launch_nearest(nullptr, wr, distances, W.seqs.as<unsigned char>(), W.doff.as<uint64_t>(),
+                                  W.len.as<int32_t>(), W.k.as<int32_t>(), W.group.as<uint32_t>(), W.refs.as<uint32_t>() + ref_at[c],
+                                  W.runs.as<smx::NearestRun>() + rat, W.chunk_start.as<uint64_t>() + cat, n, W.jobs.p,
+                                  (int)P.grid[c], P.per_block[c], P.lds_max[c], d_own, d_other, W.out.as<int32_t>(),
+                                  W.scratch.as<unsigned long long>(), P.words_max0);
+    });
     if (e != 0) return fail(SMX_ERR_DEVICE, "nearest kernel launch failed: %s", hipGetErrorString((hipError_t)e));
     if (kernel_ms) HIP_TRY(timer.stop(kernel_ms));
     HIP_TRY(hipDeviceSynchronize());
@@ -569,20 +529,13 @@ int hits_call(bool distances, const char *seqs, const uint64_t *off, uint32_t n_
     HIP_TRY(hipMemset(W.out.p, 0xff, out_bytes));
     KernelTimer timer;
     if (kernel_ms) HIP_TRY(timer.start());
-    static const int kWords[6] = {0, 1, 2, 4, 8, 16};
-    size_t rat = 0, cat = 0;
-    int e = 0;
-    for (int c = 0; c < 6 && e == 0; c++) {
-        const uint32_t n = P.n_recs[c];
-        if (!n) continue;
-        e = smx_launch_hits(nullptr, kWords[c], distances, W.seqs.as<unsigned char>(), W.doff.as<uint64_t>(),
-                            W.len.as<int32_t>(), W.k.as<int32_t>(), W.ord.as<uint32_t>(), W.recs.as<smx::HitsRec>() + rat,
-                            W.chunk_start.as<uint64_t>() + cat, n, W.jobs.p, (int)P.grid[c], P.per_block[c], P.lds_max[c],
-                            (int)K, W.out.as<unsigned long long>(), W.out.as<int32_t>(), W.scratch.as<unsigned long long>(),
-                            P.words_max0);
-        rat += n;
-        cat += (size_t)n + 1;
-    }
+    const int e = smx::chunk_for_each_class(P.n_recs, [&](int c, int wr, uint32_t n, size_t rat, size_t cat) {
+        return smx_launch_hits(nullptr, wr, distances, W.seqs.as<unsigned char>(), W.doff.as<uint64_t>(),
+                               W.len.as<int32_t>(), W.k.as<int32_t>(), W.ord.as<uint32_t>(), W.recs.as<smx::HitsRec>() + rat,
+                               W.chunk_start.as<uint64_t>() + cat, n, W.jobs.p, (int)P.grid[c], P.per_block[c], P.lds_max[c],
+                               (int)K, W.out.as<unsigned long long>(), W.out.as<int32_t>(), W.scratch.as<unsigned long long>(),
+                               P.words_max0);
+    });
     if (e != 0) return fail(SMX_ERR_DEVICE, "hits kernel launch failed: %s", hipGetErrorString((hipError_t)e));
     if (kernel_ms) HIP_TRY(timer.stop(kernel_ms));
     HIP_TRY(hipDeviceSynchronize());
@@ -646,36 +599,28 @@ int cons_call(const char *reads, const uint64_t *roff, uint32_t n_reads, const i
     HIP_TRY(W.dist.ensure((size_t)P.n_dist * 4));
     // runs of chunks per workgroup only where the history bounds the grid: a chunk is 128 alignments with traceback,
     // and a call has few of them by the standards of the device
-    uint64_t grids[6], per_block[6], grid_max = 0;
+    smx::ChunkGrid G[6];
+    uint64_t grid_max = 0;
     for (int c = 0; c < 6; c++) {
-        const uint64_t cap = std::min<uint64_t>(P.grid_cap, (uint64_t)INT32_MAX);
-        per_block[c] = std::max<uint64_t>(1, (P.chunks[c] + cap - 1) / cap);
-        grids[c] = (P.chunks[c] + per_block[c] - 1) / per_block[c];
-        grid_max = std::max(grid_max, grids[c]);
+        G[c] = smx::chunk_grid(P.chunks[c], 1, P.grid_cap);
+        grid_max = std::max(grid_max, G[c].grid);
     }
     HIP_TRY(W.hist_pm.ensure((size_t)(grid_max * P.hist_slice * MINE_THREADS * sizeof(smx::cons_pm))));
     HIP_TRY(W.hist_s.ensure((size_t)(grid_max * P.hist_slice * MINE_THREADS * sizeof(int))));
-    if (P.n_align[0]) HIP_TRY(W.scratch.ensure((size_t)grids[0] * 3 * P.words_max0 * MINE_THREADS * 8));
+    if (P.n_align[0]) HIP_TRY(W.scratch.ensure((size_t)smx::chunk_scratch_words(G[0].grid, P.words_max0) * 8));
     if (!pileup) {
         HIP_TRY(W.votes.ensure((size_t)P.votes_words * 4));
         HIP_TRY(W.aligned.ensure((size_t)n_jobs * 4));
     }
     KernelTimer timer;
     if (kernel_ms) HIP_TRY(timer.start());
-    static const int kWords[6] = {0, 1, 2, 4, 8, 16};
-    size_t jat = 0, cat = 0;
-    int e = 0;
-    for (int c = 0; c < 6 && e == 0; c++) {
-        const uint32_t n = P.n_align[c];
-        if (!n) continue;
-        e = smx_launch_cons_align(nullptr, kWords[c], W.reads.as<unsigned char>(), W.doff.as<uint64_t>(), W.len.as<int32_t>(),
-                                  W.k.as<int32_t>(), W.align.as<smx::ConsJobDev>() + jat, W.chunk_start.as<uint64_t>() + cat, n,
-                                  (int)grids[c], per_block[c], P.lds_max[c], W.rows.as<uint32_t>(), W.dist.as<int32_t>(),
-                                  W.hist_pm.p, W.hist_s.as<int>(), P.hist_slice, W.scratch.as<unsigned long long>(),
-                                  P.words_max0);
-        jat += n;
-        cat += (size_t)n + 1;
-    }
+    int e = smx::chunk_for_each_class(P.n_align, [&](int c, int wr, uint32_t n, size_t jat, size_t cat) {
+        return smx_launch_cons_align(nullptr, wr, W.reads.as<unsigned char>(), W.doff.as<uint64_t>(), W.len.as<int32_t>(),
+                                     W.k.as<int32_t>(), W.align.as<smx::ConsJobDev>() + jat, W.chunk_start.as<uint64_t>() + cat,
+                                     n, (int)G[c].grid, G[c].per_block, P.lds_max[c], W.rows.as<uint32_t>(),
+                                     W.dist.as<int32_t>(), W.hist_pm.p, W.hist_s.as<int>(), P.hist_slice,
+                                     W.scratch.as<unsigned long long>(), P.words_max0);
+    });
     if (e == 0 && !pileup)
         e = smx_launch_cons_vote(nullptr, W.len.as<int32_t>(), W.jobs.p, n_jobs, P.max_words, W.rows.as<uint32_t>(),
                                  W.dist.as<int32_t>(), W.votes.as<uint32_t>(), W.aligned.as<uint32_t>());

@@ -28,34 +28,21 @@ __global__ __launch_bounds__(MINE_THREADS) void cons_align_kernel(const unsigned
                                                                   cons_pm *hist_pm, int *hist_s, uint64_t hist_slice,
                                                                   u64 *scratch, int scratch_words) {
     extern __shared__ u64 lds[];
-    unsigned short *rowmap = reinterpret_cast<unsigned short *>(lds);     // 512 B
-    unsigned *present = reinterpret_cast<unsigned *>(lds + 64);           // 1 KiB
-    u64 *peq = lds + MINE_LDS_HEAD;
-    const uint64_t n_chunks = chunk_start[n_jobs];
-    const uint64_t lo = (uint64_t)blockIdx.x * per_block;
-    const uint64_t hi = lo + per_block < n_chunks ? lo + per_block : n_chunks;
-    // the job whose chunk range holds lo: pairs_kernel's 64-way search
-    uint32_t p = 0, cnt = n_jobs;
-    while (cnt > 1) {
-        const uint32_t step = (cnt + 63) / 64, idx = p + (threadIdx.x & 63) * step;
-        const bool le = idx < p + cnt && chunk_start[idx] <= lo;
-        const uint32_t below = (uint32_t)__popcll(__ballot(le)) - 1;
-        const uint32_t end = p + cnt;
-        p += below * step;
-        cnt = min(step, end - p);
-    }
+    const ChunkLds L = chunk_lds(lds);
+    const ChunkSpan S = chunk_span(chunk_start, n_jobs, per_block);
+    uint32_t p = chunk_owner(chunk_start, n_jobs, S.lo);      // the job whose chunk range holds the first chunk
     uint32_t cur_q = 0xffffffffu;
     const unsigned lane = threadIdx.x;
     // the workgroup's history slice: hist_slice entries per lane
     const size_t hbase = (size_t)blockIdx.x * hist_slice * MINE_THREADS + lane;
-    for (uint64_t v = lo; v < hi; v++) {
+    for (uint64_t v = S.lo; v < S.hi; v++) {
         while (chunk_start[p + 1] <= v) p++;
         const ConsJobDev J = jobs[p];
         const int m = len[J.draft];
         const int W = (m + 63) >> 6, Wp = W | 1;
         if (J.draft != cur_q) {
             __syncthreads();                       // the previous draft's lanes are done with the table
-            mine_build_peq(bytes + off[J.draft], m, W, Wp, peq, rowmap, present);
+            mine_build_peq(bytes + off[J.draft], m, W, Wp, L.peq, L.rowmap, L.present);
             cur_q = J.draft;
         }
         const uint32_t member = (uint32_t)(v - chunk_start[p]) * MINE_THREADS + lane;
@@ -65,16 +52,9 @@ __global__ __launch_bounds__(MINE_THREADS) void cons_align_kernel(const unsigned
         const int k = (kd < 0 || kj < 0) ? -1 : max(kd, kj);
         const ConsHist H{hist_pm + hbase, hist_s + hbase, (int)J.B};
         uint32_t *row = rows + J.rows_off + (uint64_t)member * (uint32_t)(m + 1);
-        int d;
-        if constexpr (WR > 0) {
-            RegState<WR> st;
-            d = cons_pair<WR>(st, H, peq, rowmap, m, W, Wp, k, bytes + off[tj], len[tj], row);
-        } else {
-            u64 *sbase = scratch + (size_t)blockIdx.x * 3 * scratch_words * MINE_THREADS;
-            GlobalState st{sbase + lane, sbase + (size_t)scratch_words * MINE_THREADS + lane,
-                           reinterpret_cast<int *>(sbase + (size_t)2 * scratch_words * MINE_THREADS) + lane};
-            d = cons_pair<0>(st, H, peq, rowmap, m, W, Wp, k, bytes + off[tj], len[tj], row);
-        }
+        const int d = chunk_lane_state<WR>(scratch, scratch_words, [&](auto &st) {
+            return cons_pair<WR>(st, H, L.peq, L.rowmap, m, W, Wp, k, bytes + off[tj], len[tj], row);
+        });
         dist[J.dist_off + member] = d;
     }
 }
@@ -117,25 +97,11 @@ extern "C" int smx_launch_cons_align(void *stream, int wr, const unsigned char *
                                      size_t lds_bytes, uint32_t *d_rows, int32_t *d_dist, void *d_hist_pm, int *d_hist_s,
                                      uint64_t hist_slice, unsigned long long *d_scratch, int scratch_words) {
     using namespace smx;
-    const void *fn;
-    switch (wr) {
-        case 1: fn = (const void *)cons_align_kernel<1>; break;
-        case 2: fn = (const void *)cons_align_kernel<2>; break;
-        case 4: fn = (const void *)cons_align_kernel<4>; break;
-        case 8: fn = (const void *)cons_align_kernel<8>; break;
-        case 16: fn = (const void *)cons_align_kernel<16>; break;
-        case 0: fn = (const void *)cons_align_kernel<0>; break;
-        default: return (int)hipErrorInvalidValue;
-    }
-    if (n_jobs == 0 || grid < 1 || per_block < 1) return (int)hipErrorInvalidValue;
-    if (lds_bytes > 65536) {
-        hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-        if (e != hipSuccess) return (int)e;
-    }
     // in the order of cons_align_kernel's parameters; every pointer is passed as the pointer it is
     void *args[] = {&d_bytes, &d_off, &d_len, &d_k, &d_jobs, &d_chunk_start, &n_jobs, &per_block, &d_rows, &d_dist,
                     &d_hist_pm, &d_hist_s, &hist_slice, &d_scratch, &scratch_words};
-    return (int)hipLaunchKernel(fn, dim3(grid), dim3(MINE_THREADS), args, lds_bytes, (hipStream_t)stream);
+    auto pick = [](auto WR) { return (const void *)cons_align_kernel<WR()>; };
+    return chunk_launch(stream, wr, pick, n_jobs, grid, per_block, lds_bytes, args);
 }
 
 extern "C" int smx_launch_cons_vote(void *stream, const int32_t *d_len, const void *d_jobs, uint32_t n_jobs,

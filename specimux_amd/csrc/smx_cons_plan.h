@@ -7,7 +7,7 @@
 #include <string>
 #include <vector>
 
-#include "smx_internal.h"
+#include "smx_chunk_plan.h"
 #include "smx_cons_core.h"
 
 namespace smx {
@@ -67,21 +67,13 @@ inline int cons_plan(const char *reads, const uint64_t *roff, uint32_t n_reads, 
     for (uint32_t j = 0; j < n_jobs; j++) {
         const smx_cons_job &J = jobs[j];
         const int m = P.len[J.draft];
-        // the draft's Peq table in LDS and its register class: as a specimine query's (mine_queries)
-        bool seen[256] = {false};
-        int nrows = 0;
-        for (uint64_t i = roff[J.draft]; i < roff[J.draft + 1]; i++) {
-            const unsigned char c = (unsigned char)reads[i];
-            if (!seen[c]) { seen[c] = true; nrows++; }
-        }
-        const size_t W = ((size_t)m + 63) / 64, Wp = W | 1;
-        const size_t lds = (MINE_LDS_HEAD + (size_t)(nrows + 1) * Wp) * 8;
-        if (lds > SMX_LDS_POOL) {
-            *why = "job " + std::to_string(j) + ": the draft's " + std::to_string(nrows) + " distinct bytes x " + std::to_string(W) +
-                   " words do not fit the LDS (" + std::to_string(lds) + " > " + std::to_string((size_t)SMX_LDS_POOL) + " bytes)";
+        // the draft's Peq table in LDS and its state class
+        const ChunkTable T = chunk_table(reads + roff[J.draft], (uint64_t)m);
+        if (!T.fits()) {
+            *why = T.refusal("job " + std::to_string(j) + ": the draft's ");
             return SMX_ERR_UNSUPPORTED;
         }
-        const int c = W <= 1 ? 1 : W <= 2 ? 2 : W <= 4 ? 3 : W <= 8 ? 4 : W <= 16 ? 5 : 0;
+        const int c = T.cls;
         // the history of the job's widest band over its longest banded read
         int B = 0, cols = 0;
         for (uint32_t i = 0; i < J.n; i++) {
@@ -97,8 +89,8 @@ inline int cons_plan(const char *reads, const uint64_t *roff, uint32_t n_reads, 
         P.max_words = std::max(P.max_words, (uint32_t)m + 1);
         if (J.n == 0) continue;
         P.hist_slice = std::max(P.hist_slice, (uint64_t)B * (uint64_t)cols);
-        P.lds_max[c] = std::max(P.lds_max[c], lds);
-        if (c == 0) P.words_max0 = std::max(P.words_max0, (int)W);
+        P.lds_max[c] = std::max(P.lds_max[c], T.lds);
+        if (c == 0) P.words_max0 = std::max(P.words_max0, (int)T.W);
         by_class[c].push_back(j);
     }
     const uint64_t slice_bytes = P.hist_slice * MINE_THREADS * CONS_HIST_ENTRY;

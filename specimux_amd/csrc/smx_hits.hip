@@ -12,7 +12,7 @@
 
 #include "smx_internal.h"
 #include "smx_hits_core.h"
-#include "smx_mine_lds.h"   // mine_build_peq
+#include "smx_mine_lds.h"   // the chunk walk, mine_build_peq
 
 namespace smx {
 
@@ -37,21 +37,12 @@ __global__ __launch_bounds__(MINE_THREADS) void hits_kernel(const unsigned char 
                                                             const HitsJobDev *__restrict__ jobs, uint64_t per_block, int K,
                                                             u64 *keys, int32_t *dist, u64 *scratch, int scratch_words) {
     extern __shared__ u64 lds[];
-    unsigned short *rowmap = reinterpret_cast<unsigned short *>(lds);     // 512 B
-    unsigned *present = reinterpret_cast<unsigned *>(lds + 64);           // 1 KiB
-    u64 *peq = lds + MINE_LDS_HEAD;
-    const uint64_t n_chunks = chunk_start[n_recs];
-    const uint64_t lo = (uint64_t)blockIdx.x * per_block;
-    const uint64_t hi = lo + per_block < n_chunks ? lo + per_block : n_chunks;
-    // the record whose chunk range holds lo: the last p with chunk_start[p] <= lo (uniform over the workgroup)
-    uint32_t p = 0, end = n_recs;
-    while (end - p > 1) {
-        const uint32_t mid = p + (end - p) / 2;
-        if (chunk_start[mid] <= lo) p = mid; else end = mid;
-    }
+    const ChunkLds L = chunk_lds(lds);
+    const ChunkSpan S = chunk_span(chunk_start, n_recs, per_block);
+    uint32_t p = chunk_owner(chunk_start, n_recs, S.lo);      // the record whose chunk range holds the first chunk
     uint32_t cur = 0xffffffffu;
     const unsigned lane = threadIdx.x;
-    for (uint64_t v = lo; v < hi; v++) {
+    for (uint64_t v = S.lo; v < S.hi; v++) {
         while (chunk_start[p + 1] <= v) p++;
         const HitsRec R = recs[p];
         const HitsJobDev J = jobs[R.job];
@@ -60,21 +51,14 @@ __global__ __launch_bounds__(MINE_THREADS) void hits_kernel(const unsigned char 
         const int W = (m + 63) >> 6, Wp = W | 1;
         if (R.pattern != cur) {
             __syncthreads();                       // the previous pattern's lanes are done with the table
-            mine_build_peq(bytes + off[R.pattern], m, W, Wp, peq, rowmap, present);
+            mine_build_peq(bytes + off[R.pattern], m, W, Wp, L.peq, L.rowmap, L.present);
             cur = R.pattern;
         }
         if (c < R.n) {
             const uint32_t text = ord[R.first + c];
-            int d;
-            if constexpr (WR > 0) {
-                RegState<WR> st;
-                d = mine_pair<WR>(st, peq, rowmap, m, W, Wp, klim[R.pattern], bytes + off[text], len[text]);
-            } else {
-                u64 *sbase = scratch + (size_t)blockIdx.x * 3 * scratch_words * MINE_THREADS;
-                GlobalState st{sbase + lane, sbase + (size_t)scratch_words * MINE_THREADS + lane,
-                               reinterpret_cast<int *>(sbase + (size_t)2 * scratch_words * MINE_THREADS) + lane};
-                d = mine_pair<0>(st, peq, rowmap, m, W, Wp, klim[R.pattern], bytes + off[text], len[text]);
-            }
+            const int d = chunk_lane_state<WR>(scratch, scratch_words, [&](auto &st) {
+                return mine_pair<WR>(st, L.peq, L.rowmap, m, W, Wp, klim[R.pattern], bytes + off[text], len[text]);
+            });
             const uint32_t q = (R.side ? text : R.pattern) - J.q0, t = (R.side ? R.pattern : text) - J.t0;
             if constexpr (DIST) dist[J.dist_off + (uint64_t)q * J.nt + t] = d;
             else if (d >= 0) hits_insert(keys + (J.row_off + q) * (uint64_t)K, K, hits_key(d, m, t), HitsAtomicMin());
@@ -90,25 +74,10 @@ extern "C" int smx_launch_hits(void *stream, int wr, int dist, const unsigned ch
                                uint64_t per_block, size_t lds_bytes, int K, unsigned long long *d_keys, int32_t *d_dist,
                                unsigned long long *d_scratch, int scratch_words) {
     using namespace smx;
-#define SMX_HITS_FN(WR) (dist ? (const void *)hits_kernel<WR, true> : (const void *)hits_kernel<WR, false>)
-    const void *fn;
-    switch (wr) {
-        case 1: fn = SMX_HITS_FN(1); break;
-        case 2: fn = SMX_HITS_FN(2); break;
-        case 4: fn = SMX_HITS_FN(4); break;
-        case 8: fn = SMX_HITS_FN(8); break;
-        case 16: fn = SMX_HITS_FN(16); break;
-        case 0: fn = SMX_HITS_FN(0); break;
-        default: return (int)hipErrorInvalidValue;
-    }
-#undef SMX_HITS_FN
-    if (n_recs == 0 || grid < 1 || per_block < 1 || K < 1 || K > HITS_MAX_K) return (int)hipErrorInvalidValue;
-    if (lds_bytes > 65536) {
-        hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-        if (e != hipSuccess) return (int)e;
-    }
+    if (K < 1 || K > HITS_MAX_K) return (int)hipErrorInvalidValue;
     // in the order of hits_kernel's parameters; every pointer is passed as the pointer it is
     void *args[] = {&d_bytes, &d_off, &d_len, &d_k, &d_ord, &d_recs, &d_chunk_start, &n_recs, &d_jobs, &per_block, &K,
                     &d_keys, &d_dist, &d_scratch, &scratch_words};
-    return (int)hipLaunchKernel(fn, dim3(grid), dim3(MINE_THREADS), args, lds_bytes, (hipStream_t)stream);
+    auto pick = [&](auto WR) { return dist ? (const void *)hits_kernel<WR(), true> : (const void *)hits_kernel<WR(), false>; };
+    return chunk_launch(stream, wr, pick, n_recs, grid, per_block, lds_bytes, args);
 }

@@ -15,12 +15,11 @@
 #include <string>
 #include <vector>
 
-#include "smx_internal.h"
+#include "smx_chunk_plan.h"
 #include "smx_hits_core.h"
 
 namespace smx {
 
-constexpr uint64_t HITS_SCRATCH_BYTES = (uint64_t)256 << 20;   // the generic class's per-lane state, at most (about)
 constexpr uint64_t HITS_BLOCK_CHUNKS = 8;                       // chunks a workgroup takes in a row: specimine's, DESIGN.md §10
 
 struct HitsPlan {
@@ -38,8 +37,6 @@ struct HitsPlan {
     uint64_t n_rows = 0, n_dist = 0;       // sum(nq), sum(nq x nt)
     uint64_t n_pairs = 0;                  // sum of the records' n: the pairs the call aligns
 };
-
-inline int hits_class(size_t W) { return W <= 1 ? 1 : W <= 2 ? 2 : W <= 4 ? 3 : W <= 8 ? 4 : W <= 16 ? 5 : 0; }
 
 // The plan of a call.  seqs may be nullptr (a lengths-only call): every check but the LDS one is made, and the records
 // are planned, from the offsets alone.  Returns SMX_OK, or the status to fail with and why.
@@ -112,22 +109,15 @@ inline int hits_plan(const char *seqs, const uint64_t *off, uint32_t n_seqs, con
             *why = "sequence " + std::to_string(r) + ": a pattern of " + std::to_string(m) + " bytes, 2^19 or more";
             return SMX_ERR_UNSUPPORTED;
         }
-        const size_t W = ((size_t)m + 63) / 64, Wp = W | 1;
-        const int c = hits_class(W);
-        if (seqs) {                                // the LDS its Peq table needs (as a specimine query's, mine_queries)
-            bool seen[256] = {false};
-            int nrows = 0;
-            for (uint64_t i = off[r]; i < off[r + 1]; i++) {
-                const unsigned char b = (unsigned char)seqs[i];
-                if (!seen[b]) { seen[b] = true; nrows++; }
-            }
-            const size_t lds = (MINE_LDS_HEAD + (size_t)(nrows + 1) * Wp) * 8;
-            if (lds > SMX_LDS_POOL) {
-                *why = "pattern " + std::to_string(r) + ": " + std::to_string(nrows) + " distinct bytes x " + std::to_string(W) +
-                       " words do not fit the LDS (" + std::to_string(lds) + " > " + std::to_string((size_t)SMX_LDS_POOL) + " bytes)";
+        const size_t W = ((size_t)m + 63) / 64;
+        const int c = chunk_class(W);
+        if (seqs) {                                // the LDS its Peq table needs
+            const ChunkTable T = chunk_table(seqs + off[r], (uint64_t)m);
+            if (!T.fits()) {
+                *why = T.refusal("pattern " + std::to_string(r) + ": ");
                 return SMX_ERR_UNSUPPORTED;
             }
-            P.lds_max[c] = std::max(P.lds_max[c], lds);
+            P.lds_max[c] = std::max(P.lds_max[c], T.lds);
         }
         if (c == 0) P.words_max0 = std::max(P.words_max0, (int)W);
         cls[r] = (signed char)c;
@@ -186,15 +176,11 @@ inline int hits_plan(const char *seqs, const uint64_t *off, uint32_t n_seqs, con
         P.recs.insert(P.recs.end(), by_class[c].begin(), by_class[c].end());
         // HITS_BLOCK_CHUNKS chunks per workgroup; more only where the grid is capped: by the launch, and in the generic
         // class by the scratch slices of the workgroups in flight
-        uint64_t cap = (uint64_t)INT32_MAX;
-        if (c == 0) {
-            const uint64_t slice = (uint64_t)3 * P.words_max0 * MINE_THREADS * 8;
-            cap = std::min(cap, std::max<uint64_t>(1, HITS_SCRATCH_BYTES / std::max<uint64_t>(slice, 1)));
-        }
-        P.per_block[c] = std::max<uint64_t>(HITS_BLOCK_CHUNKS, (P.chunks[c] + cap - 1) / cap);
-        P.grid[c] = (P.chunks[c] + P.per_block[c] - 1) / P.per_block[c];
+        const ChunkGrid G = chunk_class_grid(c, P.chunks[c], HITS_BLOCK_CHUNKS, P.words_max0);
+        P.per_block[c] = G.per_block;
+        P.grid[c] = G.grid;
     }
-    P.scratch_words = P.grid[0] * 3 * (uint64_t)P.words_max0 * MINE_THREADS;
+    P.scratch_words = chunk_scratch_words(P.grid[0], P.words_max0);
     return SMX_OK;
 }
 

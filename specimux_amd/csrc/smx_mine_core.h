@@ -99,6 +99,19 @@ struct GlobalState {   // pointers already offset to this lane; element w at [w 
     SMX_HD int &s(int w) { return S[(size_t)w * MINE_THREADS]; }
 };
 
+// The per-lane state of class WR handed to f(st): registers for WR > 0; for WR = 0 this lane's columns of a workgroup's
+// scratch slice, 3 x scratch_words x MINE_THREADS words laid out [P | M | S][word][lane].  Returns what f returns.
+template <int WR, typename F> SMX_HD int mine_lane_state(u64 *slice, int scratch_words, unsigned lane, F &&f) {
+    if constexpr (WR > 0) {
+        RegState<WR> st;
+        return f(st);
+    } else {
+        GlobalState st{slice + lane, slice + (size_t)scratch_words * MINE_THREADS + lane,
+                       reinterpret_cast<int *>(slice + (size_t)2 * scratch_words * MINE_THREADS) + lane};
+        return f(st);
+    }
+}
+
 // One pair: HW distance of the query (Peq of W words, padded row stride Wp) in target t[0..n).
 // Returns -1 if the distance exceeds k (k < 0: no limit).  t must be 16-byte aligned and readable up to the next
 // multiple of 16 bytes past n.  WR > 0: the state of W <= WR words in registers; WR = 0: any W, state in st.

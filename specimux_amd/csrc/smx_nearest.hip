@@ -34,20 +34,11 @@ __global__ __launch_bounds__(MINE_THREADS) void nearest_kernel(const unsigned ch
                                                                u64 *best_own, u64 *best_other, int32_t *dist,
                                                                u64 *scratch, int scratch_words) {
     extern __shared__ u64 lds[];
-    unsigned short *rowmap = reinterpret_cast<unsigned short *>(lds);     // 512 B
-    unsigned *present = reinterpret_cast<unsigned *>(lds + 64);           // 1 KiB
-    u64 *peq = lds + MINE_LDS_HEAD;
-    const uint64_t n_chunks = chunk_start[n_runs];
-    const uint64_t lo = (uint64_t)blockIdx.x * per_block;
-    const uint64_t hi = lo + per_block < n_chunks ? lo + per_block : n_chunks;
-    // the run whose chunk range holds lo: the last p with chunk_start[p] <= lo (uniform over the workgroup)
-    uint32_t p = 0, end = n_runs;
-    while (end - p > 1) {
-        const uint32_t mid = p + (end - p) / 2;
-        if (chunk_start[mid] <= lo) p = mid; else end = mid;
-    }
+    const ChunkLds L = chunk_lds(lds);
+    const ChunkSpan S = chunk_span(chunk_start, n_runs, per_block);
+    uint32_t p = chunk_owner(chunk_start, n_runs, S.lo);      // the run whose chunk range holds the first chunk
     const unsigned lane = threadIdx.x;
-    for (uint64_t v = lo; v < hi; v++) {
+    for (uint64_t v = S.lo; v < S.hi; v++) {
         while (chunk_start[p + 1] <= v) p++;
         const NearestRun R = runs[p];
         const NearestJobDev J = jobs[R.job];
@@ -63,19 +54,12 @@ __global__ __launch_bounds__(MINE_THREADS) void nearest_kernel(const unsigned ch
             const int m = len[ref];
             const int W = (m + 63) >> 6, Wp = W | 1;
             __syncthreads();                       // the previous ref's lanes are done with the table
-            mine_build_peq(bytes + off[ref], m, W, Wp, peq, rowmap, present);
+            mine_build_peq(bytes + off[ref], m, W, Wp, L.peq, L.rowmap, L.present);
             if (active) {
                 const int k = nearest_limit(klim[ref], kt);
-                int d;
-                if constexpr (WR > 0) {
-                    RegState<WR> st;
-                    d = pairs_pair<WR>(st, peq, rowmap, m, W, Wp, k, tb, n);
-                } else {
-                    u64 *sbase = scratch + (size_t)blockIdx.x * 3 * scratch_words * MINE_THREADS;
-                    GlobalState st{sbase + lane, sbase + (size_t)scratch_words * MINE_THREADS + lane,
-                                   reinterpret_cast<int *>(sbase + (size_t)2 * scratch_words * MINE_THREADS) + lane};
-                    d = pairs_pair<0>(st, peq, rowmap, m, W, Wp, k, tb, n);
-                }
+                const int d = chunk_lane_state<WR>(scratch, scratch_words, [&](auto &st) {
+                    return pairs_pair<WR>(st, L.peq, L.rowmap, m, W, Wp, k, tb, n);
+                });
                 if constexpr (DIST) dist[J.dist_off + (uint64_t)(ref - J.q0) * J.nt + ti] = d;
                 else nearest_offer(K, group[ref] == gt, d, ref);
             }
@@ -96,25 +80,9 @@ extern "C" int smx_launch_nearest(void *stream, int wr, int dist, const unsigned
                                   unsigned long long *d_best_own, unsigned long long *d_best_other, int32_t *d_dist,
                                   unsigned long long *d_scratch, int scratch_words) {
     using namespace smx;
-#define SMX_NEAREST_FN(WR) (dist ? (const void *)nearest_kernel<WR, true> : (const void *)nearest_kernel<WR, false>)
-    const void *fn;
-    switch (wr) {
-        case 1: fn = SMX_NEAREST_FN(1); break;
-        case 2: fn = SMX_NEAREST_FN(2); break;
-        case 4: fn = SMX_NEAREST_FN(4); break;
-        case 8: fn = SMX_NEAREST_FN(8); break;
-        case 16: fn = SMX_NEAREST_FN(16); break;
-        case 0: fn = SMX_NEAREST_FN(0); break;
-        default: return (int)hipErrorInvalidValue;
-    }
-#undef SMX_NEAREST_FN
-    if (n_runs == 0 || grid < 1 || per_block < 1) return (int)hipErrorInvalidValue;
-    if (lds_bytes > 65536) {
-        hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-        if (e != hipSuccess) return (int)e;
-    }
     // in the order of nearest_kernel's parameters; every pointer is passed as the pointer it is
     void *args[] = {&d_bytes, &d_off, &d_len, &d_k, &d_group, &d_refs, &d_runs, &d_chunk_start, &n_runs, &d_jobs,
                     &per_block, &d_best_own, &d_best_other, &d_dist, &d_scratch, &scratch_words};
-    return (int)hipLaunchKernel(fn, dim3(grid), dim3(MINE_THREADS), args, lds_bytes, (hipStream_t)stream);
+    auto pick = [&](auto WR) { return dist ? (const void *)nearest_kernel<WR(), true> : (const void *)nearest_kernel<WR(), false>; };
+    return chunk_launch(stream, wr, pick, n_runs, grid, per_block, lds_bytes, args);
 }

@@ -8,12 +8,11 @@
 #include <string>
 #include <vector>
 
-#include "smx_internal.h"
+#include "smx_chunk_plan.h"
 #include "smx_nearest_core.h"
 
 namespace smx {
 
-constexpr uint64_t NEAREST_SCRATCH_BYTES = (uint64_t)256 << 20;   // the generic class's per-lane state, at most (about)
 constexpr uint64_t NEAREST_CHUNKS_PER_CU = 32;                    // G = this x the CU count: measured, DESIGN.md §16
 
 struct NearestPlan {
@@ -34,8 +33,6 @@ struct NearestPlan {
     struct Slice { uint32_t job, lo, n; }; // a job's refs of one class: refs [lo, lo + n) of the class's list
     std::vector<Slice> slices[6];          // per class, the jobs with reads and refs of the class, in job order
 };
-
-inline int nearest_class(size_t W) { return W <= 1 ? 1 : W <= 2 ? 2 : W <= 4 ? 3 : W <= 8 ? 4 : W <= 16 ? 5 : 0; }
 
 // The first half of the plan, which needs no device: the checks, the jobs and the refs by class.  Returns SMX_OK, or the
 // status to fail with and why.
@@ -74,7 +71,7 @@ inline int nearest_plan(const char *seqs, const uint64_t *off, uint32_t n_seqs, 
             *why = "jobs " + std::to_string(order[i - 1]) + " and " + std::to_string(order[i]) + ": read ranges overlap";
             return SMX_ERR_ARG;
         }
-    // the refs by class, with the LDS their Peq tables need (as a specimine query's, mine_queries)
+    // the refs by class, with the LDS their Peq tables need
     std::vector<uint32_t> by_class[6];
     int32_t depth = 0;
     for (uint32_t r = 0; r < n_seqs; r++) {
@@ -85,22 +82,14 @@ inline int nearest_plan(const char *seqs, const uint64_t *off, uint32_t n_seqs, 
             *why = "sequence " + std::to_string(r) + ": an empty ref";
             return SMX_ERR_ARG;
         }
-        bool seen[256] = {false};
-        int nrows = 0;
-        for (uint64_t i = off[r]; i < off[r + 1]; i++) {
-            const unsigned char c = (unsigned char)seqs[i];
-            if (!seen[c]) { seen[c] = true; nrows++; }
-        }
-        const size_t W = ((size_t)m + 63) / 64, Wp = W | 1;
-        const size_t lds = (MINE_LDS_HEAD + (size_t)(nrows + 1) * Wp) * 8;
-        if (lds > SMX_LDS_POOL) {
-            *why = "ref " + std::to_string(r) + ": " + std::to_string(nrows) + " distinct bytes x " + std::to_string(W) +
-                   " words do not fit the LDS (" + std::to_string(lds) + " > " + std::to_string((size_t)SMX_LDS_POOL) + " bytes)";
+        const ChunkTable T = chunk_table(seqs + off[r], (uint64_t)m);
+        if (!T.fits()) {
+            *why = T.refusal("ref " + std::to_string(r) + ": ");
             return SMX_ERR_UNSUPPORTED;
         }
-        const int c = nearest_class(W);
-        P.lds_max[c] = std::max(P.lds_max[c], lds);
-        if (c == 0) P.words_max0 = std::max(P.words_max0, (int)W);
+        const int c = T.cls;
+        P.lds_max[c] = std::max(P.lds_max[c], T.lds);
+        if (c == 0) P.words_max0 = std::max(P.words_max0, (int)T.W);
         by_class[c].push_back(r);
     }
     // per (job, class) the job's refs are a slice of the class list
@@ -165,15 +154,11 @@ inline void nearest_plan_runs(NearestPlan *plan, uint64_t min_chunks) {
         }
         // one chunk per workgroup; several only where the grid is capped: by the launch, and in the generic class by
         // the scratch slices of the workgroups in flight
-        uint64_t cap = (uint64_t)INT32_MAX;
-        if (c == 0) {
-            const uint64_t slice = (uint64_t)3 * P.words_max0 * MINE_THREADS * 8;
-            cap = std::min(cap, std::max<uint64_t>(1, NEAREST_SCRATCH_BYTES / std::max<uint64_t>(slice, 1)));
-        }
-        P.per_block[c] = std::max<uint64_t>(1, (P.chunks[c] + cap - 1) / cap);
-        P.grid[c] = (P.chunks[c] + P.per_block[c] - 1) / P.per_block[c];
+        const ChunkGrid G = chunk_class_grid(c, P.chunks[c], 1, P.words_max0);
+        P.per_block[c] = G.per_block;
+        P.grid[c] = G.grid;
     }
-    P.scratch_words = P.grid[0] * 3 * (uint64_t)P.words_max0 * MINE_THREADS;
+    P.scratch_words = chunk_scratch_words(P.grid[0], P.words_max0);
 }
 
 }  // namespace smx

@@ -33,25 +33,12 @@ __global__ __launch_bounds__(MINE_THREADS) void pairs_kernel(const unsigned char
                                                              const PairsJobDev *__restrict__ jobs, uint64_t per_block,
                                                              uint32_t *out, u64 *scratch, int scratch_words) {
     extern __shared__ u64 lds[];
-    unsigned short *rowmap = reinterpret_cast<unsigned short *>(lds);     // 512 B
-    unsigned *present = reinterpret_cast<unsigned *>(lds + 64);           // 1 KiB
-    u64 *peq = lds + MINE_LDS_HEAD;
-    const uint64_t n_chunks = chunk_start[n_rows];
-    const uint64_t lo = (uint64_t)blockIdx.x * per_block;
-    const uint64_t hi = lo + per_block < n_chunks ? lo + per_block : n_chunks;
-    // the row whose chunk range holds lo: a 64-way search, one load per lane and round; each wave finds it on its own
-    uint32_t p = 0, cnt = n_rows;                  // the row is in [p, p + cnt)
-    while (cnt > 1) {
-        const uint32_t step = (cnt + 63) / 64, idx = p + (threadIdx.x & 63) * step;
-        const bool le = idx < p + cnt && chunk_start[idx] <= lo;   // true on a prefix of the lanes (lane 0 always)
-        const uint32_t below = (uint32_t)__popcll(__ballot(le)) - 1;
-        const uint32_t end = p + cnt;
-        p += below * step;
-        cnt = min(step, end - p);
-    }
+    const ChunkLds L = chunk_lds(lds);
+    const ChunkSpan S = chunk_span(chunk_start, n_rows, per_block);
+    uint32_t p = chunk_owner(chunk_start, n_rows, S.lo);      // the row whose chunk range holds the first chunk
     uint32_t cur_q = 0xffffffffu;
     const unsigned lane = threadIdx.x;
-    for (uint64_t v = lo; v < hi; v++) {
+    for (uint64_t v = S.lo; v < S.hi; v++) {
         while (chunk_start[p + 1] <= v) p++;
         const PairsRow R = rows[p];
         const PairsJobDev J = jobs[R.job];
@@ -62,7 +49,7 @@ __global__ __launch_bounds__(MINE_THREADS) void pairs_kernel(const unsigned char
         const int W = (m + 63) >> 6, Wp = W | 1;
         if (R.read != cur_q) {
             __syncthreads();                       // the previous query's lanes are done with the table
-            mine_build_peq(bytes + off[R.read], m, W, Wp, peq, rowmap, present);
+            mine_build_peq(bytes + off[R.read], m, W, Wp, L.peq, L.rowmap, L.present);
             cur_q = R.read;
         }
         const uint32_t j = c0 + lane;
@@ -72,15 +59,9 @@ __global__ __launch_bounds__(MINE_THREADS) void pairs_kernel(const unsigned char
             const uint32_t tj = J.r0 + j;
             const int ki = klim[R.read], kj = klim[tj];
             const int k = (ki < 0 || kj < 0) ? -1 : max(ki, kj);          // no limit on either read: none on the pair
-            if constexpr (WR > 0) {
-                RegState<WR> st;
-                d = pairs_pair<WR>(st, peq, rowmap, m, W, Wp, k, bytes + off[tj], len[tj]);
-            } else {
-                u64 *sbase = scratch + (size_t)blockIdx.x * 3 * scratch_words * MINE_THREADS;
-                GlobalState st{sbase + lane, sbase + (size_t)scratch_words * MINE_THREADS + lane,
-                               reinterpret_cast<int *>(sbase + (size_t)2 * scratch_words * MINE_THREADS) + lane};
-                d = pairs_pair<0>(st, peq, rowmap, m, W, Wp, k, bytes + off[tj], len[tj]);
-            }
+            d = chunk_lane_state<WR>(scratch, scratch_words, [&](auto &st) {
+                return pairs_pair<WR>(st, L.peq, L.rowmap, m, W, Wp, k, bytes + off[tj], len[tj]);
+            });
         }
         if constexpr (DIST) {
             if (active) out[J.out_off + (uint64_t)i * J.n - (uint64_t)i * (i + 1) / 2 + (j - i - 1)] = (uint32_t)d;
@@ -104,25 +85,9 @@ extern "C" int smx_launch_pairs(void *stream, int wr, int dist, const unsigned c
                                 uint64_t per_block, size_t lds_bytes, void *d_out, unsigned long long *d_scratch,
                                 int scratch_words) {
     using namespace smx;
-#define SMX_PAIRS_FN(WR) (dist ? (const void *)pairs_kernel<WR, true> : (const void *)pairs_kernel<WR, false>)
-    const void *fn;
-    switch (wr) {
-        case 1: fn = SMX_PAIRS_FN(1); break;
-        case 2: fn = SMX_PAIRS_FN(2); break;
-        case 4: fn = SMX_PAIRS_FN(4); break;
-        case 8: fn = SMX_PAIRS_FN(8); break;
-        case 16: fn = SMX_PAIRS_FN(16); break;
-        case 0: fn = SMX_PAIRS_FN(0); break;
-        default: return (int)hipErrorInvalidValue;
-    }
-#undef SMX_PAIRS_FN
-    if (n_rows == 0 || grid < 1 || per_block < 1) return (int)hipErrorInvalidValue;
-    if (lds_bytes > 65536) {
-        hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-        if (e != hipSuccess) return (int)e;
-    }
     // in the order of pairs_kernel's parameters; every pointer is passed as the pointer it is
     void *args[] = {&d_bytes, &d_off, &d_len, &d_k, &d_rows, &d_chunk_start, &n_rows, &d_jobs, &per_block,
                     &d_out, &d_scratch, &scratch_words};
-    return (int)hipLaunchKernel(fn, dim3(grid), dim3(MINE_THREADS), args, lds_bytes, (hipStream_t)stream);
+    auto pick = [&](auto WR) { return dist ? (const void *)pairs_kernel<WR(), true> : (const void *)pairs_kernel<WR(), false>; };
+    return chunk_launch(stream, wr, pick, n_rows, grid, per_block, lds_bytes, args);
 }

@@ -141,7 +141,7 @@ int main() {
             const ConsHist H{hpm.data() + lane, hs.data() + lane, (int)J.B};
             uint32_t *row = rows.data() + J.rows_off + (size_t)i * (Q.m + 1);
             int d;
-            switch (Q.W <= 1 ? 1 : Q.W <= 2 ? 2 : Q.W <= 4 ? 4 : Q.W <= 8 ? 8 : Q.W <= 16 ? 16 : 0) {
+            switch (CHUNK_CLASS_WORDS[chunk_class((size_t)Q.W)]) {
                 case 1: d = pair_in_class<1>(H, Q, k, t, n, row, sP, sM, sS, lane); break;
                 case 2: d = pair_in_class<2>(H, Q, k, t, n, row, sP, sM, sS, lane); break;
                 case 4: d = pair_in_class<4>(H, Q, k, t, n, row, sP, sM, sS, lane); break;

@@ -20,6 +20,7 @@
 #include <string>
 #include <vector>
 
+#include "smx_chunk_plan.h"   // chunk_class: the state class a call gives a draft
 #include "smx_cons_core.h"
 
 using namespace smx;
@@ -92,7 +93,7 @@ struct Query {
     }
 };
 
-static int reg_class(int W) { return W <= 1 ? 1 : W <= 2 ? 2 : W <= 4 ? 4 : W <= 8 ? 8 : W <= 16 ? 16 : 0; }
+static int reg_class(int W) { return CHUNK_CLASS_WORDS[chunk_class((size_t)W)]; }
 
 struct Sim {
     std::mt19937_64 rng;

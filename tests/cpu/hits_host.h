@@ -32,21 +32,15 @@ struct HitsHostMin {     // the simulation's "atomic minimum that returns the ol
 template <int WR>
 inline int hits_host_pair(const NearestHostTable &T, int m, int W, int Wp, int k, const unsigned char *t, int n, u64 *sbase,
                           int scratch_words, unsigned lane) {
-    if constexpr (WR > 0) {
-        RegState<WR> st;
+    return mine_lane_state<WR>(sbase, scratch_words, lane, [&](auto &st) {
         return mine_pair<WR>(st, T.peq.data(), T.rowmap, m, W, Wp, k, t, n);
-    } else {
-        GlobalState st{sbase + lane, sbase + (size_t)scratch_words * MINE_THREADS + lane,
-                       reinterpret_cast<int *>(sbase + (size_t)2 * scratch_words * MINE_THREADS) + lane};
-        return mine_pair<0>(st, T.peq.data(), T.rowmap, m, W, Wp, k, t, n);
-    }
+    });
 }
 
 // One call.  dist != nullptr: distances mode (keys unused), dist holds P.n_dist entries filled with -1 by the caller;
 // else keys holds P.n_rows x K keys filled with HITS_NONE.  scratch: P.scratch_words words.
 inline void hits_host_run(const HitsPlan &P, const NearestHostSeqs &S, const int32_t *klim, int K, u64 *keys, int32_t *dist,
                           u64 *scratch, HitsHostCounts *counts) {
-    static const int kWords[6] = {0, 1, 2, 4, 8, 16};
     const unsigned char *bytes = S.bytes();
     const int32_t *len = P.len.data();
     const uint32_t *ord = P.ord.data();
@@ -62,11 +56,8 @@ inline void hits_host_run(const HitsPlan &P, const NearestHostSeqs &S, const int
         const uint64_t per_block = P.per_block[c], n_chunks = chunk_start[n_recs];
         for (uint64_t block = 0; block < P.grid[c]; block++) {
             const uint64_t lo = block * per_block, hi = lo + per_block < n_chunks ? lo + per_block : n_chunks;
-            uint32_t p = 0, end = n_recs;
-            while (end - p > 1) {
-                const uint32_t mid = p + (end - p) / 2;
-                if (chunk_start[mid] <= lo) p = mid; else end = mid;
-            }
+            // the record that owns lo, as chunk_owner finds it: the last p with chunk_start[p] <= lo
+            uint32_t p = (uint32_t)(std::upper_bound(chunk_start, chunk_start + n_recs, lo) - chunk_start) - 1;
             uint32_t cur = 0xffffffffu;
             for (uint64_t v = lo; v < hi; v++) {
                 while (chunk_start[p + 1] <= v) p++;
@@ -88,7 +79,7 @@ inline void hits_host_run(const HitsPlan &P, const NearestHostSeqs &S, const int
                     const unsigned char *tb = bytes + S.doff[text];
                     const int k = klim[R.pattern], n = len[text];
                     int d;
-                    switch (kWords[c]) {
+                    switch (CHUNK_CLASS_WORDS[c]) {
                         case 1: d = hits_host_pair<1>(T, m, W, Wp, k, tb, n, sbase, P.words_max0, lane); break;
                         case 2: d = hits_host_pair<2>(T, m, W, Wp, k, tb, n, sbase, P.words_max0, lane); break;
                         case 4: d = hits_host_pair<4>(T, m, W, Wp, k, tb, n, sbase, P.words_max0, lane); break;

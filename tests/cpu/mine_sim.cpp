@@ -16,6 +16,7 @@
 #include <string>
 #include <vector>
 
+#include "smx_chunk_plan.h"   // chunk_class: the state class a call gives a query
 #include "smx_mine_core.h"
 
 using namespace smx;
@@ -65,8 +66,8 @@ struct Query {
     }
 };
 
-// the register class smx_calls.cpp's mine_call picks: words of per-lane state, 0 = generic (global scratch)
-static int reg_class(int W) { return W <= 1 ? 1 : W <= 2 ? 2 : W <= 4 ? 4 : W <= 8 ? 8 : W <= 16 ? 16 : 0; }
+// the register class the call picks (smx_chunk_plan.h): words of per-lane state, 0 = generic (global scratch)
+static int reg_class(int W) { return CHUNK_CLASS_WORDS[chunk_class((size_t)W)]; }
 
 struct Sim {
     std::mt19937_64 rng;

@@ -55,21 +55,15 @@ struct NearestHostCounts {
 template <int WR>
 inline int nearest_host_pair(const NearestHostTable &T, int m, int W, int Wp, int k, const unsigned char *t, int n, u64 *sbase,
                              int scratch_words, unsigned lane) {
-    if constexpr (WR > 0) {
-        RegState<WR> st;
+    return mine_lane_state<WR>(sbase, scratch_words, lane, [&](auto &st) {
         return pairs_pair<WR>(st, T.peq.data(), T.rowmap, m, W, Wp, k, t, n);
-    } else {
-        GlobalState st{sbase + lane, sbase + (size_t)scratch_words * MINE_THREADS + lane,
-                       reinterpret_cast<int *>(sbase + (size_t)2 * scratch_words * MINE_THREADS) + lane};
-        return pairs_pair<0>(st, T.peq.data(), T.rowmap, m, W, Wp, k, t, n);
-    }
+    });
 }
 
 // One call.  dist != nullptr: distances mode (own / other unused); else own / other hold P.n_best keys each, filled with
 // NEAREST_NONE by the caller.  scratch: P.scratch_words words.
 inline void nearest_host_run(const NearestPlan &P, const NearestHostSeqs &S, const int32_t *klim, const uint32_t *group,
                              u64 *own, u64 *other, int32_t *dist, u64 *scratch, NearestHostCounts *counts) {
-    static const int kWords[6] = {0, 1, 2, 4, 8, 16};
     const unsigned char *bytes = S.bytes();
     const int32_t *len = P.len.data();
     size_t qat = 0, rat = 0, cat = 0;
@@ -86,11 +80,8 @@ inline void nearest_host_run(const NearestPlan &P, const NearestHostSeqs &S, con
         const uint64_t per_block = P.per_block[c], n_chunks = chunk_start[n_runs];
         for (uint64_t block = 0; block < P.grid[c]; block++) {
             const uint64_t lo = block * per_block, hi = lo + per_block < n_chunks ? lo + per_block : n_chunks;
-            uint32_t p = 0, end = n_runs;
-            while (end - p > 1) {
-                const uint32_t mid = p + (end - p) / 2;
-                if (chunk_start[mid] <= lo) p = mid; else end = mid;
-            }
+            // the record that owns lo, as chunk_owner finds it: the last p with chunk_start[p] <= lo
+            uint32_t p = (uint32_t)(std::upper_bound(chunk_start, chunk_start + n_runs, lo) - chunk_start) - 1;
             for (uint64_t v = lo; v < hi; v++) {
                 while (chunk_start[p + 1] <= v) p++;
                 const NearestRun R = runs[p];
@@ -121,7 +112,7 @@ inline void nearest_host_run(const NearestPlan &P, const NearestHostSeqs &S, con
                         const int k = nearest_limit(klim[ref], kt);
                         u64 *sbase = scratch + (size_t)block * 3 * P.words_max0 * MINE_THREADS;
                         int d;
-                        switch (kWords[c]) {
+                        switch (CHUNK_CLASS_WORDS[c]) {
                             case 1: d = nearest_host_pair<1>(T, m, W, Wp, k, tb, n, sbase, P.words_max0, lane); break;
                             case 2: d = nearest_host_pair<2>(T, m, W, Wp, k, tb, n, sbase, P.words_max0, lane); break;
                             case 4: d = nearest_host_pair<4>(T, m, W, Wp, k, tb, n, sbase, P.words_max0, lane); break;

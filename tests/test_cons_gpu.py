@@ -112,6 +112,53 @@ def test_pileup_equals_the_reference(shapes):
     assert (want_rows == NO_ROW).any() and ((want_rows >> 3) & 255 >= 6).any() and ((want_rows & 7) == 4).any()
 
 
+def test_pileup_walk_over_many_short_jobs(monkeypatch):
+    """The chunk walk (smx_mine_lds.h) where it can go wrong, all in state class 1: more than 4096 jobs, so that the owner
+    search takes its third round, of 1, 2 and 129 members in turn, so that a job of 129 owns two chunks.  Once with one
+    chunk per workgroup, and once with a history workspace of 39 slices: 39 workgroups of ceil(chunks / 39) chunks,
+    some of which start inside a job and the last of which is short.  The reads are drawn from a small pool, so the
+    twin aligns every distinct pair once; every distance and every row word of both calls is compared."""
+    rng = random.Random(63)
+    pool = [rand_seq(rng, rng.randrange(12, 41)) for _ in range(20)]
+    pool += [(mutate(rng, r, 0.1) or r)[:40].ljust(12, "A") for r in pool]
+    pool = [r.encode("latin-1") for r in pool]
+    kpool = [rng.choice((-1, 3, 6, 12)) for _ in pool]
+    twin = {}
+    for a in range(len(pool)):
+        for b in range(len(pool)):
+            d, row = row_reference(pool[a], pool[b], -1 if kpool[a] < 0 or kpool[b] < 0 else max(kpool[a], kpool[b]))
+            twin[a, b] = d, np.array(row, dtype=np.uint32)
+    sizes = [(1, 2, 129)[j % 3] for j in range(4099)]
+    ids = [rng.randrange(len(pool)) for _ in range(sum(sizes))]
+    jobs, r0 = [], 0
+    for n in sizes:
+        jobs.append((r0 + rng.randrange(n), r0, n))            # the draft: one of the job's own members
+        r0 += n
+    want_dist = np.array([twin[ids[d], ids[r]][0] for d, r0, n in jobs for r in range(r0, r0 + n)], dtype=np.int32)
+    want_rows = np.concatenate([twin[ids[d], ids[r]][1] for d, r0, n in jobs for r in range(r0, r0 + n)])
+    assert (want_dist >= 0).sum() > 20000 and (want_dist == -1).sum() > 20000
+    chunks = sum((n + 127) // 128 for n in sizes)
+    starts = np.concatenate([[0], np.cumsum([(n + 127) // 128 for n in sizes])])
+    per_block = -(-chunks // 39)
+    first = np.arange(0, chunks, per_block)                     # every workgroup's first chunk in the second call
+    assert chunks % per_block != 0 and np.isin(first, starts, invert=True).sum() >= 5
+    reads, ks = [pool[x] for x in ids], [kpool[x] for x in ids]
+    monkeypatch.setenv("SMX_CONS_HIST_BYTES", "1")
+    assert cons_raw(reads, ks, jobs)[0] == _lib.ERR_UNSUPPORTED
+    need = int(re.search(r"needs (\d+) bytes", _lib.load().smx_last_error().decode()).group(1))
+    for budget in (None, 39 * need):
+        if budget is None:
+            monkeypatch.delenv("SMX_CONS_HIST_BYTES")
+        else:
+            monkeypatch.setenv("SMX_CONS_HIST_BYTES", str(budget))
+        rc, rows, dist, _ms = cons_raw(reads, ks, jobs)
+        assert rc == _lib.OK, _lib.load().smx_last_error()
+        bad = np.nonzero(dist != want_dist)[0]
+        assert bad.size == 0, (budget, bad.size, [(int(x), int(dist[x]), int(want_dist[x])) for x in bad[:10]])
+        bad = np.nonzero(rows != want_rows)[0]
+        assert rows.size == want_rows.size and bad.size == 0, (budget, bad.size, bad[:10].tolist())
+
+
 def test_votes_equal_the_reduced_rows(shapes):
     reads, ks, jobs, want_rows, want_dist = shapes
     rc, votes, aligned, ms = cons_raw(reads, ks, jobs, votes=True)

@@ -159,6 +159,44 @@ def test_distances_match_the_oracle(case):
     assert sum(int((w >= 0).sum()) for w in want) >= 600 and sum(int((w < 0).sum()) for w in want) >= 500
 
 
+def test_distances_walk_over_many_short_records():
+    """The chunk walk (smx_mine_lds.h) where it can go wrong, all in state class 1: 4201 jobs of one short query each over
+    windows of 1, 129 and 257 longer targets of a shared set, more than 4096 records, so that the owner search takes its
+    third round; records of one, two and three chunks in turn, so that most workgroups of 8 chunks start inside a
+    record; a chunk total that is no multiple of 8.  The sequences are drawn from two small pools, so the oracle aligns
+    every distinct pair once; every distance of the call is compared."""
+    rng = random.Random(6)
+    qpool = [rand_seq(rng, rng.randrange(12, 21)) for _ in range(48)]
+    kpool = [rng.choice((-1, 1, 3, 6)) for _ in qpool]
+    tpool = [rand_seq(rng, rng.randrange(21, 41)) if i % 2 else
+             (rand_seq(rng, rng.randrange(9)) + mutate(rng, qpool[i], 0.1) + rand_seq(rng, 20))[:rng.randrange(23, 41)]
+             for i in range(48)]
+    assert all(identify.pair_rule(len(q), len(t), COV) == (True, True) for q in qpool for t in tpool)
+    table = np.empty((48, 48), dtype=np.int32)
+    for a, (q, k) in enumerate(zip(qpool, kpool)):
+        for b, t in enumerate(tpool):
+            d = align_c(q, t, HW, -1, iupac=False)["editDistance"]
+            table[a, b] = d if k < 0 or d <= k else -1
+    n_t, n_rec = 600, 4201
+    tid = np.array([rng.randrange(48) for _ in range(n_t)])
+    qid = [rng.randrange(48) for _ in range(n_rec)]
+    jobs = [(n_t + i, 1, rng.randrange(300), (1, 129, 257)[i % 3]) for i in range(n_rec)]
+    starts = np.concatenate([[0], np.cumsum([(j[3] + 127) // 128 for j in jobs])])      # the records' chunk prefix
+    first = np.arange(0, starts[-1], 8)                                                # every workgroup's first chunk
+    assert starts[-1] % 8 != 0 and np.isin(first, starts, invert=True).mean() > 0.5
+    seqs = [tpool[x].encode("latin-1") for x in tid] + [qpool[x].encode("latin-1") for x in qid]
+    ks = [4] * n_t + [kpool[x] for x in qid]
+    got = identify.best_hits_distances(seqs, ks, jobs, 5, COV)
+    assert len(got) == n_rec
+    n_in = n_out = 0
+    for i, (g, (_, _, t0, nt)) in enumerate(zip(got, jobs)):
+        w = table[qid[i], tid[t0:t0 + nt]].reshape(1, nt)
+        bad = np.argwhere(g != w)
+        assert g.shape == w.shape and bad.size == 0, (i, jobs[i], bad[:5].tolist(), [(int(g[q, t]), int(w[q, t])) for q, t in bad[:5]])
+        n_in, n_out = n_in + int((w >= 0).sum()), n_out + int((w < 0).sum())
+    assert n_in > 50000 and n_out > 50000
+
+
 @pytest.mark.parametrize("K", [1, 3, 16])
 def test_keys_equal_the_sorted_reference(case, K):
     seqs, ks, jobs, want = case

@@ -16,7 +16,8 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 @pytest.fixture(scope="module")
 def sim(tmp_path_factory):
     exe = os.fspath(tmp_path_factory.mktemp("mine") / "mine_sim")
-    subprocess.check_call(["g++", "-O2", "-std=c++17", "-I", os.path.join(REPO, "specimux_amd", "csrc"), "-o", exe,
+    subprocess.check_call(["g++", "-O2", "-std=c++17", "-I", os.path.join(REPO, "specimux_amd", "csrc"),
+                           "-I", os.path.join(REPO, "include"), "-o", exe,
                            os.path.join(REPO, "tests", "cpu", "mine_sim.cpp")])
     return exe
 

@@ -126,6 +126,43 @@ def test_distances_match_the_oracle(case):
     assert sum(int((w >= 0).sum()) for w in want) >= 600 and sum(int((w < 0).sum()) for w in want) >= 2000
 
 
+def test_distances_walk_over_many_short_runs(monkeypatch):
+    """The chunk walk (smx_mine_lds.h) where it can go wrong, all in state class 1: 701 jobs over six shared refs with runs
+    of one ref, more than 4096 runs, so that the owner search takes its third round; runs of two, three and one chunk
+    (jobs of 129, 257 and 1 reads), one chunk per workgroup, so that most workgroups start inside a run.  The reads are
+    drawn from a small pool, so the oracle aligns every distinct pair once; every distance of the call is compared."""
+    monkeypatch.setenv("SMX_NEAREST_MIN_CHUNKS", "18446744073709551615")      # runs of one ref
+    rng = random.Random(9)
+    refs = ["".join(rng.choice("ACGT") for _ in range(rng.randrange(12, 41))) for _ in range(6)]
+    pool = [(mutate(rng, rng.choice(refs), 0.02 * rng.randrange(10), "ACGT") or "A")[:40].ljust(12, "A") for _ in range(40)]
+    kref, kpool = [rng.choice((-1, 2, 5)) for _ in refs], [rng.choice((-1, 1, 4, 8)) for _ in pool]
+    table = np.empty((len(refs), len(pool)), dtype=np.int32)
+    for q, a in enumerate(refs):
+        for t, b in enumerate(pool):
+            d = align_c(a, b, NW, -1, iupac=False)["editDistance"]
+            k = -1 if kref[q] < 0 or kpool[t] < 0 else max(kref[q], kpool[t])
+            table[q, t] = d if k < 0 or d <= k else -1
+    sizes = [(129, 257, 1, 257)[j % 4] for j in range(701)]
+    ids = np.array([rng.randrange(len(pool)) for _ in range(sum(sizes))])
+    jobs, t0 = [], len(refs)
+    for nt in sizes:
+        jobs.append((0, len(refs), t0, nt))
+        t0 += nt
+    per_run = [(nt + 127) // 128 for nt in sizes for _ in refs]               # the chunks of every run, in launch order
+    assert len(per_run) > 4096 and sum(per_run) - len(per_run) > sum(per_run) // 2
+    seqs = [s.encode("latin-1") for s in refs + [pool[x] for x in ids]]
+    ks = kref + [kpool[x] for x in ids]
+    got = crosstalk.nearest_distances(seqs, ks, [0] * len(seqs), jobs)         # prefilled with a sentinel (-7)
+    assert len(got) == len(jobs)
+    n_in = n_out = 0
+    for j, (g, (_, _, t0, nt)) in enumerate(zip(got, jobs)):
+        w = table[:, ids[t0 - len(refs):t0 - len(refs) + nt]]
+        bad = np.argwhere(g != w)
+        assert g.shape == w.shape and bad.size == 0, (j, jobs[j], bad[:5].tolist(), [(int(g[q, t]), int(w[q, t])) for q, t in bad[:5]])
+        n_in, n_out = n_in + int((w >= 0).sum()), n_out + int((w < 0).sum())
+    assert n_in > 50000 and n_out > 50000
+
+
 def expected_keys(case):
     seqs, ks, groups, jobs, want = case
     owns, others = [], []

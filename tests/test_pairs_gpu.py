@@ -111,6 +111,34 @@ def test_distances_mixed_limits_and_empty_reads():
     assert want[(0, 1)] == -1 or want[(0, 1)] <= 40
 
 
+def test_distances_walk_over_many_short_rows():
+    """The chunk walk (smx_mine_lds.h) where it can go wrong, all in state class 1: fourteen jobs of about 300 reads, more
+    than 4096 rows, so that the owner search takes its third round; a job's rows own three, two and one chunk, so that
+    most workgroups of 8 chunks start inside a row; a chunk total that is no multiple of 8.  The reads are drawn from a
+    small pool, so the oracle aligns every distinct pair once; every distance of the call is compared."""
+    rng = random.Random(33)
+    pool = [rand_seq(rng, rng.randrange(12, 41)) for _ in range(24)]
+    pool += [(mutate(rng, r, 0.1) or r)[:40].ljust(12, "A") for r in pool]
+    kpool = [rng.choice((-1, 3, 6, 12)) for _ in pool]
+    table = np.array([[oracle_dist(a, b, pair_limit(ka, kb)) for b, kb in zip(pool, kpool)] for a, ka in zip(pool, kpool)],
+                     dtype=np.int64)
+    sizes = [300 + (j * 7) % 11 - 5 for j in range(14)]
+    ids = np.array([rng.randrange(len(pool)) for _ in range(sum(sizes))])
+    jobs = [(sum(sizes[:j]), n) for j, n in enumerate(sizes)]
+    per_row = [(n + 127) // 128 - (i + 1) // 128 for _, n in jobs for i in range(n - 1)]   # chunks of every row with a j > i
+    starts = np.concatenate([[0], np.cumsum(per_row)])
+    first = np.arange(0, starts[-1], 8)                                                    # every workgroup's first chunk
+    assert len(per_row) > 4096 and {1, 2, 3} == set(per_row)
+    assert starts[-1] % 8 != 0 and np.isin(first, starts, invert=True).mean() > 0.5
+    want = np.concatenate([table[ids[r0:r0 + n][i], ids[r0:r0 + n][j]] for r0, n in jobs for i, j in [np.triu_indices(n, 1)]])
+    assert (want >= 0).sum() > 50000 and (want == -1).sum() > 50000
+    rc, got, _ = pairs_raw([pool[x] for x in ids], [kpool[x] for x in ids], jobs)
+    assert rc == _lib.OK, _lib.load().smx_last_error()
+    bad = np.nonzero(got != want)[0]
+    assert got.size == want.size > 500000 and bad.size == 0, \
+        f"{bad.size} of {got.size} distances differ: {[(int(x), int(got[x]), int(want[x])) for x in bad[:10]]}"
+
+
 def neighbour_matrix(dist, n):
     """The host reduction of a job's distances: n x ceil(n / 32) words, bit j of row i = the pair is within its limit."""
     nw = (n + 31) // 32

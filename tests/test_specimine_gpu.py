@@ -114,6 +114,33 @@ def test_distances_one_query_many_targets_and_many_queries_one_target():
     check([(x, t, int(len(x) * 0.15)) for x in queries])
 
 
+def test_distances_walk_over_many_short_records():
+    """The chunk walk (smx_mine_lds.h) where it can go wrong, all in state class 1: more than 4096 (job, query) records, so
+    that the owner search takes its third round; records of one, two and three chunks in turn, so that most workgroups
+    of 8 chunks start inside a record; a chunk total that is no multiple of 8.  The sequences are drawn from two small
+    pools, so the oracle aligns every distinct pair once; every distance of the call is compared."""
+    rng = random.Random(14)
+    qpool = [rand_seq(rng, rng.randrange(12, 41)) for _ in range(48)]
+    kpool = [rng.choice((-1, 2, 5, 9)) for _ in qpool]
+    tpool = [rand_seq(rng, rng.randrange(12, 41)) if i % 2 else mutate(rng, qpool[i], 0.15)[:40].ljust(12, "A")
+             for i in range(48)]
+    table = np.array([[oracle_dist(q, t, k) for t in tpool] for q, k in zip(qpool, kpool)], dtype=np.int64)
+    n_rec = 4201
+    qid = [rng.randrange(48) for _ in range(n_rec)]
+    tid = np.array([rng.randrange(48) for _ in range(600)])
+    jobs = [(i, 1, rng.randrange(300), (1, 129, 257)[i % 3], 0.0) for i in range(n_rec)]
+    starts = np.concatenate([[0], np.cumsum([(j[3] + 127) // 128 for j in jobs])])      # the records' chunk prefix
+    first = np.arange(0, starts[-1], 8)                                                # every workgroup's first chunk
+    assert starts[-1] % 8 != 0 and np.isin(first, starts, invert=True).mean() > 0.5
+    want = np.concatenate([table[qid[i], tid[t0:t0 + nt]] for i, _, t0, nt, _ in jobs])
+    assert (want >= 0).sum() > 50000 and (want == -1).sum() > 50000
+    rc, got = mine_raw([qpool[x] for x in qid], [kpool[x] for x in qid], [tpool[x] for x in tid], jobs)
+    assert rc == _lib.OK, _lib.load().smx_last_error()
+    bad = np.nonzero(got != want)[0]
+    assert got.size == want.size > 500000 and bad.size == 0, \
+        f"{bad.size} of {got.size} distances differ: {[(int(x), int(got[x]), int(want[x])) for x in bad[:10]]}"
+
+
 # ---------------------------------------------------------------------------------------- edges of the kernel
 ALL_BYTES = "".join(map(chr, range(256)))
 
@@ -214,8 +241,8 @@ def test_generic_class_grid_stride():
     runs: each one rebuilds its LDS Peq for queries of other lengths and reuses its scratch slice."""
     rng = random.Random(22)
     long_q = rand_seq(rng, 130972)
-    # smx_calls.cpp, mine_call: cap = 256 MiB / slice, slice = 3 * W_max * MINE_THREADS * 8 bytes;
-    # per_block = max(MINE_BLOCK_CHUNKS, ceil(chunks / cap)), one chunk per query here (1-3 targets each)
+    # smx_chunk_plan.h, chunk_scratch_cap and chunk_grid: cap = 256 MiB / slice, slice = 3 * W_max * MINE_THREADS * 8
+    # bytes; per_block = max(MINE_BLOCK_CHUNKS, ceil(chunks / cap)), one chunk per query here (1-3 targets each)
     w_max = (len(long_q) + 63) // 64
     cap = (256 << 20) // (3 * w_max * 128 * 8)
     assert 40 <= cap <= 45
@@ -249,7 +276,7 @@ def test_generic_class_grid_stride():
 
 
 def lds_table_bytes(m, rows):
-    """LDS bytes of a query's Peq table (smx_calls.cpp, mine_call): MINE_LDS_HEAD words + (rows + 1) x (W | 1) words."""
+    """LDS bytes of a query's Peq table (smx_chunk_plan.h, chunk_table): MINE_LDS_HEAD words + (rows + 1) x (W | 1) words."""
     return (192 + (rows + 1) * (((m + 63) // 64) | 1)) * 8
 
 
