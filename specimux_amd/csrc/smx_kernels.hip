@@ -952,8 +952,18 @@ struct DemuxTile {
     // records}.  The last workgroup to get here zeroes the queue head; the last launch of a batch (aux.chain == 0) also
     // publishes the extra-record count and zeroes the rest, so a launch needs no memset in front of it (two small fills
     // per batch were ~2 % of a 0.4 ms launch).
+    //
+    // The fence in front of the count is a workgroup-scope release (a wait for this wave's outstanding memory operations),
+    // not __threadfence(): all the last workgroup consumes from the others are launch counters, and those are only ever
+    // touched by returning atomics -- the tile pops, the extra-record slots, the overflow appends of a compact launch --
+    // which execute at the memory side and had returned to their waves before the barrier in front of this call; the one
+    // plain read, tile_counter[1] by a redo workgroup, has likewise returned (a redo workgroup that leaves through setup()'s
+    // early exit has issued nothing else).  Records, `counts`, the overflow list are read
+    // after the kernel, or by the next one.  An agent-scope release is an L2 write-back per workgroup, 1280 of them on the
+    // launch's tail while the L2s hold the records just stored: about 10 us of every launch
+    // (profiles/ab_counter_stripes.txt; with every wave fencing, +90 us).
     __device__ __forceinline__ void workgroup_done() {
-        __threadfence();
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
         const unsigned prev = atomicAdd(tile_counter + 2, 1u);
         if (prev == gridDim.x - 1) {
             __threadfence();
