@@ -403,29 +403,41 @@ __device__ inline bool tied_has_global(const ReadCtx &c, int h, int gb) {
 // instead of three dependent ones (head of the chain, its primer masks, its pool): the scorer wave sits on a tile's
 // critical path and every dependent global load is most of a microsecond.  The flat tables are gone from the device:
 // five fewer pointers held in (spilled) SGPRs.
+// (load_specrec: the record's two 16-byte halves are requested together and pass through one point.  A plain struct copy
+// is taken apart by the compiler: `spec` first, the masks once it is known to be >= 0, `next` and `pool` where they are
+// used -- up to four dependent round trips for one 32-byte record.)
+__device__ __forceinline__ SpecRec load_specrec(const SpecRec *p) {
+    static_assert(sizeof(SpecRec) == 32 && offsetof(SpecRec, spec) == 16, "SpecRec layout");   // (tables are 16-byte aligned: blob_add)
+    uint4 a = ((const uint4 *)p)[0], b = ((const uint4 *)p)[1];
+    asm volatile("" : "+v"(a.x), "+v"(a.y), "+v"(a.z), "+v"(a.w), "+v"(b.x), "+v"(b.y), "+v"(b.z), "+v"(b.w));
+    SpecRec rec;
+    rec.p1m = ((unsigned long long)a.y << 32) | a.x; rec.p2m = ((unsigned long long)a.w << 32) | a.z;
+    rec.spec = (int)b.x; rec.next = (int)b.y; rec.pool = (int)b.z; rec.pad = (int)b.w;
+    return rec;
+}
 __device__ inline int specimen_exact(const DevPanel *P, int gb1, int gb2, int f, int r, int *pool_out = nullptr) {
-    SpecRec rec = P->pairrec[(size_t)gb1 * P->NB + gb2];
+    SpecRec rec = load_specrec(&P->pairrec[(size_t)gb1 * P->NB + gb2]);
     while (rec.spec >= 0) {
         if (((rec.p1m >> f) & 1) && ((rec.p2m >> r) & 1)) {
             if (pool_out) *pool_out = rec.pool;
             return rec.spec;
         }
         if (rec.next < 0) break;
-        rec = P->specrec[rec.next];
+        rec = load_specrec(&P->specrec[rec.next]);
     }
     return -1;
 }
 // Specimens.specimens_for_barcodes_and_primers (databases.py): how many specimens carry (b1, b2) with these primers, and
 // the first of them in file order
 __device__ inline void specimens_for(const DevPanel *P, int gb1, int gb2, int f, int r, int &first, int &cnt) {
-    SpecRec rec = P->pairrec[(size_t)gb1 * P->NB + gb2];
+    SpecRec rec = load_specrec(&P->pairrec[(size_t)gb1 * P->NB + gb2]);
     while (rec.spec >= 0) {
         if (((rec.p1m >> f) & 1) && ((rec.p2m >> r) & 1)) {
             cnt++;
             if (first < 0 || rec.spec < first) first = rec.spec;
         }
         if (rec.next < 0) break;
-        rec = P->specrec[rec.next];
+        rec = load_specrec(&P->specrec[rec.next]);
     }
 }
 
@@ -473,8 +485,11 @@ struct Emitter {
     bool overflow;
 };
 
-// create_write_operation (demultiplex.py:30-103) in index form.
-__device__ inline void emit_op(Emitter &E, const CandView *v, int cand_id, int sample, int rtype, int pool,
+// create_write_operation (demultiplex.py:30-103) in index form.  has_v = false: the record of a read without any
+// candidate; `v` is then a view the caller happens to have (or a dummy) and is not looked at.  (A `const CandView *` that
+// may be null kept the caller's view in scratch memory: every field the record takes was a dependent scratch load on the
+// scorer wave's critical path.)
+__device__ inline void emit_op(Emitter &E, const CandView &v, bool has_v, int cand_id, int sample, int rtype, int pool,
                                int barcode, unsigned xflags) {
     const ReadCtx &c = *E.c;
     smx_op op;
@@ -483,23 +498,23 @@ __device__ inline void emit_op(Emitter &E, const CandView *v, int cand_id, int s
     op.flags = (unsigned char)xflags;
     op.barcode = (short)barcode;
     int s = 0, e = c.L;
-    if (v) {
-        op.dist[0] = (int8_t)v->p1d; op.dist[1] = (int8_t)v->b1d; op.dist[2] = (int8_t)v->b2d; op.dist[3] = (int8_t)v->p2d;
-        op.p1 = (short)(v->p1 ? v->f : -1);
-        op.p2 = (short)(v->p2 ? v->r : -1);
-        if (v->o) op.flags |= SMX_OPF_REVERSE;
+    if (has_v) {
+        op.dist[0] = (int8_t)v.p1d; op.dist[1] = (int8_t)v.b1d; op.dist[2] = (int8_t)v.b2d; op.dist[3] = (int8_t)v.p2d;
+        op.p1 = (short)(v.p1 ? v.f : -1);
+        op.p2 = (short)(v.p2 ? v.r : -1);
+        if (v.o) op.flags |= SMX_OPF_REVERSE;
     } else {
         op.dist[0] = op.dist[1] = op.dist[2] = op.dist[3] = -1;
         op.p1 = op.p2 = -1;
     }
     bool fallback = false;
     if (c.trim != SMX_TRIM_NONE) {
-        if (v) {
+        if (has_v) {
             // Q8: the same CandidateMatch emitted earlier already had its locations shifted by the trim start of each of
             // those emissions.  One running sum per candidate: any number of emissions per read (a tie storm at a large
             // index distance emits one record per tied specimen, hundreds for one read).
             const int cum = E.cum[cand_id];
-            cand_extent(c, *v, cum, s, e);
+            cand_extent(c, v, cum, s, e);
             if (s < e) E.cum[cand_id] = cum + s;
         }
         if (s >= e) { fallback = true; s = 0; e = c.L; }   // Q12
@@ -534,11 +549,11 @@ __device__ inline void emit_op(Emitter &E, const CandView *v, int cand_id, int s
 __device__ inline void emit_partial_or_unknown(Emitter &E, const CandView &v, int cand_id, int pool) {
     const ReadCtx &c = *E.c;
     if (v.b1 && !v.b2 && c.hit(v.h1).ntied == 1)
-        emit_op(E, &v, cand_id, -1, SMX_R_PARTIAL_FWD, pool, global_bc(c, v.h1, c.hit(v.h1).first_tied), 0);
+        emit_op(E, v, true, cand_id, -1, SMX_R_PARTIAL_FWD, pool, global_bc(c, v.h1, c.hit(v.h1).first_tied), 0);
     else if (v.b2 && !v.b1 && c.hit(v.h2).ntied == 1)
-        emit_op(E, &v, cand_id, -1, SMX_R_PARTIAL_REV, pool, global_bc(c, v.h2, c.hit(v.h2).first_tied), 0);
+        emit_op(E, v, true, cand_id, -1, SMX_R_PARTIAL_REV, pool, global_bc(c, v.h2, c.hit(v.h2).first_tied), 0);
     else
-        emit_op(E, &v, cand_id, -1, SMX_R_UNKNOWN, pool, -1, 0);
+        emit_op(E, v, true, cand_id, -1, SMX_R_UNKNOWN, pool, -1, 0);
 }
 
 // Iterate the best-scoring candidates in find_candidate_matches order.
@@ -736,12 +751,12 @@ __device__ inline bool score_fast(Emitter &E, int ori, int sub, int G) {
     if (!lead) return true;
     const CandView v = cand_view(c, pair, o);
     const int pool = !has_v ? -1 : (sample >= 0 ? (spool != -2 ? spool : P->specrec[sample].pool) : c.LP.pair_pool[pair]);
-    emit_op(E, has_v ? &v : nullptr, pair * 2 + o, sample, rtype, pool, barcode, xflags);
-    for (int e = 1; e < repeat; e++) emit_op(E, &v, pair * 2 + o, -1, SMX_R_UNKNOWN, pool, -1, 0);   // rare
+    emit_op(E, v, has_v, pair * 2 + o, sample, rtype, pool, barcode, xflags);   // (best == 0: the view of candidate 0, not looked at)
+    for (int e = 1; e < repeat; e++) emit_op(E, v, true, pair * 2 + o, -1, SMX_R_UNKNOWN, pool, -1, 0);   // rare
     if (more1 >= 0) {   // rare
         for (int e = 0; e < 3; e++) {
             int sp = e == 0 ? more1 : (e == 1 ? more2 : more3);
-            if (sp >= 0) emit_op(E, &v, pair * 2 + o, sp, SMX_R_DEREP_FULL, P->specrec[sp].pool, -1, 0);
+            if (sp >= 0) emit_op(E, v, true, pair * 2 + o, sp, SMX_R_DEREP_FULL, P->specrec[sp].pool, -1, 0);
         }
     }
     return true;
@@ -760,8 +775,10 @@ __device__ inline void score_general(Emitter &E, int ori) {
             int sc = cand_score(v);
             best = sc > best ? sc : best;
         }
-    if (best == 0) {
-        emit_op(E, nullptr, 0, -1, SMX_R_UNKNOWN, -1, -1, 0);
+    if (best == 0) {   // (not reached from the kernel: score_fast emits this record itself, under either dereplicate mode;
+                       //  kept so that the function is whole on its own)
+        const CandView none = {};   // not looked at
+        emit_op(E, none, false, 0, -1, SMX_R_UNKNOWN, -1, -1, 0);
         return;
     }
     if (c.derep == SMX_DEREP_NONE) {   // demultiplex.py:181-197
@@ -773,9 +790,9 @@ __device__ inline void score_general(Emitter &E, int ori) {
                         int g1 = global_bc(c, v.h1, i), g2 = global_bc(c, v.h2, j);
                         specimens_for(P, g1, g2, v.f, v.r, first, cnt);
                     }
-                if (cnt > 1) emit_op(E, &v, cand_id, first, SMX_R_MULTIPLE, P->specrec[first].pool, -1, 0);
-                else if (cnt == 1) emit_op(E, &v, cand_id, first, SMX_R_FULL, P->specrec[first].pool, -1, 0);
-                else emit_op(E, &v, cand_id, -1, SMX_R_UNKNOWN, cand_pool, -1, SMX_OPF_NO_SPECIMEN);
+                if (cnt > 1) emit_op(E, v, true, cand_id, first, SMX_R_MULTIPLE, P->specrec[first].pool, -1, 0);
+                else if (cnt == 1) emit_op(E, v, true, cand_id, first, SMX_R_FULL, P->specrec[first].pool, -1, 0);
+                else emit_op(E, v, true, cand_id, -1, SMX_R_UNKNOWN, cand_pool, -1, SMX_OPF_NO_SPECIMEN);
             } else {
                 emit_partial_or_unknown(E, v, cand_id, cand_pool);
             }
@@ -816,7 +833,7 @@ __device__ inline void score_general(Emitter &E, int ori) {
                         if (k < wkey && cand_has_specimen(c, v, spec)) { wkey = k; wid = cand_id; }
                     })
                     CandView w = cand_view(c, wid >> 1, wid & 1);
-                    emit_op(E, &w, wid, spec, SMX_R_DEREP_FULL, P->specrec[spec].pool, -1, 0);
+                    emit_op(E, w, true, wid, spec, SMX_R_DEREP_FULL, P->specrec[spec].pool, -1, 0);
                 }
             if (!any && !none_done) {
                 // the None group sits where its first entry appeared; it holds every best candidate
@@ -826,7 +843,7 @@ __device__ inline void score_general(Emitter &E, int ori) {
                 FOR_BEST_CANDS(c, ori, best, {
                     if (cand_id < first_id) continue;
                     if (!cand_has_specimen(c, v, -1))
-                        emit_op(E, &v, cand_id, -1, SMX_R_UNKNOWN, cand_pool, -1, SMX_OPF_NO_SPECIMEN);
+                        emit_op(E, v, true, cand_id, -1, SMX_R_UNKNOWN, cand_pool, -1, SMX_OPF_NO_SPECIMEN);
                 })
             }
         })
@@ -865,7 +882,7 @@ __device__ inline void score_general(Emitter &E, int ori) {
             if (k < wkey) { wkey = k; wid = cand_id; }
         })
         CandView w = cand_view(c, wid >> 1, wid & 1);
-        emit_op(E, &w, wid, -1, SMX_R_UNKNOWN, c.LP.pair_pool[wid >> 1], -1, 0);
+        emit_op(E, w, true, wid, -1, SMX_R_UNKNOWN, c.LP.pair_pool[wid >> 1], -1, 0);
     }
 }
 
@@ -944,6 +961,7 @@ struct DemuxTile {
     int par, nr, nh, nI;        // cur's lens/ocnt buffer; reads, alignments, alignments with a record
     bool live;                  // false: nothing to do for `cur` (none yet, or a compact tile left to the redo launch)
     unsigned popped;
+    bool pop_issued;
     int *lensC, *ocntC;
     bool prelisted;
     int nq, nE_pre;
@@ -1000,6 +1018,21 @@ struct DemuxTile {
     __device__ __forceinline__ void stamp(int i) {
         asm volatile("" : "+v"(tid));
         if (timing) { unsigned long long _t = clock64(); tacc[i] += _t - tacc[10]; tacc[10] = _t; }
+    }
+
+    // The tile-queue pop: which tile this workgroup encodes next.  A returning device-scope atomic takes microseconds, so
+    // it is issued where the next vector-memory wait is farthest away -- the head of the barcode scan, which touches LDS
+    // only -- and its result is first looked at in zero_for_next.  The counter's offset goes through a VGPR: with an
+    // address the compiler can prove uniform, its atomic optimiser wraps the add in mbcnt / readfirstlane, and the
+    // readfirstlane waits for the result on the spot, whatever the source does with it.  (The offset, not the pointer: a
+    // laundered pointer becomes a flat atomic, which every LDS wait would wait for as well.)
+    __device__ __forceinline__ void pop_tile() {
+        if (tid == 0) {
+            unsigned off = 0;
+            asm volatile("" : "+v"(off));
+            popped = atomicAdd(tile_counter + off, 1u);
+        }
+        pop_issued = true;
     }
 
     // Everything that does not change during the launch.  Returns false when this workgroup has nothing to do at all (the
@@ -1728,6 +1761,7 @@ struct DemuxTile {
                 __syncthreads();
             }
             stamp(3);
+            if (!pop_issued) pop_tile();   // (the first round of the tile)
             phase3b_barcodes(nE);
             __syncthreads();
             stamp(4);
@@ -1815,8 +1849,22 @@ struct DemuxTile {
         uint32_t r0n;
         int nrn;
         tile_span(nxt, r0n, nrn);
+        // The tile's memory requests -- codes, flag bytes, lengths -- are all issued before the first of them is looked at:
+        // one round trip per lane and tile.  The length is requested INSIDE the item loops of the prescan paths, with
+        // the codes and flags of the item and in front of their one wait, and goes to LDS at the end of this function
+        // (nothing in it reads the LDS copy).  Stored at once it was a round trip of its own in front of the codes';
+        // requested in front of the loop it still was one: the compiler drains vmcnt in the preheader of a loop that loads.
         int *lensN = lensL + (par ^ 1) * R;
-        if (wid < nrn) lensN[wid] = lens[r0n + wid];
+        int len_n = 0;
+        bool have_len = false;
+        // (the offset passes through a VGPR inside the loop, or the loop-invariant load is hoisted back in front of it; a lane
+        // past the tile's reads asks for the length of a read of its item, or of the tile's first (tile_span keeps that one
+        // in range for an empty tile): no branch around the load)
+        auto load_len = [&](int r_item) {
+            unsigned off = r0n + (uint32_t)(wid < nrn ? wid : r_item);
+            asm volatile("" : "+v"(off));
+            return lens[off];
+        };
         // one 16-byte chunk: generic per-byte encode (short reads, search_len not a multiple of 16)
         auto encode_bytes = [&](int r, int L, int cpos, const uint4 &v) {
             int Sp = L < S ? L : S;
@@ -1871,14 +1919,21 @@ struct DemuxTile {
                 // tile-major, the tile's first read and read count multiples of four (every tile of a 64-read plan but a batch's
                 // last): item = (run = end * hc + chunk, four consecutive reads) -- one 16-byte load of their dwords and one dword
                 // of their flag bytes, both requested before either is looked at; 16 lanes cover a 256-byte run, and a 64-read
-                // tile is one item per lane: one memory round trip per tile where the dword-per-lane loop takes three to four.
+                // tile is one item per lane, two loads instead of the dword-per-lane loop's eight.
                 const int nq = nrn >> 2;
                 for (int ci = wid; ci < per * 16; ci += nw) {
                     const int run = ci >> 4, r = (ci & 15) * 4;
+                    // (first: behind the codes, the compiler moved one of their registers and waited for it; and in front of the
+                    // skip: in a tile of 32 reads or fewer, half of the lanes that hold a length have no item)
+                    len_n = load_len(0);
+                    have_len = true;
                     if ((ci & 15) >= nq) continue;
                     const int end = run >= hc ? 1 : 0, c = run - (end ? hc : 0);
-                    const uint4 z4 = *(const uint4 *)(aux.codes2 + tilecodes_word((size_t)(r0n + r), hc, end, c));
-                    const unsigned f4 = *(const unsigned *)(aux.naflag + r0n + r);
+                    uint4 z4 = *(const uint4 *)(aux.codes2 + tilecodes_word((size_t)(r0n + r), hc, end, c));
+                    unsigned f4 = *(const unsigned *)(aux.naflag + r0n + r);
+                    // (all results pass through here: left alone, the compiler waits for f4, then requests the codes, the
+                    // last dword of them only inside its own branch)
+                    asm volatile("" : "+v"(z4.x), "+v"(z4.y), "+v"(z4.z), "+v"(z4.w), "+v"(f4), "+v"(len_n));
                     if (!(f4 & 0xFFu)) fast(r, end, c, z4.x);
                     if (!(f4 & 0xFF00u)) fast(r + 1, end, c, z4.y);
                     if (!(f4 & 0xFF0000u)) fast(r + 2, end, c, z4.z);
@@ -1892,15 +1947,45 @@ struct DemuxTile {
             } else {
                 // a dword per lane.  Tile-major: item = (run, read slot of 64), a wave loads one run's 4 nrn contiguous bytes; the
                 // address is per read, as a tile may straddle two 1024-read DP tiles.
+                // Four items per lane and pass (a 64-read tile of 80-column windows is 640 items for 192 lanes: one pass), their
+                // eight loads requested before the first is used.
                 const unsigned permagic = (unsigned)((0x100000000ull + (unsigned)per - 1) / (unsigned)per);
-                for (int ci = wid; ci < (tiled ? per * 64 : nrn * per); ci += nw) {
-                    int r, rem;
-                    if (tiled) { r = ci & 63; rem = ci >> 6; if (r >= nrn) continue; }
+                const int nci = tiled ? per * 64 : nrn * per;
+                auto item_of = [&](int ci, int &r, int &end, int &c) {
+                    int rem;
+                    if (tiled) { r = ci & 63; rem = ci >> 6; }
                     else { r = (int)__umulhi((unsigned)ci, permagic); rem = ci - __mul24(r, per); }
-                    const int end = rem >= hc ? 1 : 0, c = rem - (end ? hc : 0);
-                    const unsigned z = aux.codes2[tiled ? tilecodes_word((size_t)(r0n + r), hc, end, c) : (size_t)r0n * per + ci];
-                    if (!aux.naflag[r0n + r]) fast(r, end, c, z);
-                    else slow(r, end, c);
+                    end = rem >= hc ? 1 : 0; c = rem - (end ? hc : 0);
+                    return ci < nci && r < nrn;
+                };
+                for (int ci0 = wid; ci0 < nci; ci0 += 4 * nw) {
+                    unsigned z[4], fl[4];
+#pragma unroll
+                    for (int u = 0; u < 4; u++) {
+                        const int ci = ci0 + u * nw;
+                        int r, end, c;
+                        // (an item past the end loads the tile's first word: a branch around a load is a wait per load)
+                        if (!item_of(ci, r, end, c)) r = end = c = 0;
+                        z[u] = aux.codes2[tiled ? tilecodes_word((size_t)(r0n + r), hc, end, c) : (size_t)r0n * per + (size_t)(__mul24(r, per) + end * hc + c)];
+                        fl[u] = aux.naflag[r0n + r];
+                        if (u == 0) len_n = load_len(r);   // (every lane of the tile's reads has a first item: nci >= nrn)
+                    }
+                    have_len = true;
+                    asm volatile("" : "+v"(z[0]), "+v"(z[1]), "+v"(z[2]), "+v"(z[3]), "+v"(fl[0]), "+v"(fl[1]), "+v"(fl[2]), "+v"(fl[3]), "+v"(len_n));
+                    unsigned slow_u = 0;   // flagged reads (rare): after the others, in a loop of their own
+#pragma unroll
+                    for (int u = 0; u < 4; u++) {
+                        int r, end, c;
+                        if (!item_of(ci0 + u * nw, r, end, c)) continue;
+                        if (!fl[u]) fast(r, end, c, z[u]);
+                        else slow_u |= 1u << u;
+                    }
+#pragma nounroll
+                    for (; slow_u; slow_u &= slow_u - 1u) {
+                        int r, end, c;
+                        item_of(ci0 + (__ffs((int)slow_u) - 1) * nw, r, end, c);
+                        slow(r, end, c);
+                    }
                 }
             }
         } else if (!sp && (S & 15) == 0) {
@@ -1943,6 +2028,11 @@ struct DemuxTile {
                 int r = ci / chunks;
                 encode_bytes(r, lens[r0n + r], (ci - r * chunks) * 16, src[ci]);
             }
+        }
+        if (wid < nrn) {
+            // (no item of its own: the ASCII paths, search_len 16 on a 64-read tile)
+            if (!have_len) len_n = lens[r0n + wid];
+            lensN[wid] = len_n;
         }
         if (timing_enc) tacc[8] += clock64() - t_enc0;
     }
@@ -1987,11 +2077,10 @@ struct DemuxTile {
             // every phase and ends up spilled to scratch (HBM traffic, reload latency); recomputing it is a few ALU ops
             asm volatile("" : "+v"(tid));
             const bool have = cur != 0xFFFFFFFFu;
-            // the tile to encode during this iteration: the queue pop is issued here, its result is only parked in LDS after
-            // the barcode phases (a returning global atomic takes microseconds; storing it at once stalled wave 0, and with
-            // it the first barrier of every tile)
+            // the tile to encode during this iteration: popped at the head of the barcode scan (pop_tile), parked in LDS by
+            // zero_for_next
             popped = 0;
-            if (tid == 0) popped = atomicAdd(tile_counter, 1u);
+            pop_issued = false;
             r0 = 0u;
             nr = 0;
             if (have) tile_span(cur, r0, nr);
@@ -2009,6 +2098,7 @@ struct DemuxTile {
                     phase3_rounds();
                 }
             }
+            if (!pop_issued) pop_tile();   // no barcode scan in this iteration: the pipeline's fill, a tile without a primer hit
             zero_for_next();
             stamp(0);
             // ---- phase 4 || phase 1: the scorer of this tile (lowest wave(s), one lane per read) runs beside the
