@@ -46,7 +46,8 @@
 extern "C" {
 #endif
 
-#define SMX_ABI_VERSION 10
+#define SMX_ABI_VERSION 11   /* goes up with every change of this file's declarations, additions included: the binding
+                              * (specimux_amd/_lib.py) refuses a library of another number */
 
 typedef enum {
     SMX_OK = 0,
@@ -167,6 +168,48 @@ size_t smx_counts_len(const smx_panel *panel);      /* SMX_CNT_SPECIMEN0 + n_spe
 size_t smx_window_stride(const smx_panel *panel);   /* bytes per read in the window buffer: round16(2*search_len) */
 size_t smx_hits_per_read(const smx_panel *panel);   /* 2 * n_primers */
 size_t smx_bdist_per_read(const smx_panel *panel);  /* 2 * n_primers * max barcodes per primer */
+
+/*
+ * What smx_panel_create admits; anything else is SMX_ERR_UNSUPPORTED with the limit in the message:
+ *   distinct primers 1..64, primer pairs 1..127, distinct barcodes 1..2048, barcodes on one primer 1..1024,
+ *   primer length 1..64 with 0 <= k < length, barcode length 1..32 with 0 <= k_index < length,
+ *   barcode_len_max + k_index <= 200, prefilter_min_len 0 or >= 2, search_len 1..256,
+ *   and every tile plan the panel can launch (lean, slots, compact) within the LDS pool of a CU, 159744 bytes.  The last
+ *   rule is what bounds large barcode lists in practice: the per-barcode ("slots") kernel keeps 64 bytes per distinct
+ *   barcode of the panel, the count rounded up to a power of two.  Up to 1024 distinct barcodes that is 64 KiB; from
+ *   1025 to 2048 it is 128 KiB and few panels still fit ("The admitted envelope"); above 2048 none can.  A
+ *   panel with a plan over the pool is refused as a whole -- not accepted for the lean kernel and refused at the first
+ *   --trim tails launch.
+ *
+ * smx_panel_plan: the launch plan smx_panel_create made, for inspection and tests.  Host only: no device is needed
+ * or touched.  Per mode -- lean, slots (--trim tails where the lean kernel cannot report the extent, the d_bdist dump),
+ * compact (panels with many primers; R = 0: the panel never launches it) -- the reads per tile, the dynamic LDS of one
+ * workgroup, and the row (primer word bits, barcode scan variant, dense 0 / compact 1 / redo 2, default-flags
+ * specialisation) of the kernel's instantiation list a launch gets: variant[1] with the primer prescan in front of it,
+ * variant[0] without (a panel launches the one its pre_ok names; compact tiles exist with the prescan only, their variant[0]
+ * is all zero).  With nitems > 0 every lean launch is a compact launch followed by a dense lean launch over the tiles
+ * the compact one could not hold: that launch takes the lean tile and the rows redo[].  MBW .. CAPE are the tile layout's
+ * sizes as the kernel computes them, SMX_TEST_CAPS applied.
+ */
+typedef struct smx_plan_variant { int32_t wbits, bsv, cm, sp; } smx_plan_variant;
+typedef struct smx_plan_mode {
+    int32_t R;                   /* reads per tile */
+    uint32_t lds_bytes;          /* dynamic LDS of one workgroup */
+    smx_plan_variant variant[2]; /* [0] launched without the prescan, [1] with it */
+    int32_t MBW;                 /* tie-mask words per hit: ceil(max barcodes on one primer / 32) */
+    int32_t G;                   /* barcode slots per hit: that maximum rounded up to a power of two */
+    int32_t CAPH, CAPE;          /* hits and (hit, location) entries of one barcode round */
+} smx_plan_mode;
+typedef struct smx_plan_info {
+    uint32_t lds_pool;           /* LDS a CU gives to workgroups: no lds_bytes above is larger */
+    int32_t nitems;              /* records per compact tile; 0: no compact tiles */
+    int32_t use64;               /* 64-bit primer words (a primer longer than 32 nt) */
+    int32_t bs_ok;               /* bit-sliced barcode scan: one barcode length <= 16, k_index <= 7 */
+    int32_t pre_ok, pre_tile;    /* primer prescan in front of every launch; it hands tile-major codes on */
+    smx_plan_mode lean, slots, compact;
+    smx_plan_variant redo[2];    /* the dense lean launch behind a compact one */
+} smx_plan_info;
+int smx_panel_plan(const smx_panel *panel, smx_plan_info *out);
 
 /*
  * Cut the two end windows of each read (host, no device work): for read i with bases

@@ -235,9 +235,12 @@ def setup_params(panel, search_len=80, index_edit_distance=-1, primer_edit_dista
     combined = b1s + [revcomp(b) for b in b2s]
     if len(combined) <= 1:
         raise TypeError("need at least two barcodes to derive the index threshold (Q14)")
-    min_bc = min(E.align(a, b, E.NW, -1, iupac=False)["editDistance"]
-                 for a, b in itertools.combinations(combined, 2))
-    k_idx = math.ceil(min_bc / 2.0) if index_edit_distance == -1 else index_edit_distance
+    if index_edit_distance == -1:
+        min_bc = min(E.align(a, b, E.NW, -1, iupac=False)["editDistance"]
+                     for a, b in itertools.combinations(combined, 2))
+        k_idx = math.ceil(min_bc / 2.0)
+    else:   # (the reference aligns all pairs here too and drops the result: half a million alignments at 1000 barcodes)
+        k_idx = index_edit_distance
     thr = {}
     for p in panel.get_primers(FWD) + panel.get_primers(REV):
         thr[p.primer] = primer_edit_distance if primer_edit_distance != -1 else int(bp_adjusted_length(p.primer) / 3)

@@ -9,7 +9,7 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SMX_LIB") or os.path.join(_HERE, "libsmx.so")   # SMX_LIB: A/B builds (tools/tune.sh)
 
-ABI_VERSION = 10
+ABI_VERSION = 11
 OK, ERR_ARG, ERR_UNSUPPORTED, ERR_DEVICE, ERR_OVERFLOW = 0, -1, -2, -3, -4
 TRIM = {"none": 0, "tails": 1, "barcodes": 2, "primers": 3}
 DEREP = {"none": 0, "best": 1}
@@ -52,6 +52,21 @@ class PanelDesc(C.Structure):
                 ("want_starts", C.c_int32)]
 
 
+class PlanVariant(C.Structure):
+    _fields_ = [("wbits", C.c_int32), ("bsv", C.c_int32), ("cm", C.c_int32), ("sp", C.c_int32)]
+
+
+class PlanMode(C.Structure):
+    _fields_ = [("R", C.c_int32), ("lds_bytes", C.c_uint32), ("variant", PlanVariant * 2), ("MBW", C.c_int32),
+                ("G", C.c_int32), ("CAPH", C.c_int32), ("CAPE", C.c_int32)]
+
+
+class PlanInfo(C.Structure):
+    _fields_ = [("lds_pool", C.c_uint32), ("nitems", C.c_int32), ("use64", C.c_int32), ("bs_ok", C.c_int32),
+                ("pre_ok", C.c_int32), ("pre_tile", C.c_int32), ("lean", PlanMode), ("slots", PlanMode),
+                ("compact", PlanMode), ("redo", PlanVariant * 2)]
+
+
 # every symbol include/smx.h declares: (name, restype, argtypes)
 _P = C.c_void_p
 SYMBOLS = [
@@ -64,6 +79,7 @@ SYMBOLS = [
     ("smx_window_stride", C.c_size_t, [_P]),
     ("smx_hits_per_read", C.c_size_t, [_P]),
     ("smx_bdist_per_read", C.c_size_t, [_P]),
+    ("smx_panel_plan", C.c_int, [_P, C.POINTER(PlanInfo)]),
     ("smx_pack_windows", C.c_int, [_P, _P, C.c_uint32, C.c_int32, _P, _P]),
     ("smx_batch_run_device", C.c_int, [_P, _P, _P, _P, C.c_uint32, _P, _P, C.c_uint32, _P, _P, _P, _P]),
     ("smx_batch_run", C.c_int, [_P, _P, _P, C.c_uint32, _P, _P, C.c_uint32, C.POINTER(C.c_uint32), _P, _P, _P]),

@@ -149,7 +149,11 @@ int smx_prescan_occupancy(int S, int mr, int nx, int tile, size_t lds_t, int *bl
 int smx_prescan_transpose_threads(int S);
 size_t smx_demux_lds_bytes(const smx::DevPanel *P, int use64, int R, int slots, int nitems);
 int smx_set_demux_lds_limit(int use64, size_t bytes);
-int smx_demux_sp_query(const smx::DevPanel *P, int use64, int use_slots, int cm, int R, int nitems, int have_prescan);
+// The instantiation row (cm: 0 dense, 1 compact, 2 redo) a launch with these parameters gets and, with sizes != nullptr, the
+// MBW, G, CAPH and CAPE of its tile layout (nitems: what the launch passes -- 0 for the dense and redo launches).  For
+// plan_tiles and smx_panel_plan.  Nonzero: the library holds no such instantiation.
+int smx_demux_plan_query(const smx::DevPanel *P, int use64, int use_slots, int cm, int R, int nitems, int have_prescan,
+                         smx_plan_variant *row, smx_plan_mode *sizes);
 int smx_query_occupancy(const smx::DevPanel *P, int use64, int use_slots, int cm, int R, int nitems, size_t lds_bytes,
                         int *blocks_per_cu, int have_prescan);
 int smx_launch_align(void *stream, const unsigned long long *d_peq, const unsigned long long *d_rpeq, int m,

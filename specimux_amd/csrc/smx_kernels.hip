@@ -2292,11 +2292,6 @@ DemuxVariant demux_variant(const smx::DevPanel *P, int use64, int use_slots, int
 }
 }  // namespace
 
-// which default-flags instantiation a launch with these parameters would get (0: the generic kernel)
-extern "C" int smx_demux_sp_query(const smx::DevPanel *P, int use64, int use_slots, int cm, int R, int nitems, int have_prescan) {
-    return demux_variant(P, use64, use_slots, cm, R, nitems, have_prescan != 0).sp;
-}
-
 extern "C" int smx_launch_demux(const smx::DevPanel *P, int use64, int use_slots, const smx::TilePlan *plan, int grid,
                                 const smx::DemuxBatch *b, const smx::DemuxAux *aux_in) {
     smx::DemuxAux aux = *aux_in;
@@ -2321,14 +2316,32 @@ extern "C" int smx_launch_demux(const smx::DevPanel *P, int use64, int use_slots
     return (int)(e != hipSuccess ? e : hipGetLastError());
 }
 
+// The layout of a tile of R reads (nitems > 0: a compact tile with that many records) as DemuxTile::setup computes it from the
+// same panel: the default-flags kernels are only selected where their constants are the panel's values.
+static smx::TileLayout panel_layout(const smx::DevPanel *P, int use64, int R, int slots, int nitems, bool test_caps) {
+    const smx::LayoutArgs la = smx::layout_args(P->NP, P->NB, P->n_pbc, P->NPAIR, P->trim);
+    auto layout = [&](auto w) {
+        return smx::make_layout<decltype(w)>(P->NP, P->NB, P->S, R, P->maxB, P->need_starts, la.npmeta, P->kidx, slots, P->bs_ok,
+                                             la.ncand, test_caps ? P->cap_hits : 0, test_caps ? P->cap_ents : 0, nitems, la.tails,
+                                             P->n_bstab);
+    };
+    return use64 ? layout(smx_w64()) : layout(smx_w32());
+}
+
 // LDS bytes of a tile of R reads (nitems > 0: a compact tile with that many records).  The test caps only shrink a tile.
 extern "C" size_t smx_demux_lds_bytes(const smx::DevPanel *P, int use64, int R, int slots, int nitems) {
-    const smx::LayoutArgs la = smx::layout_args(P->NP, P->NB, P->n_pbc, P->NPAIR, P->trim);
-    auto total = [&](auto w) {
-        return (size_t)smx::make_layout<decltype(w)>(P->NP, P->NB, P->S, R, P->maxB, P->need_starts, la.npmeta, P->kidx, slots, P->bs_ok,
-                                                     la.ncand, 0, 0, nitems, la.tails, P->n_bstab).total;
-    };
-    return use64 ? total(smx_w64()) : total(smx_w32());
+    return (size_t)panel_layout(P, use64, R, slots, nitems, false).total;
+}
+
+extern "C" int smx_demux_plan_query(const smx::DevPanel *P, int use64, int use_slots, int cm, int R, int nitems, int have_prescan,
+                                    smx_plan_variant *row, smx_plan_mode *sizes) {
+    const DemuxVariant v = demux_variant(P, use64, use_slots, cm, R, nitems, have_prescan != 0);
+    *row = {v.wbits, v.bsv, v.cm, v.sp};
+    if (sizes) {
+        const smx::TileLayout t = panel_layout(P, use64, R, use_slots, nitems, true);
+        sizes->MBW = t.MBW; sizes->G = t.G; sizes->CAPH = t.CAPH; sizes->CAPE = t.CAPE;
+    }
+    return demux_fn(v) ? 0 : 1;
 }
 
 extern "C" int smx_set_demux_lds_limit(int use64, size_t bytes) {

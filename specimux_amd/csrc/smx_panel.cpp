@@ -69,7 +69,9 @@ static void plan_tiles(const smx::DevPanel &h, int use64, bool pre_ok, const Swi
     for (int R = 64; R >= 8; R -= 8) {
         const size_t need = need_c(R);
         if (need > SMX_LDS_POOL || lds_blocks(need) < 3) continue;
-        if (smx_demux_sp_query(&h, use64, 0, 1, R, items, 1) != 0) {
+        smx_plan_variant row;
+        (void)smx_demux_plan_query(&h, use64, 0, 1, R, items, 1, &row, nullptr);
+        if (row.sp != 0) {
             if (R != best_R) { best_R = R; best_blocks = std::min(4, lds_blocks(need)); best_need = need; }
             break;
         }
@@ -88,7 +90,9 @@ int smx_panel_create(const smx_panel_desc *d, smx_panel **out) {
     if (NP <= 0 || NB <= 0 || NS <= 0 || NPAIR <= 0) return fail(SMX_ERR_ARG, "empty panel");
     if (NP > 64) return fail(SMX_ERR_UNSUPPORTED, "more than 64 distinct primers (%d)", NP);
     if (NPAIR > 127) return fail(SMX_ERR_UNSUPPORTED, "more than 127 primer pairs (%d)", NPAIR);
-    if (NB > 4096) return fail(SMX_ERR_UNSUPPORTED, "more than 4096 distinct barcodes (%d)", NB);   // (b1, b2) table: 32 B per pair
+    // the per-barcode ("slots") kernel keeps a Peq table of 64 bytes per barcode in LDS, the count rounded up to a power of
+    // two: 4096 slots are 262 144 bytes, more than a CU has.  Up to 2048 the LDS check at the end decides.
+    if (NB > 2048) return fail(SMX_ERR_UNSUPPORTED, "more than 2048 distinct barcodes (%d)", NB);
     if (d->search_len < 1 || d->search_len > 256)
         return fail(SMX_ERR_UNSUPPORTED, "search_len %d outside 1..256", d->search_len);
     if (d->k_index < 0 || d->k_index > 32) return fail(SMX_ERR_UNSUPPORTED, "index edit distance %d outside 0..32", d->k_index);
@@ -154,7 +158,7 @@ int smx_panel_create(const smx_panel_desc *d, smx_panel **out) {
             // (every DP instantiation fits its registers on tile codes without scratch: profiles/ab_tile_codes.txt)
             P->pre_tile = NP <= 2 && !sw.prescan_planes;
             P->pre_lds = smx_prescan_lds_bytes(h.S, P->pre_tile);
-            if (P->pre_lds > 160 * 1024) P->pre_ok = false;
+            if (P->pre_lds > SMX_LDS_POOL) P->pre_ok = false;
         }
     }
     if (maxB > 1024) return fail(SMX_ERR_UNSUPPORTED, "more than 1024 barcodes on one primer (%d)", maxB);
@@ -256,9 +260,37 @@ int smx_panel_create(const smx_panel_desc *d, smx_panel **out) {
 
     P->use64 = maxm > 32 ? 1 : 0;
     plan_tiles(h, P->use64, P->pre_ok, sw, P->plan, &P->nitems);
-    if (P->plan[LEAN].lds > 160 * 1024 || P->plan[SLOTS].lds > 160 * 1024)
-        return fail(SMX_ERR_UNSUPPORTED, "panel needs %zu bytes of LDS per read tile", std::max(P->plan[LEAN].lds, P->plan[SLOTS].lds));
+    // Every plan the panel can launch fits the pool, or the panel is refused as a whole: a panel that ran until the first
+    // --trim tails or d_bdist launch would be the worse surprise ("The admitted envelope").
+    static const char *const mode_name[N_MODES] = {"lean", "slots", "compact"};
+    for (int m = 0; m < N_MODES; m++)
+        if (P->plan[m].lds > SMX_LDS_POOL)
+            return fail(SMX_ERR_UNSUPPORTED, "the %s tiles of %d read(s) (%d primers, %d barcodes, %d on one primer) do not fit the LDS (%zu > %zu bytes)",
+                        mode_name[m], P->plan[m].R, NP, NB, maxB, P->plan[m].lds, SMX_LDS_POOL);
     *out = owner.release();
+    return SMX_OK;
+}
+
+int smx_panel_plan(const smx_panel *P, smx_plan_info *out) {
+    if (!P || !out) return fail(SMX_ERR_ARG, "null argument");
+    memset(out, 0, sizeof(*out));
+    out->lds_pool = (uint32_t)SMX_LDS_POOL;
+    out->nitems = P->nitems; out->use64 = P->use64; out->bs_ok = P->hp.bs_ok;
+    out->pre_ok = P->pre_ok ? 1 : 0; out->pre_tile = P->pre_tile ? 1 : 0;
+    smx_plan_mode *const modes[N_MODES] = {&out->lean, &out->slots, &out->compact};
+    for (int m = 0; m < N_MODES; m++) {
+        if (m == COMPACT && P->nitems == 0) continue;
+        const TilePlan &t = P->plan[m];
+        const int items = m == COMPACT ? P->nitems : 0;
+        modes[m]->R = t.R; modes[m]->lds_bytes = (uint32_t)t.lds;
+        for (int pre = m == COMPACT ? 1 : 0; pre < 2; pre++)
+            if (smx_demux_plan_query(&P->hp, P->use64, m == SLOTS, m == COMPACT, t.R, items, pre, &modes[m]->variant[pre], modes[m]) != 0)
+                return fail(SMX_ERR_UNSUPPORTED, "no instantiation of the demux kernel for the %s launch", m == SLOTS ? "slots" : m == COMPACT ? "compact" : "lean");
+    }
+    if (P->nitems > 0)
+        for (int pre = 0; pre < 2; pre++)
+            if (smx_demux_plan_query(&P->hp, P->use64, 0, 2, P->plan[LEAN].R, 0, pre, &out->redo[pre], nullptr) != 0)
+                return fail(SMX_ERR_UNSUPPORTED, "no instantiation of the demux kernel for the redo launch");
     return SMX_OK;
 }
 
@@ -496,6 +528,7 @@ int smx_batch_run_device(const smx_panel *Pc, void *stream, const uint8_t *d_win
             unsigned n_ovf = 0;
             (void)hipMemcpyAsync(&n_ovf, tc + 1, sizeof(unsigned), hipMemcpyDeviceToHost, (hipStream_t)stream);
             (void)hipStreamSynchronize((hipStream_t)stream);
+            // (tests read the two numbers from this line: tests/test_panel_limits_gpu.py, tests/test_gpu_parity.py)
             fprintf(stderr, "[smx] compact launch: %u of %u tiles left to the redo launch\n", n_ovf, (n_reads + comp.R - 1) / comp.R);
         }
         // the redo launch usually finds an empty list: one workgroup per CU is enough to start with (its workgroups

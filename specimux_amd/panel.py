@@ -27,6 +27,8 @@ class CompiledPanel:
         primers = list(specimens._primers.values())
         if not primers:
             raise ValueError("no primers registered")
+        if len(primers) > 64:   # smx_panel_create's limit and its words: the 64-bit specimen masks below cannot hold more
+            raise _lib.SmxError(_lib.ERR_UNSUPPORTED, f"more than 64 distinct primers ({len(primers)})")
         self.primers = primers
         self.primer_names = [p.name for p in primers]
         pidx = {id(p): i for i, p in enumerate(primers)}
@@ -140,6 +142,28 @@ class CompiledPanel:
         """The caller keeps n batches in flight on n streams (smx_panel_set_streams): each demux launch then takes 1/n of
         the CUs' workgroup slots and kernels of different batches run side by side."""
         _lib.check(self._lib.smx_panel_set_streams(self.handle, int(n)))
+
+    def plan(self):
+        """The launch plan of this panel (smx_panel_plan; host only): .lds_pool, .nitems, .use64, .bs_ok, .pre_ok, .pre_tile,
+        and per mode .lean / .slots / .compact (None when the panel has no compact tiles) with .R, .lds, .MBW, .G, .CAPH,
+        .CAPE, .variants = the (wbits, bsv, cm, sp) rows (without, with) the prescan and .variant = the one of them this
+        panel launches.  .redo / .redo_variants likewise for the dense launch behind a compact one (None without)."""
+        from types import SimpleNamespace as NS
+        info = _lib.PlanInfo()
+        _lib.check(self._lib.smx_panel_plan(self.handle, C.byref(info)))
+        pre = 1 if info.pre_ok else 0
+
+        def rows(v):
+            return tuple((r.wbits, r.bsv, r.cm, r.sp) for r in v)
+
+        def mode(m):
+            v = rows(m.variant)
+            return NS(R=m.R, lds=m.lds_bytes, MBW=m.MBW, G=m.G, CAPH=m.CAPH, CAPE=m.CAPE, variants=v, variant=v[pre])
+        compact = info.nitems > 0
+        redo = rows(info.redo) if compact else None
+        return NS(lds_pool=info.lds_pool, nitems=info.nitems, use64=bool(info.use64), bs_ok=bool(info.bs_ok),
+                  pre_ok=bool(info.pre_ok), pre_tile=bool(info.pre_tile), lean=mode(info.lean), slots=mode(info.slots),
+                  compact=mode(info.compact) if compact else None, redo_variants=redo, redo=redo[pre] if compact else None)
 
     def close(self):
         if self.handle is not None:

@@ -751,11 +751,14 @@ def test_generic_kernel_on_default_flags(lib, c2, c3, monkeypatch, env):
 
 
 @pytest.mark.parametrize("shape", ["mixed_lengths", "24nt_barcodes", "96x4_multiword", "16nt_barcodes_k5"])
-def test_compact_tiles_other_scan_variants(lib, tmp_path_factory, monkeypatch, shape):
+def test_compact_tiles_other_scan_variants(lib, tmp_path_factory, monkeypatch, capfd, shape):
     """Compact tiles under the barcode-scan variants the default panels do not reach: the per-barcode lean scan (mixed
     lengths, 24-nt barcodes), three tie-mask words per hit, the k 4..7 bit-sliced scan -- forced on, with a record
-    capacity that every tile fits and one that sends most tiles through the overflow list and the redo launch."""
+    capacity that every tile fits and one that sends most tiles through the overflow list and the redo launch: both
+    read from the overflow count of every compact launch (SMX_DEBUG_OVERFLOW)."""
+    import re
     from specimux_amd import synth
+    monkeypatch.setenv("SMX_DEBUG_OVERFLOW", "1")
     flags = {}
     if shape == "mixed_lengths":
         pan, (pf, sf) = _custom_panel(tmp_path_factory, "cm_" + shape, 8, 6, 13, 6, mixed=True)
@@ -770,13 +773,19 @@ def test_compact_tiles_other_scan_variants(lib, tmp_path_factory, monkeypatch, s
         flags = dict(index_edit_distance=5)
     rs = synth.make_reads(pan, 600, 123, windows_only=False, n_frac=0.03)
     reads = reads_from_set(rs, range(600), 80)
-    for items in ("176", "120"):   # every tile fits / most tiles go through the overflow list (measured with SMX_DEBUG_OVERFLOW)
+    for items in ("176", "120"):   # every tile fits / most tiles go through the overflow list
         monkeypatch.setenv("SMX_COMPACT_ITEMS", items)
         for fl in (flags, dict(flags, trim="primers")):
             both = Both(pf, sf, **fl)
+            capfd.readouterr()
             both.assert_hits_equal(reads[:100], f"compact {shape} {fl} {items}", lean=True)
             got = both.assert_ops_equal(reads, f"compact {shape} {fl} {items}")
             assert sum(1 for k in got if k[6] == "DEREP") > 100
+            launches = re.findall(r"compact launch: (\d+) of (\d+) tiles left to the redo launch", capfd.readouterr().err)
+            left, tiles = sum(int(a) for a, _b in launches), sum(int(b) for _a, b in launches)
+            print(f"compact {shape} {fl} items {items}: {left} of {tiles} tiles left to the redo launch")
+            assert len(launches) == 2 and tiles > 0
+            assert left == 0 if items == "176" else 2 * left > tiles, (items, left, tiles)
 
 
 # ------------------------------------------------------------------ randomised evidence inside the suite

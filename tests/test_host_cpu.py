@@ -111,6 +111,13 @@ def test_panel_limits_fail_loudly(tmp_path):
     with pytest.raises(_lib.SmxError) as ei:
         compiled_panel(both.specimens, both.parameters, both.args, both.prefilter)
     assert ei.value.code == _lib.ERR_UNSUPPORTED and "length 68" in str(ei.value)
+    # the largest primer that is admitted compiles to a plan on 64-bit primer words within the LDS pool (every other limit,
+    # from both sides: tests/test_panel_limits_cpu.py)
+    pf.write_text(">F pool=X position=forward\n" + "ACGT" * 16 + "\n>R pool=X position=reverse\nTCCTCCGCTTATTGATATGC\n")
+    both = Both(os.fspath(pf), os.fspath(sf))
+    plan = compiled_panel(both.specimens, both.parameters, both.args, both.prefilter).plan()
+    assert plan.use64 and not plan.pre_ok and plan.lean.variant[0] == 64
+    assert max(plan.lean.lds, plan.slots.lds) <= plan.lds_pool == 159744
 
 
 def test_pack_windows():
