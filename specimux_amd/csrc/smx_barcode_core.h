@@ -1,6 +1,6 @@
-// smx_barcode_core.h -- the bit-sliced barcode scans of the demux kernel's lean mode (phase 3b / 3c of smx_kernels.hip)
+// smx_barcode_core.h -- the bit-sliced barcode scans of the demux kernel's lean mode (phase 3b / 3c of smx_demux_tile.h)
 // and the host-side fill of their tables.  Which scan and which padded height M a barcode length runs at is decided at
-// the call sites in smx_kernels.hip (phase3b_barcodes, phase3c_summary).
+// the call sites in DemuxTile (phase3b_barcodes, phase3c_summary).
 //
 // This header is host/device code: the kernel and the CPU unit test (tests/cpu/barcode_sim.cpp) run the same functions;
 // on the host the table block and the target codes are plain arrays and a "lane" is one call.  The only device-only
@@ -12,15 +12,8 @@
 #ifndef SMX_BARCODE_CORE_H
 #define SMX_BARCODE_CORE_H
 
+#include "smx_hd.h"
 #include "smx_bitslice_core.h"
-
-#ifndef SMX_HD
-#if defined(__HIPCC__)
-#define SMX_HD __host__ __device__ __forceinline__
-#else
-#define SMX_HD inline
-#endif
-#endif
 
 namespace smx {
 

@@ -3,13 +3,7 @@
 #ifndef SMX_BITSLICE_CORE_H
 #define SMX_BITSLICE_CORE_H
 
-#ifndef SMX_HD
-#if defined(__HIPCC__)
-#define SMX_HD __host__ __device__ __forceinline__
-#else
-#define SMX_HD inline
-#endif
-#endif
+#include "smx_hd.h"
 
 namespace smx {
 

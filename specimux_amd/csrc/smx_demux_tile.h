@@ -1,4 +1,5 @@
-// smx_kernels.hip -- gfx950 (MI355X / CDNA4) kernels of the specimux hot path.
+// smx_demux_tile.h -- the demux kernel of the specimux hot path for gfx950 (MI355X / CDNA4): DemuxTile (phases 0-3 and 5,
+// the tile loop) and demux_kernel.  Phase 4 is smx_scorer.h, the LDS layout smx_demux_layout.h; smx_demux.hip instantiates.
 //
 // A read batch takes three kernels on one stream.  The two prescan kernels (smx_prescan.hip) come first: the first turns
 // the windows into 2-bit codes and one "not plain ACGT" flag byte per read -- tile-major codes alone for panels of at most
@@ -37,226 +38,16 @@
 // rates of tools/ubench (bit-ops / add / sub / v_bitop3 are fast; shifts, min, compares, SDWA and three-source VOP3
 // forms are about half rate; generic integer division is avoided in per-item code).  See DESIGN.md for the data
 // layout, the exactness arguments and the rooflines.
+#ifndef SMX_DEMUX_TILE_H
+#define SMX_DEMUX_TILE_H
 #include <hip/hip_runtime.h>
-#ifndef SMX_PART
-#error "compile with -DSMX_PART=1, 2 or 3 (see the Makefile)"
-#endif
 #include <stdint.h>
-#include "smx.h"
 #include "smx_internal.h"
 #include "smx_barcode_core.h"
+#include "smx_align_core.h"
+#include "smx_scorer.h"
 
 namespace smx {
-
-// ------------------------------------------------------------------------------------------------
-// Myers / Hyyro bit-vector column step.  Bits above the pattern length carry garbage
-// that never flows downwards (adds carry upwards, shifts go left), so no masking is needed.
-template <typename W, bool PREFIX>
-__device__ __forceinline__ void myers_step(W Eq, W &Pv, W &Mv, int &score, int top) {
-    W Xv = Eq | Mv;
-    W Xh = (((Eq & Pv) + Pv) ^ Pv) | Eq;
-    W Ph = Mv | ~(Xh | Pv);
-    W Mh = Pv & Xh;
-    score += (int)((Ph >> top) & 1) - (int)((Mh >> top) & 1);
-    Ph = (Ph << 1) | (W)(PREFIX ? 1 : 0);
-    Mh <<= 1;
-    Pv = Mh | ~(Xv | Ph);
-    Mv = Ph & Xv;
-}
-
-// HW column step for a 32-bit pattern LEFT-ALIGNED in its word (row m-1 = bit 31; the padding rows below the
-// pattern have Eq = 0 and stay inert: Pv = 1, Mv = Ph = Mh = 0), so the score delta is two plain shifts of
-// the top bit (one of them arithmetic: -1) and a three-operand add.
-__device__ __forceinline__ void myers_step_hw_top(unsigned Eq, unsigned &Pv, unsigned &Mv, int &score) {
-    unsigned Xv = Eq | Mv;
-    unsigned Xh = (((Eq & Pv) + Pv) ^ Pv) | Eq;
-    unsigned Ph = Mv | ~(Xh | Pv);
-    unsigned Mh = Pv & Xh;
-    score = score + (int)(Ph >> 31) + ((int)Mh >> 31);
-    // x + x instead of x << 1: measured on gfx950 (tools/ubench/valu_rate.hip, primer_col.hip) v_add_u32 issues
-    // faster than v_lshlrev_b32; the asm keeps LLVM from canonicalising the add back into a shift
-    asm("v_add_u32 %0, %1, %1" : "=v"(Ph) : "v"(Ph));
-    asm("v_add_u32 %0, %1, %1" : "=v"(Mh) : "v"(Mh));
-    Pv = Mh | ~(Xv | Ph);
-    Mv = Ph & Xv;
-}
-
-// Geometry of one end string q of length L.  The stored window holds
-// q[L-Sp : L], Sp = min(S, L); window coordinate j <-> q index j + base.
-struct EndGeom {
-    int Sp;     // stored window length
-    int base;   // q index of window position 0
-    int j_lo;   // window position where match_one_end's primer target starts
-    int shift;  // reference coordinate = (j - j_lo) + shift
-};
-__device__ __forceinline__ EndGeom end_geom(int L, int S) {
-    EndGeom g;
-    g.Sp = L < S ? L : S;
-    g.base = L - g.Sp;
-    if (L >= S) { g.j_lo = 0; g.shift = L - S; }
-    else if (L == S - 1) { g.j_lo = 0; g.shift = 0; }           // start == -1 means 0 (alignment.py:37)
-    else { int lo = 2 * L - S; g.j_lo = lo > 0 ? lo : 0; g.shift = L - S; }  // negative slice start wraps
-    return g;
-}
-
-// Barcode target of align_seq(b_rc, q, k, bstart, L, SHW) (demultiplex.py:787-800) in window coordinates.
-struct BcGeom {
-    int tj0;     // window position of the first target base (may be >= Sp: empty target)
-    int delta;   // reference coordinate of window position j = j + base - delta ... see bc_abs()
-    bool pf_same; // prefilter slice sequence[bstart:] is the same string as the alignment target
-};
-__device__ __forceinline__ BcGeom bc_geom(int L, int base, int bstart) {
-    BcGeom b;
-    int s_ = (bstart == -1) ? 0 : bstart;
-    int lo = s_ < 0 ? (L + s_ > 0 ? L + s_ : 0) : (s_ < L ? s_ : L);
-    int plo = bstart < 0 ? (L + bstart > 0 ? L + bstart : 0) : (bstart < L ? bstart : L);
-    b.tj0 = lo - base;
-    b.delta = lo - s_;      // reference coordinate = q index - delta
-    b.pf_same = (plo == lo);
-    return b;
-}
-
-// ------------------------------------------------------------------------------------------------
-// LDS-resident per (read, primer, end) record.
-// Tile geometry of the two-primer default-flags kernel (SP = 2): reads per tile, and the resident workgroups per CU it is
-// built for.  Five: its tile is 31.5 KB of LDS (five of them fit a CU: tools/ubench/lds_residency.hip) and the register
-// allocator is held to 96 VGPRs (8 values spilled).  Measured: 56-read tiles at four per CU 0.255 ms, at five 0.228 ms.
-#ifndef SMX_SP2_R
-#define SMX_SP2_R 64
-#define SMX_SP2_WG 5
-#endif
-
-struct HitL {
-    int tail_end;       // reference coord: max optimal end over all within-k barcodes (slots mode), valid if bbest >= 0
-    short nloc;
-    short ntied;
-    short first_tied;   // local index in the primer's barcode list
-    signed char pdist;  // -1 no primer match (primers <= 64 nt)
-    signed char bbest;  // -1 none, -2 not searched (barcodes <= 32 nt)
-    unsigned char jstar;   // window position of the first optimal primer end
-    unsigned char fs_j;    // window position of its start (need_starts only)
-    unsigned char flags;   // bit0: orientation vote, bit1: barcode search needed
-    unsigned char pad;
-};
-static_assert(sizeof(HitL) == 16, "HitL layout");
-
-struct TileLayout {   // byte offsets into dynamic LDS
-    int tacc, ppeq, prpeq, bpeq, bsre, lut, pmeta, codes, namask, lens, ocnt, rflag, hits, masks, tiem, bres, dmask, ents, offsA, offsB, queue, emit, opsL, aggr, etail,
-        hmap, clist, pmask, hcand, total;
-    int NI;      // per-alignment records a tile keeps: R * H (dense) or the compact capacity
-    int CS;      // bytes per code row (odd number of dwords: conflict-free column reads across rows)
-    int lNPs, lNBs;  // their log2
-    int NPs, NBs;  // power-of-two strides of the transposed Peq tables: entry [code][pattern]
-    int G, logG;   // barcode slots per (hit) group: power of two >= maxB
-    int MBW;     // tie-mask words per hit
-    int BSP;     // bit-sliced table: words per primer
-    int CAPH, CAPE;  // hits / (hit, location) entries processed per barcode round
-};
-
-struct EntL {   // one optimal primer location of one searched hit = one barcode target
-    unsigned short hit;     // r * H + h
-    unsigned short slot;    // first bres slot of the hit in this round
-    unsigned char tj0;      // window position of the first target base
-    unsigned char loc_ord;  // ordinal of the location (ascending end)
-    unsigned char ncol;     // target columns available (capped)
-    unsigned char ok;       // 0: target empty or rejected by the prefilter rule
-    short delta;            // reference coordinate of window position j at this location = j + base - delta (bc_geom)
-    short pad;
-};
-static_assert(sizeof(EntL) == 12, "EntL layout");
-
-// the scorer looks at the candidates of matched alignments only (panels with more than two primer pairs)
-__host__ __device__ inline bool layout_cfilt(int H, int ncand) { return H <= 64 && ncand <= 64 && ncand > 4; }
-__host__ __device__ inline bool layout_tie_in_rec(int MBW, int slots, int tails) { return MBW == 1 && !slots && !tails; }
-#define OCNT_NA 0x8000
-
-template <typename PW>
-__host__ __device__ inline TileLayout make_layout(int NP, int NB, int S, int R, int maxB, int need_starts,
-                                                    int npmeta, int kidx, int slots, int bs, int ncand, int cap_hits = 0,
-                                                    int cap_ents = 0, int nitems = 0, int tails = 1, int nbstab = -1) {
-    // nitems > 0: compact mode.  The tile keeps per-alignment state (hit record, end mask, scan slots) for at most nitems
-    // of its R * H alignments -- the ones the prescan's match words flag -- plus one shared "no match" record; hmap maps
-    // (read, alignment) to its record.  Panels with many primers spend most of their LDS on alignments that never match.
-    TileLayout t;
-    int H = 2 * NP, MW = (S + 31) / 32;
-    t.CS = 4 * (((S + 3) / 4) | 1);
-    t.NPs = 1; t.lNPs = 0; while (t.NPs < NP) { t.NPs <<= 1; t.lNPs++; }   // table index = (code << log2) | pattern:
-    t.NBs = 1; t.lNBs = 0; while (t.NBs < NB) { t.NBs <<= 1; t.lNBs++; }   // no integer multiply in the inner loops
-    t.G = 1; t.logG = 0;
-    while (t.G < maxB) { t.G <<= 1; t.logG++; }
-    t.MBW = (maxB + 31) / 32;
-    // barcode rounds.  slots mode (--trim tails, parity dumps): one 4-byte atomicMin slot per (hit, barcode),
-    // at most 16 KiB worth of hits per round.  lean mode: per hit only (k+1) x MBW words of "barcodes seen at
-    // distance d" bitmasks, at most 4 KiB per round.
-    const int sentinel = nitems > 0 ? 1 : 0;
-    t.NI = nitems > 0 ? nitems : R * H;
-    int dense = t.NI;
-    // (compact mode: up to 8 KiB, so that the searched hits of a 64-read tile usually go in ONE round -- the several-round
-    // path has serial bookkeeping)
-    int fit = slots ? (16 * 1024) / (t.G * 4) : ((nitems > 0 ? 8 : 3) * 1024) / ((kidx + 1) * t.MBW * 4);
-    t.CAPH = dense < fit ? dense : (fit < 1 ? 1 : fit);
-    t.CAPE = t.CAPH + t.CAPH / 4 < 256 ? 256 : t.CAPH + t.CAPH / 4;   // >= 256 = max locations of one hit (progress)
-    if (nitems > 0) t.CAPE = t.CAPH + t.CAPH / 2 < 256 ? 256 : t.CAPH + t.CAPH / 2;   // (noisy reads of a wide window: several optimal ends per hit)
-    if (cap_hits > 0 && cap_hits < t.CAPH) t.CAPH = cap_hits;          // test hook: many small rounds
-    if (cap_ents >= S && cap_ents < t.CAPE) t.CAPE = cap_ents;         // (a hit has at most S locations)
-    // Order: regions whose offsets depend on the tile geometry only (R, S) come first -- compile-time constants in the
-    // default-flags kernel --, then the per-alignment regions (R * 2 NP or the compact capacity), the panel tables last.
-    int o = 0;
-    t.tacc = o;  o += 11 * 8 + 8;
-    t.lut = o;   o += 512;
-    t.aggr = o;  o += 12 * 4;
-    o = (o + 15) & ~15;
-    t.codes = o; o += R * 2 * t.CS;
-    t.namask = o; o += R * 2 * MW * 4;         // per code row: bit j set = code[j] is not A/C/G/T
-    t.lens = o;  o += 2 * R * 4;               // double-buffered: the next tile is encoded while this one is scored
-    t.ocnt = o;  o += 2 * R * 4;               // per read: forward votes | OCNT_NA (a window holds something other than upper-case
-                                               // ACGT: scalar primer scan) | reverse votes << 16; double-buffered
-    t.rflag = o;                               // (round 3: the flag is bit 15 of ocnt, no region of its own)
-    o = (o + 7) & ~7;
-    const bool cf = layout_cfilt(H, ncand);
-    t.pmask = o; o += cf ? R * 8 : 0;          // per read: bit h = alignment h found its primer (scorer: which candidates to look at)
-    o = (o + 15) & ~15;
-    t.hits = o;  o += (t.NI + sentinel) * (int)sizeof(HitL);
-    // one tie-mask word per record and nothing else wanting HitL::tail_end (it belongs to slots mode and --trim tails): the word
-    // lives there, no array of its own
-    t.tiem = o;  o += layout_tie_in_rec(t.MBW, slots, tails) ? 0 : (t.NI + sentinel) * t.MBW * 4;
-    t.clist = o; o += nitems > 0 ? ((t.NI + 1) & ~1) * 2 : 0;       // record -> read * H + alignment
-    // time-shared regions: {location entries} are dead after the barcode scan -> staged result records;
-    // {primer end masks, scans, queue} are dead once the scorer starts -> its per-(read, candidate) trim shifts (Q8)
-    t.bres = t.dmask = o; o += slots ? t.CAPH * t.G * 4 : t.CAPH * (kidx + 1) * t.MBW * 4;
-    {
-        int c = t.CAPE * (int)sizeof(EntL), d = R * 32;
-        o = (o + 15) & ~15;
-        t.ents = t.opsL = o; o += c > d ? c : d;
-    }
-    t.etail = o; o += (bs && !slots && tails) ? t.CAPE * 4 : 0;   // --trim tails on the lean path (BSV == 3): end of the kept alignment per entry
-    t.masks = t.emit = o; o += t.NI * MW * 4;
-    o = (o + 3) & ~3;
-    t.offsA = o; o += ((t.NI + 2) & ~1) * 2;   // 16-bit scans: a tile has at most NI * S < 65536 locations
-    t.offsB = o; o += ((t.NI + 2) & ~1) * 2 < 16 ? 16 : ((t.NI + 2) & ~1) * 2;   // (>= 16 bytes: the one-round path parks four wave sums here)
-    t.queue = o; o += ((t.NI + 1) & ~1) * 2;
-    if (o < t.emit + R * ncand * 4) o = t.emit + R * ncand * 4;
-    o = (o + 7) & ~7;
-    t.hmap = o;  o += nitems > 0 ? ((R * H + 1) & ~1) * 2 : 0;     // (read, alignment) -> record; t.NI = the shared "no match" record
-    o = (o + 7) & ~7;
-    t.hcand = o; o += cf ? H * 8 : 0;          // per alignment: the candidates (pair * 2 + orientation) it belongs to
-    o = (o + 15) & ~15;
-    t.ppeq = o;  o += t.NPs * 16 * (int)sizeof(PW);
-    t.prpeq = o; o += (need_starts ? t.NPs * 16 * (int)sizeof(PW) : 0);
-    t.bpeq = o;  o += (bs && !slots) ? 0 : t.NBs * 16 * 4;
-    t.BSP = 16 * 16 + 4;                        // words per (primer, 32-barcode word) block of the bit-sliced table (+4: bank skew)
-    t.bsre = o;  o += (bs && !slots) ? (nbstab > 0 ? nbstab : NP) * t.MBW * t.BSP * 4 : 0;   // one table per distinct barcode list
-    t.pmeta = o; o += npmeta * 4;
-    t.total = (o + 15) & ~15;
-    return t;
-}
-
-// The make_layout arguments that follow from a panel's sizes.  The host (smx_demux_lds_bytes: the LDS a launch reserves) and
-// DemuxTile::setup (the LDS the kernel addresses) both take them from here; a specialised kernel passes its constants.
-struct LayoutArgs { int npmeta, ncand, tails; };
-__host__ __device__ __forceinline__ LayoutArgs layout_args(int NP, int NB, int n_pbc, int NPAIR, int trim) {
-    return {6 * NP + 1 + n_pbc + NB + 3 * NPAIR, 2 * NPAIR, trim == SMX_TRIM_TAILS ? 1 : 0};
-}
 
 // exclusive scan of a[0..n) in LDS by ONE wave (all 64 lanes of it call this); a[n] = total.
 __device__ inline void wave_exclusive_scan(unsigned short *a, int n) {
@@ -292,599 +83,6 @@ __device__ __forceinline__ int nth_location(const unsigned *mrow, int MW, int js
 }
 
 // Bit-sliced SHW scans of the lean mode: smx_barcode_core.h (bitsliced_shw, bitsliced_shw_pad, bitsliced_shw_pad_tails).
-
-// ------------------------------------------------------------------------------------------------
-
-// Scorer helpers (phase 4).  Everything is indexed, nothing is string keyed.
-// Small per-panel tables staged in LDS (the scorer and the barcode scan read them constantly).
-struct LPanel {
-    const int *pm, *pk, *pdir, *pfidx, *pbc_off, *pbc, *bm, *pair_f, *pair_r, *pair_pool, *bstab;
-};
-
-struct ReadCtx {
-    const DevPanel *P;
-    LPanel LP;
-    const HitL *hits;          // this read's H records (compact mode: the tile's records, indexed through hmap)
-    const unsigned *tiem;      // the records' tie bitmasks (barcodes at the best distance): word w of record i = tiem[i * tstr + w]
-    int tstr;
-    const unsigned short *hmap;   // compact mode: this read's alignment -> record; nullptr: record = alignment
-    const unsigned long long *hcand;   // per alignment: bitmask of the candidates it belongs to; nullptr: look at every candidate
-    int trim, derep;              // the panel's --trim / --dereplicate (compile-time constants in the default-flags kernel)
-    int npair;                    // primer pairs (a constant 1 in the two-primer kernel)
-    unsigned long long pm;        // this read's alignments with a primer match (bit h)
-    unsigned long long live;      // candidates (pair * 2 + orientation) worth looking at: one of their alignments matched, and
-                                  // the orientation is allowed; all ones when there is no candidate table (hcand == nullptr)
-    // Panels with many primer pairs: a candidate scores > 0 only if one of its two alignments found its primer, so only the
-    // candidates of this read's matched alignments are looked at (a handful of the 2 * NPAIR).  Nothing else changes: every
-    // quantity the scorers compute is a function of the candidates with a positive score.
-    __device__ __forceinline__ void set_live(int ori) {
-        live = ~0ull;
-        if (hcand) {
-            live = 0ull;
-            for (unsigned long long m = pm; m; m &= m - 1ull) live |= hcand[__ffsll((long long)m) - 1];
-            if (ori == 2) live &= 0xAAAAAAAAAAAAAAAAull;        // reverse-complement candidates only (odd ids)
-            else if (ori == 1) live &= 0x5555555555555555ull;
-        }
-    }
-    __device__ __forceinline__ bool cand_live(int ci) const { return !hcand || ((live >> ci) & 1ull); }
-    int MBW;
-    __device__ __forceinline__ int rec(int h) const { return hmap ? (int)hmap[h] : h; }
-    __device__ __forceinline__ const HitL &hit(int h) const { return hits[rec(h)]; }
-    int L, S;
-    EndGeom g;
-};
-
-struct CandView {
-    int f, r, o;               // forward primer, reverse primer, orientation 0 = as read, 1 = reverse complement
-    int h1, h2;                // hit indices (primer*2 + end)
-    bool p1, p2, b1, b2;
-    int p1d, p2d, b1d, b2d;
-};
-
-__device__ __forceinline__ CandView cand_view(const ReadCtx &c, int pair, int o) {
-    CandView v;
-    v.f = c.LP.pair_f[pair];
-    v.r = c.LP.pair_r[pair];
-    v.o = o;
-    v.h1 = v.f * 2 + (o == 0 ? 0 : 1);   // forward primer: end A (of rs) when the read is kept as is
-    v.h2 = v.r * 2 + (o == 0 ? 1 : 0);
-    const HitL &a = c.hit(v.h1);
-    const HitL &b = c.hit(v.h2);
-    v.p1 = a.pdist >= 0;
-    v.p2 = b.pdist >= 0;
-    v.b1 = v.p1 && a.bbest >= 0;
-    v.b2 = v.p2 && b.bbest >= 0;
-    v.p1d = v.p1 ? a.pdist : -1;
-    v.p2d = v.p2 ? b.pdist : -1;
-    v.b1d = v.b1 ? a.bbest : -1;
-    v.b2d = v.b2 ? b.bbest : -1;
-    return v;
-}
-
-__device__ __forceinline__ int cand_score(const CandView &v) {   // demultiplex.py:226-236
-    if (v.p1 && v.p2 && v.b1 && v.b2) return 5;
-    if (v.p1 && v.p2 && (v.b1 || v.b2)) return 4;
-    if ((v.p1 || v.p2) && (v.b1 || v.b2)) return 3;
-    if (v.p1 && v.p2) return 2;
-    if (v.p1 || v.p2) return 1;
-    return 0;
-}
-
-// next tied barcode (local index >= from) of hit h in canonical order; -1 when exhausted.  (Find-first-set on the tie
-// mask words: the scorers enumerate tie sets in nested loops, and a bit-by-bit scan of up to maxB positions per call was
-// most of the general scorer's instruction stream.)
-__device__ inline int next_tied(const ReadCtx &c, int h, int from) {
-    int p = h >> 1;
-    int nb = c.LP.pbc_off[p + 1] - c.LP.pbc_off[p];
-    if (from >= nb) return -1;
-    const unsigned *tm = c.tiem + c.rec(h) * c.tstr;
-    int w = from >> 5;
-    unsigned word = tm[w] & (~0u << (from & 31));
-    for (;;) {
-        if (word) {
-            const int i = w * 32 + __ffs((int)word) - 1;
-            return i < nb ? i : -1;
-        }
-        if (++w >= c.MBW) return -1;
-        word = tm[w];
-    }
-}
-__device__ __forceinline__ int global_bc(const ReadCtx &c, int h, int local) {
-    return c.LP.pbc[c.LP.pbc_off[h >> 1] + local];
-}
-__device__ inline bool tied_has_global(const ReadCtx &c, int h, int gb) {
-    for (int i = next_tied(c, h, 0); i >= 0; i = next_tied(c, h, i + 1))
-        if (global_bc(c, h, i) == gb) return true;
-    return false;
-}
-
-// Specimens.specimen_for_exact_match (databases.py:232-245): first specimen in file order.
-// One 32-byte load in the usual case -- the (b1, b2) cell holds the first specimen's whole record (masks, pool, next) --
-// instead of three dependent ones (head of the chain, its primer masks, its pool): the scorer wave sits on a tile's
-// critical path and every dependent global load is most of a microsecond.  The flat tables are gone from the device:
-// five fewer pointers held in (spilled) SGPRs.
-// (load_specrec: the record's two 16-byte halves are requested together and pass through one point.  A plain struct copy
-// is taken apart by the compiler: `spec` first, the masks once it is known to be >= 0, `next` and `pool` where they are
-// used -- up to four dependent round trips for one 32-byte record.)
-__device__ __forceinline__ SpecRec load_specrec(const SpecRec *p) {
-    static_assert(sizeof(SpecRec) == 32 && offsetof(SpecRec, spec) == 16, "SpecRec layout");   // (tables are 16-byte aligned: blob_add)
-    uint4 a = ((const uint4 *)p)[0], b = ((const uint4 *)p)[1];
-    asm volatile("" : "+v"(a.x), "+v"(a.y), "+v"(a.z), "+v"(a.w), "+v"(b.x), "+v"(b.y), "+v"(b.z), "+v"(b.w));
-    SpecRec rec;
-    rec.p1m = ((unsigned long long)a.y << 32) | a.x; rec.p2m = ((unsigned long long)a.w << 32) | a.z;
-    rec.spec = (int)b.x; rec.next = (int)b.y; rec.pool = (int)b.z; rec.pad = (int)b.w;
-    return rec;
-}
-__device__ inline int specimen_exact(const DevPanel *P, int gb1, int gb2, int f, int r, int *pool_out = nullptr) {
-    SpecRec rec = load_specrec(&P->pairrec[(size_t)gb1 * P->NB + gb2]);
-    while (rec.spec >= 0) {
-        if (((rec.p1m >> f) & 1) && ((rec.p2m >> r) & 1)) {
-            if (pool_out) *pool_out = rec.pool;
-            return rec.spec;
-        }
-        if (rec.next < 0) break;
-        rec = load_specrec(&P->specrec[rec.next]);
-    }
-    return -1;
-}
-// Specimens.specimens_for_barcodes_and_primers (databases.py): how many specimens carry (b1, b2) with these primers, and
-// the first of them in file order
-__device__ inline void specimens_for(const DevPanel *P, int gb1, int gb2, int f, int r, int &first, int &cnt) {
-    SpecRec rec = load_specrec(&P->pairrec[(size_t)gb1 * P->NB + gb2]);
-    while (rec.spec >= 0) {
-        if (((rec.p1m >> f) & 1) && ((rec.p2m >> r) & 1)) {
-            cnt++;
-            if (first < 0 || rec.spec < first) first = rec.spec;
-        }
-        if (rec.next < 0) break;
-        rec = load_specrec(&P->specrec[rec.next]);
-    }
-}
-
-// Trim extents of a candidate whose stored locations were already shifted by `cum` (Q8).
-// models.py:278-319 with p1 locations mirrored by AlignmentResult.reversed (models.py:58-63).
-__device__ inline void cand_extent(const ReadCtx &c, const CandView &v, int cum, int &s, int &e) {
-    const DevPanel *P = c.P;
-    int L = c.L;
-    const HitL &a = c.hit(v.h1);
-    const HitL &b = c.hit(v.h2);
-    // first primer location in reference coordinates of the searched string
-    int a_end = 0, a_start = 0, b_end = 0, b_start = 0;
-    if (v.p1) { a_end = (int)a.jstar - c.g.j_lo + c.g.shift; a_start = (int)a.fs_j - c.g.j_lo + c.g.shift; }
-    if (v.p2) { b_end = (int)b.jstar - c.g.j_lo + c.g.shift; b_start = (int)b.fs_j - c.g.j_lo + c.g.shift; }
-    s = 0; e = L;
-    if (c.trim == SMX_TRIM_BARCODES) {
-        if (v.p1) s = (L - a_end - 1) - cum;
-        if (v.p2) e = (b_end + 1) - cum;
-    } else if (c.trim == SMX_TRIM_PRIMERS || c.trim == SMX_TRIM_TAILS) {
-        int ps = 0, pe = L;
-        if (v.p1) ps = (L - a_start - 1) + 1 - cum;
-        if (v.p2) pe = b_start - cum;
-        if (c.trim == SMX_TRIM_PRIMERS) { s = ps; e = pe; }
-        else {
-            if (v.b1) s = (L - a.tail_end - 1) - cum;
-            else { s = ps - P->bmax; if (s < 0) s = 0; }
-            if (v.b2) e = (b.tail_end + 1) - cum;
-            else { e = pe + P->bmax; if (e > L) e = L; }
-        }
-    }
-}
-
-struct Emitter {
-    const ReadCtx *c;
-    smx_op *primary;           // LDS staging slot of this read's first record
-    smx_op *extra;
-    unsigned extra_cap;
-    unsigned *n_extra;
-    unsigned long long *counts;
-    int *cum;                  // LDS, one int per candidate of this read: the trim shift its earlier emissions have added up (Q8)
-    int *aggr;                 // LDS block aggregates
-    unsigned read;
-    int n;                     // ops emitted so far
-    bool matched;
-    bool overflow;
-};
-
-// create_write_operation (demultiplex.py:30-103) in index form.  has_v = false: the record of a read without any
-// candidate; `v` is then a view the caller happens to have (or a dummy) and is not looked at.  (A `const CandView *` that
-// may be null kept the caller's view in scratch memory: every field the record takes was a dependent scratch load on the
-// scorer wave's critical path.)
-__device__ inline void emit_op(Emitter &E, const CandView &v, bool has_v, int cand_id, int sample, int rtype, int pool,
-                               int barcode, unsigned xflags) {
-    const ReadCtx &c = *E.c;
-    smx_op op;
-    op.read = E.read;
-    op.n_ops = 0;
-    op.flags = (unsigned char)xflags;
-    op.barcode = (short)barcode;
-    int s = 0, e = c.L;
-    if (has_v) {
-        op.dist[0] = (int8_t)v.p1d; op.dist[1] = (int8_t)v.b1d; op.dist[2] = (int8_t)v.b2d; op.dist[3] = (int8_t)v.p2d;
-        op.p1 = (short)(v.p1 ? v.f : -1);
-        op.p2 = (short)(v.p2 ? v.r : -1);
-        if (v.o) op.flags |= SMX_OPF_REVERSE;
-    } else {
-        op.dist[0] = op.dist[1] = op.dist[2] = op.dist[3] = -1;
-        op.p1 = op.p2 = -1;
-    }
-    bool fallback = false;
-    if (c.trim != SMX_TRIM_NONE) {
-        if (has_v) {
-            // Q8: the same CandidateMatch emitted earlier already had its locations shifted by the trim start of each of
-            // those emissions.  One running sum per candidate: any number of emissions per read (a tie storm at a large
-            // index distance emits one record per tied specimen, hundreds for one read).
-            const int cum = E.cum[cand_id];
-            cand_extent(c, v, cum, s, e);
-            if (s < e) E.cum[cand_id] = cum + s;
-        }
-        if (s >= e) { fallback = true; s = 0; e = c.L; }   // Q12
-    }
-    op.trim_start = s;
-    op.trim_end = e;
-    if (fallback) {
-        op.flags |= SMX_OPF_TRIM_EMPTY;
-        op.sample = -1; op.pool = -1; op.p1 = -1; op.p2 = -1; op.barcode = -1;
-        op.rtype = SMX_R_UNKNOWN;
-    } else {
-        op.sample = sample;
-        op.pool = (short)pool;
-        op.rtype = (unsigned char)rtype;
-    }
-    if (rtype == SMX_R_FULL || rtype == SMX_R_DEREP_FULL) E.matched = true;
-    // counters
-    int cls = (op.rtype == SMX_R_UNKNOWN) ? 2 : ((op.rtype == SMX_R_PARTIAL_FWD || op.rtype == SMX_R_PARTIAL_REV) ? 1 : 0);
-    atomicAdd(&E.aggr[3 + cls], 1);
-    if (cls == 0 && op.sample >= 0) atomicAdd(&E.counts[SMX_CNT_SPECIMEN0 + op.sample], 1ull);
-    if (E.n == 0) {
-        *E.primary = op;
-    } else {
-        unsigned slot = atomicAdd(E.n_extra, 1u);
-        if (slot < E.extra_cap) E.extra[slot] = op;
-    }
-    E.n++;
-    if (E.n > 0xFFFF) E.overflow = true;   // n_ops is 16 bits wide
-}
-
-// resolve_specimen for a non-full candidate (demultiplex.py:576-589) -> emits.
-__device__ inline void emit_partial_or_unknown(Emitter &E, const CandView &v, int cand_id, int pool) {
-    const ReadCtx &c = *E.c;
-    if (v.b1 && !v.b2 && c.hit(v.h1).ntied == 1)
-        emit_op(E, v, true, cand_id, -1, SMX_R_PARTIAL_FWD, pool, global_bc(c, v.h1, c.hit(v.h1).first_tied), 0);
-    else if (v.b2 && !v.b1 && c.hit(v.h2).ntied == 1)
-        emit_op(E, v, true, cand_id, -1, SMX_R_PARTIAL_REV, pool, global_bc(c, v.h2, c.hit(v.h2).first_tied), 0);
-    else
-        emit_op(E, v, true, cand_id, -1, SMX_R_UNKNOWN, pool, -1, 0);
-}
-
-// Iterate the best-scoring candidates in find_candidate_matches order.
-#define FOR_BEST_CANDS(c, ori, best, ...)                                               \
-    for (int _pair = 0; _pair < (c).npair; _pair++)                                      \
-        for (int _o = 0; _o < 2; _o++) {                                                 \
-            if ((_o == 0 && (ori) == 2) || (_o == 1 && (ori) == 1)) continue;            \
-            if (!(c).cand_live(_pair * 2 + _o)) continue;                                \
-            CandView v = cand_view((c), _pair, _o);                                      \
-            if (!(v.p1 || v.p2)) continue;                                               \
-            if (cand_score(v) != (best)) continue;                                       \
-            int cand_id = _pair * 2 + _o;                                                \
-            int cand_pool = (c).LP.pair_pool[_pair];                                     \
-            (void)cand_id; (void)cand_pool;                                              \
-            __VA_ARGS__                                                                  \
-        }
-
-// key for dereplicate_matches' specimen groups (demultiplex.py:371-378); all lexicographic, small ints
-__device__ __forceinline__ int key_full(const LPanel &P, const CandView &v) {
-    return ((v.b1d + v.b2d) << 20) | ((v.p1d + v.p2d) << 12) | (P.pfidx[v.f] + P.pfidx[v.r]);
-}
-__device__ __forceinline__ int key_partial(const LPanel &P, const CandView &v, bool fwd) {   // :442-463
-    int cnt = (v.p1 ? 1 : 0) + (v.p2 ? 1 : 0);
-    int pd = (v.p1 ? v.p1d : 0) + (v.p2 ? v.p2d : 0);
-    int fi = (v.p1 ? P.pfidx[v.f] : 0) + (v.p2 ? P.pfidx[v.r] : 0);
-    return ((fwd ? v.b1d : v.b2d) << 24) | ((2 - cnt) << 22) | (pd << 12) | fi;
-}
-__device__ __forceinline__ int key_unknown(const LPanel &P, const CandView &v) {             // :502-528
-    int cnt = (v.p1 ? 1 : 0) + (v.p2 ? 1 : 0);
-    int pd = (v.p1 ? v.p1d : 0) + (v.p2 ? v.p2d : 0);
-    int fi = (v.p1 ? P.pfidx[v.f] : 999) + (v.p2 ? P.pfidx[v.r] : 999);
-    return ((2 - cnt) << 22) | (pd << 12) | fi;
-}
-
-// does candidate v map some tied (b1,b2) combination to specimen `spec`?  (spec = -1: to ANY specimen)
-__device__ inline bool cand_has_specimen(const ReadCtx &c, const CandView &v, int spec) {
-    for (int i = next_tied(c, v.h1, 0); i >= 0; i = next_tied(c, v.h1, i + 1))
-        for (int j = next_tied(c, v.h2, 0); j >= 0; j = next_tied(c, v.h2, j + 1)) {
-            int s = specimen_exact(c.P, global_bc(c, v.h1, i), global_bc(c, v.h2, j), v.f, v.r);
-            if (s >= 0 && (spec < 0 || s == spec)) return true;
-        }
-    return false;
-}
-
-// Fast scorer of the hot kernel: handles "no candidate" and "exactly one candidate at the best score, no
-// barcode tie".  Every dereplication group then has one member and the reference's machinery reduces to a
-// single emission.  Returns false for everything else (several best candidates, ties): the caller then runs
-// score_general, the reference's selection / dereplication in full, for that read.
-// `G` lanes (a power of two, consecutive, `sub` = this lane's index among them) share one read: the candidate loops are
-// split over them and reduced by xor-shuffles (tiles of panels with many primers hold fewer than 64 reads, so the scorer
-// wave has lanes to spare, and with 10 candidates the loops are most of its instruction stream); everything after the
-// reductions -- one record in the usual case -- is done by sub-lane 0, the others return true at once.
-__device__ inline bool score_fast(Emitter &E, int ori, int sub, int G) {
-    const ReadCtx &c = *E.c;
-    const DevPanel *P = c.P;
-    // ---- select_best_matches (demultiplex.py:216-259): best score, how many carry it, the first of them
-    int best = 0, nbest = 0, first = 0x7FFF;
-    const int ncand = c.npair * 2;
-    const unsigned long long live = c.live;   // (ReadCtx::set_live)
-    if (c.hcand) {
-        for (unsigned long long m = live; m; m &= m - 1ull) {
-            const int ci = __ffsll((long long)m) - 1;
-            if ((ci & (G - 1)) != sub) continue;
-            CandView v = cand_view(c, ci >> 1, ci & 1);
-            int sc = cand_score(v);
-            if (sc > best) { best = sc; nbest = 1; first = ci; }
-            else if (sc == best) { nbest++; first = ci < first ? ci : first; }
-        }
-    } else
-    for (int ci = sub; ci < ncand; ci += G) {
-        const int pair = ci >> 1, o = ci & 1;
-        if ((o == 0 && ori == 2) || (o == 1 && ori == 1)) continue;
-        CandView v = cand_view(c, pair, o);
-        int sc = cand_score(v);
-        if (sc > best) { best = sc; nbest = 1; first = ci; }
-        else if (sc == best) { nbest++; first = ci < first ? ci : first; }
-    }
-    for (int d = 1; d < G; d <<= 1) {
-        const int ob = __shfl_xor(best, d, 64), on = __shfl_xor(nbest, d, 64), of = __shfl_xor(first, d, 64);
-        if (ob > best) { best = ob; nbest = on; first = of; }
-        else if (ob == best) { nbest += on; first = of < first ? of : first; }
-    }
-    const int only_pair = first >> 1, only_o = first & 1;
-    // The divergent case analysis below only picks the parameters of the ONE record this read emits; the record
-    // itself is built once, after the lanes have converged again (emit_op is by far the longest piece of code here).
-    bool has_v = true;
-    int pair = only_pair, o = only_o, sample = -1, rtype = SMX_R_UNKNOWN, barcode = -1;
-    const bool lead = sub == 0;   // the lane that analyses the winner and emits; its partners only take part in the shuffles
-    unsigned xflags = 0;
-    int more1 = -1, more2 = -1, more3 = -1;   // further specimens of a tied full match
-    int repeat = 1;                           // identical UNKNOWN records (one per tied barcode of a partial match)
-    int spool = -2;                           // the specimen's pool when the lookup already brought it along
-    if (best == 0) {   // no candidate at all (demultiplex.py:202-210)
-        has_v = false; pair = 0; o = 0;
-    } else if (best <= 2 && nbest > 1) {
-        // several primer-only candidates (typically both orientations of one pair): no barcode logic involved.
-        // dereplicate=best -> dereplicate_unknown_matches: stable minimum of (-primer_count, primer_dist, file index);
-        // dereplicate=none -> every best candidate is written as UNKNOWN (demultiplex.py:181-197, :480-538): general path
-        if (c.derep == SMX_DEREP_NONE) return sub != 0;
-        int wkey = 0x7FFFFFFF, wci = 0x7FFF;
-        for (int ci = sub; ci < ncand; ci += G) {
-            const int pr = ci >> 1, oo = ci & 1;
-            if ((oo == 0 && ori == 2) || (oo == 1 && ori == 1)) continue;
-            if (!((live >> ci) & 1ull)) continue;
-            CandView v = cand_view(c, pr, oo);
-            if (cand_score(v) != best) continue;
-            int k = key_unknown(c.LP, v);
-            if (k < wkey) { wkey = k; wci = ci; }   // first minimum in candidate order within this lane's stride
-        }
-        for (int d = 1; d < G; d <<= 1) {
-            const int ok = __shfl_xor(wkey, d, 64), oc = __shfl_xor(wci, d, 64);
-            if (ok < wkey || (ok == wkey && oc < wci)) { wkey = ok; wci = oc; }
-        }
-        pair = wci >> 1; o = wci & 1;
-    } else if (best <= 4 && nbest > 1) {
-        // several partial candidates (typically the pairs that share one primer, when only that primer's end of the read is
-        // good).  dereplicate_partial_matches (demultiplex.py:396-477) groups them by (direction, barcode); when every one
-        // of them has a single untied barcode and it is the same (direction, barcode) for all, there is one group and its
-        // winner -- stable minimum of key_partial -- is the one record.  Anything else: the general scorer.
-        if (!lead) return true;
-        if (c.derep != SMX_DEREP_BEST) return false;
-        int gdir = -1, ggb = -1, wkey = 0x7FFFFFFF, wci = -1;
-        for (int ci = 0; ci < ncand; ci++) {
-            if (!((live >> ci) & 1ull)) continue;
-            if (((ci & 1) == 0 && ori == 2) || ((ci & 1) == 1 && ori == 1)) continue;
-            const CandView v = cand_view(c, ci >> 1, ci & 1);
-            if (cand_score(v) != best) continue;
-            const bool fwd = v.b1;
-            const int h = fwd ? v.h1 : v.h2;
-            const HitL &x = c.hit(h);
-            if (x.ntied != 1) return false;
-            const int gb = global_bc(c, h, x.first_tied);
-            if (gdir < 0) { gdir = fwd ? 1 : 0; ggb = gb; }
-            else if (gdir != (fwd ? 1 : 0) || ggb != gb) return false;
-            const int k = key_partial(c.LP, v, fwd);
-            if (k < wkey) { wkey = k; wci = ci; }
-        }
-        pair = wci >> 1; o = wci & 1;
-        const CandView w = cand_view(c, pair, o);   // resolve_specimen of the winner (demultiplex.py:576-589)
-        if (w.b1 && !w.b2) { rtype = SMX_R_PARTIAL_FWD; barcode = ggb; }
-        else if (w.b2 && !w.b1) { rtype = SMX_R_PARTIAL_REV; barcode = ggb; }
-    } else {
-        if (!lead) return true;
-        if (nbest != 1) return false;
-        const CandView v = cand_view(c, pair, o);
-        const HitL &a = c.hit(v.h1), &b = c.hit(v.h2);
-        const bool t1 = !v.b1 || a.ntied == 1, t2 = !v.b2 || b.ntied == 1;
-        if (best <= 2) {
-            // dereplicate_unknown_matches / resolve_specimen: UNKNOWN either way
-        } else if (best <= 4) {   // one (direction, barcode) group: resolve_specimen (demultiplex.py:576-589)
-            if (!(t1 && t2)) {
-                // tied barcodes on the one end that has any: dereplicate_partial_matches makes one group per tied barcode,
-                // each with this candidate as its only member, and resolve_specimen turns each into UNKNOWN (the barcode is
-                // ambiguous): ntied identical records
-                if (c.derep != SMX_DEREP_BEST) return false;
-                repeat = v.b1 ? a.ntied : b.ntied;
-            }
-            else if (v.b1 && !v.b2) { rtype = SMX_R_PARTIAL_FWD; barcode = global_bc(c, v.h1, a.first_tied); }
-            else if (v.b2 && !v.b1) { rtype = SMX_R_PARTIAL_REV; barcode = global_bc(c, v.h2, b.first_tied); }
-        } else if (c.derep != SMX_DEREP_BEST) {
-            // --dereplicate none: resolve_specimen's full branch (demultiplex.py:555-575) for untied barcodes --
-            // specimens_for_barcodes_and_primers in file order: one -> FULL_MATCH, several -> the first + MULTIPLE
-            if (!(t1 && t2)) return false;
-            const int g1 = global_bc(c, v.h1, a.first_tied), g2 = global_bc(c, v.h2, b.first_tied);
-            int first = -1, cnt = 0;
-            specimens_for(P, g1, g2, v.f, v.r, first, cnt);
-            if (cnt > 0) { sample = first; rtype = cnt > 1 ? SMX_R_MULTIPLE : SMX_R_FULL; }
-            else xflags = SMX_OPF_NO_SPECIMEN;
-        } else {
-            if (t1 && t2) {
-                int spec = specimen_exact(P, global_bc(c, v.h1, a.first_tied), global_bc(c, v.h2, b.first_tied), v.f, v.r, &spool);
-                if (spec >= 0) { sample = spec; rtype = SMX_R_DEREP_FULL; }
-                else xflags = SMX_OPF_NO_SPECIMEN;
-            } else {
-                // one candidate, tied barcodes (by far the most frequent reason to leave the single-record path):
-                // dereplicate_matches (demultiplex.py:262-393) with one member per group = one DEREP_FULL record per
-                // distinct specimen among the tied (b1, b2) combinations, in first-appearance order
-                int s0 = -1, s1 = -1, s2 = -1, s3 = -1, ns = 0;
-                for (int i = next_tied(c, v.h1, 0); i >= 0; i = next_tied(c, v.h1, i + 1))
-                    for (int j = next_tied(c, v.h2, 0); j >= 0; j = next_tied(c, v.h2, j + 1)) {
-                        int sp = specimen_exact(P, global_bc(c, v.h1, i), global_bc(c, v.h2, j), v.f, v.r);
-                        if (sp < 0 || sp == s0 || sp == s1 || sp == s2 || sp == s3) continue;
-                        if (ns == 4) return false;   // more groups than this path keeps: the general scorer takes over
-                        if (ns == 0) s0 = sp; else if (ns == 1) s1 = sp; else if (ns == 2) s2 = sp; else s3 = sp;
-                        ns++;
-                    }
-                if (ns == 0) xflags = SMX_OPF_NO_SPECIMEN;
-                else {
-                    sample = s0; rtype = SMX_R_DEREP_FULL;
-                    more1 = s1; more2 = s2; more3 = s3;
-                }
-            }
-        }
-    }
-    if (!lead) return true;
-    const CandView v = cand_view(c, pair, o);
-    const int pool = !has_v ? -1 : (sample >= 0 ? (spool != -2 ? spool : P->specrec[sample].pool) : c.LP.pair_pool[pair]);
-    emit_op(E, v, has_v, pair * 2 + o, sample, rtype, pool, barcode, xflags);   // (best == 0: the view of candidate 0, not looked at)
-    for (int e = 1; e < repeat; e++) emit_op(E, v, true, pair * 2 + o, -1, SMX_R_UNKNOWN, pool, -1, 0);   // rare
-    if (more1 >= 0) {   // rare
-        for (int e = 0; e < 3; e++) {
-            int sp = e == 0 ? more1 : (e == 1 ? more2 : more3);
-            if (sp >= 0) emit_op(E, v, true, pair * 2 + o, sp, SMX_R_DEREP_FULL, P->specrec[sp].pool, -1, 0);
-        }
-    }
-    return true;
-}
-
-// General scorer: the reference's selection / dereplication in full (reads score_fast declines, ~0.1 %).
-__device__ inline void score_general(Emitter &E, int ori) {
-    const ReadCtx &c = *E.c;
-    const DevPanel *P = c.P;
-    int best = 0;
-    for (int pair = 0; pair < c.npair; pair++)
-        for (int o = 0; o < 2; o++) {
-            if ((o == 0 && ori == 2) || (o == 1 && ori == 1)) continue;
-            if (!c.cand_live(pair * 2 + o)) continue;
-            CandView v = cand_view(c, pair, o);
-            int sc = cand_score(v);
-            best = sc > best ? sc : best;
-        }
-    if (best == 0) {   // (not reached from the kernel: score_fast emits this record itself, under either dereplicate mode;
-                       //  kept so that the function is whole on its own)
-        const CandView none = {};   // not looked at
-        emit_op(E, none, false, 0, -1, SMX_R_UNKNOWN, -1, -1, 0);
-        return;
-    }
-    if (c.derep == SMX_DEREP_NONE) {   // demultiplex.py:181-197
-        FOR_BEST_CANDS(c, ori, best, {
-            if (best == 5) {   // resolve_specimen full branch (:555-575): specimens_for_barcodes_and_primers
-                int first = -1, cnt = 0;
-                for (int i = next_tied(c, v.h1, 0); i >= 0; i = next_tied(c, v.h1, i + 1))
-                    for (int j = next_tied(c, v.h2, 0); j >= 0; j = next_tied(c, v.h2, j + 1)) {
-                        int g1 = global_bc(c, v.h1, i), g2 = global_bc(c, v.h2, j);
-                        specimens_for(P, g1, g2, v.f, v.r, first, cnt);
-                    }
-                if (cnt > 1) emit_op(E, v, true, cand_id, first, SMX_R_MULTIPLE, P->specrec[first].pool, -1, 0);
-                else if (cnt == 1) emit_op(E, v, true, cand_id, first, SMX_R_FULL, P->specrec[first].pool, -1, 0);
-                else emit_op(E, v, true, cand_id, -1, SMX_R_UNKNOWN, cand_pool, -1, SMX_OPF_NO_SPECIMEN);
-            } else {
-                emit_partial_or_unknown(E, v, cand_id, cand_pool);
-            }
-        })
-        return;
-    }
-    // ---- dereplicate_matches (demultiplex.py:262-393); the best list is homogeneous in score
-    if (best == 5) {
-        // expanded entries in order: (candidate, tied b1, tied b2) -> specimen, or one None entry per
-        // candidate without any specimen.  Groups keep first-appearance order (dict insertion).
-        bool none_done = false;
-        FOR_BEST_CANDS(c, ori, best, {
-            bool any = false;
-            for (int i = next_tied(c, v.h1, 0); i >= 0; i = next_tied(c, v.h1, i + 1))
-                for (int j = next_tied(c, v.h2, 0); j >= 0; j = next_tied(c, v.h2, j + 1)) {
-                    int spec = specimen_exact(P, global_bc(c, v.h1, i), global_bc(c, v.h2, j), v.f, v.r);
-                    if (spec < 0) continue;
-                    any = true;
-                    // first appearance of this specimen? (earlier candidate, or earlier combo of this one)
-                    bool seen = false;
-                    {
-                        const int cur_id = cand_id; const int ci = i; const int cj = j;
-                        FOR_BEST_CANDS(c, ori, best, {
-                            if (seen || cand_id > cur_id) continue;
-                            if (cand_id < cur_id) { if (cand_has_specimen(c, v, spec)) seen = true; continue; }
-                            for (int i2 = next_tied(c, v.h1, 0); i2 >= 0 && !seen; i2 = next_tied(c, v.h1, i2 + 1))
-                                for (int j2 = next_tied(c, v.h2, 0); j2 >= 0; j2 = next_tied(c, v.h2, j2 + 1)) {
-                                    if (i2 > ci || (i2 == ci && j2 >= cj)) break;
-                                    if (specimen_exact(P, global_bc(c, v.h1, i2), global_bc(c, v.h2, j2), v.f, v.r) == spec) { seen = true; break; }
-                                }
-                        })
-                    }
-                    if (seen) continue;
-                    // the group's winner: stable min of (b1d+b2d, p1d+p2d, file index sum) over its entries
-                    int wkey = 0x7FFFFFFF, wid = -1;
-                    FOR_BEST_CANDS(c, ori, best, {
-                        int k = key_full(c.LP, v);
-                        if (k < wkey && cand_has_specimen(c, v, spec)) { wkey = k; wid = cand_id; }
-                    })
-                    CandView w = cand_view(c, wid >> 1, wid & 1);
-                    emit_op(E, w, true, wid, spec, SMX_R_DEREP_FULL, P->specrec[spec].pool, -1, 0);
-                }
-            if (!any && !none_done) {
-                // the None group sits where its first entry appeared; it holds every best candidate
-                // without a specimen ("other_matches", :361-363) -> resolve_specimen -> UNKNOWN (Q10)
-                none_done = true;
-                const int first_id = cand_id;
-                FOR_BEST_CANDS(c, ori, best, {
-                    if (cand_id < first_id) continue;
-                    if (!cand_has_specimen(c, v, -1))
-                        emit_op(E, v, true, cand_id, -1, SMX_R_UNKNOWN, cand_pool, -1, SMX_OPF_NO_SPECIMEN);
-                })
-            }
-        })
-        return;
-    }
-    if (best >= 3) {
-        // dereplicate_partial_matches (:396-477): groups keyed (direction, barcode) for every tied barcode
-        FOR_BEST_CANDS(c, ori, best, {
-            bool fwd = v.b1;
-            int h = fwd ? v.h1 : v.h2;
-            for (int i = next_tied(c, h, 0); i >= 0; i = next_tied(c, h, i + 1)) {
-                int gb = global_bc(c, h, i);
-                const int cur_id = cand_id;
-                bool seen = false;
-                int wkey = 0x7FFFFFFF, wid = -1;
-                FOR_BEST_CANDS(c, ori, best, {
-                    if (v.b1 != fwd) continue;
-                    int h2 = fwd ? v.h1 : v.h2;
-                    if (!tied_has_global(c, h2, gb)) continue;
-                    if (cand_id < cur_id) seen = true;
-                    int k = key_partial(c.LP, v, fwd);
-                    if (k < wkey) { wkey = k; wid = cand_id; }
-                })
-                if (seen) continue;
-                CandView w = cand_view(c, wid >> 1, wid & 1);
-                emit_partial_or_unknown(E, w, wid, c.LP.pair_pool[wid >> 1]);
-            }
-        })
-        return;
-    }
-    // dereplicate_unknown_matches (:480-538): one stable minimum
-    {
-        int wkey = 0x7FFFFFFF, wid = -1;
-        FOR_BEST_CANDS(c, ori, best, {
-            int k = key_unknown(c.LP, v);
-            if (k < wkey) { wkey = k; wid = cand_id; }
-        })
-        CandView w = cand_view(c, wid >> 1, wid & 1);
-        emit_op(E, w, true, wid, -1, SMX_R_UNKNOWN, c.LP.pair_pool[wid >> 1], -1, 0);
-    }
-}
 
 // ------------------------------------------------------------------------------------------------
 // BSV selects the barcode scan compiled into the kernel (one variant per kernel keeps their register allocations
@@ -2152,241 +1350,5 @@ __global__ __launch_bounds__(NT, SP == 2 ? SMX_SP2_WG : 4) void demux_kernel(Dev
     D.finish();
 }
 
-#if SMX_PART == 1
-// ------------------------------------------------------------------------------------------------
-// Single alignment (smx_align): one lane, same column step, arbitrary target length.
-__global__ void align_kernel(const unsigned long long *peq, const unsigned long long *rpeq, int m,
-                             const unsigned char *tcodes, int n, int k, int mode, int *out_dist,
-                             unsigned char *endflag, int *starts) {
-    if (threadIdx.x != 0 || blockIdx.x != 0) return;
-    unsigned long long Pv = ~0ull, Mv = 0;
-    int score = m, best = m + 1, top = m - 1;
-    for (int j = 0; j < n; j++) {
-        if (mode == 0) myers_step<unsigned long long, false>(peq[tcodes[j]], Pv, Mv, score, top);
-        else myers_step<unsigned long long, true>(peq[tcodes[j]], Pv, Mv, score, top);
-        if (score < best) best = score;
-        endflag[j] = (unsigned char)score;   // raw score, thresholded below
-    }
-    if (best > k) { *out_dist = -1; return; }
-    *out_dist = best;
-    for (int j = 0; j < n; j++) {
-        bool hit = endflag[j] == (unsigned char)best;
-        endflag[j] = hit ? 1 : 0;
-        starts[j] = 0;
-        if (hit && mode == 0) {
-            unsigned long long P2 = ~0ull, M2 = 0;
-            int sc = m, lastc = 1;
-            for (int c = 1; c <= m + best && j - (c - 1) >= 0; c++) {
-                myers_step<unsigned long long, true>(rpeq[tcodes[j - (c - 1)]], P2, M2, sc, top);
-                if (sc == best) lastc = c;
-            }
-            starts[j] = j - (lastc - 1);
-        }
-    }
-}
-
-// Many alignments per launch (smx_align_batch): one lane per alignment, the same column step.  q_peq: per distinct query
-// 32 words (Peq of the query, then Peq of the reversed query); the raw scores of alignment i go to ws[toff[i] ..).
-__global__ __launch_bounds__(64) void align_batch_kernel(const unsigned long long *__restrict__ q_peq, const int *__restrict__ q_len,
-                                                        const unsigned *__restrict__ qidx, const unsigned char *__restrict__ tcodes,
-                                                        const unsigned long long *__restrict__ toff, const int *__restrict__ kk,
-                                                        const unsigned char *__restrict__ modes, unsigned n, unsigned char *ws,
-                                                        int *__restrict__ out_dist, int *__restrict__ out_nloc,
-                                                        int *__restrict__ out_starts, int *__restrict__ out_ends, unsigned cap) {
-    const unsigned i = blockIdx.x * 64u + threadIdx.x;
-    if (i >= n) return;
-    const unsigned long long *peq = q_peq + (size_t)qidx[i] * 32, *rpeq = peq + 16;
-    const int m = q_len[qidx[i]], k = kk[i], mode = modes[i], top = m - 1;
-    const unsigned char *t = tcodes + toff[i];
-    int nt = (int)(toff[i + 1] - toff[i]);
-    if (mode == 1 && nt > m + k) nt = m + k;   // SHW: an end beyond m + k costs more than k
-    unsigned char *sc = ws + toff[i];
-    unsigned long long Pv = ~0ull, Mv = 0;
-    int score = m, best = m + 1;
-    for (int j = 0; j < nt; j++) {
-        if (mode == 0) myers_step<unsigned long long, false>(peq[t[j]], Pv, Mv, score, top);
-        else myers_step<unsigned long long, true>(peq[t[j]], Pv, Mv, score, top);
-        best = score < best ? score : best;
-        sc[j] = (unsigned char)score;
-    }
-    if (best > k) { out_dist[i] = -1; out_nloc[i] = 0; return; }
-    out_dist[i] = best;
-    int cnt = 0;
-    for (int j = 0; j < nt; j++) {
-        if (sc[j] != (unsigned char)best) continue;
-        if ((unsigned)cnt < cap) {
-            int st = 0;
-            if (mode == 0) {   // edlib's start rule: last optimal position of the reversed problem
-                unsigned long long P2 = ~0ull, M2 = 0;
-                int s2 = m, lastc = 1;
-                for (int c = 1; c <= m + best && j - (c - 1) >= 0; c++) {
-                    myers_step<unsigned long long, true>(rpeq[t[j - (c - 1)]], P2, M2, s2, top);
-                    if (s2 == best) lastc = c;
-                }
-                st = j - (lastc - 1);
-            }
-            out_starts[(size_t)i * cap + cnt] = st;
-            out_ends[(size_t)i * cap + cnt] = j;
-        }
-        cnt++;
-    }
-    out_nloc[i] = cnt;
-}
-
-#endif   // SMX_PART == 1 (alignment kernels)
-
 }  // namespace smx
-
-// ------------------------------------------------------------------------------------------------
-// launch glue used by smx_panel.cpp and smx_calls.cpp
-// The kernel's instantiations, 20 of them at half a minute of compile time each, one row per (part, primer word bits,
-// barcode scan variant BSV, dense / compact / redo mode CM, default-flags specialisation SP).  This file is compiled three
-// times (-DSMX_PART=1 / 2 / 3, in parallel); each part instantiates the rows that name it, part 1 also holds the alignment
-// kernels and the glue.  A new instantiation is one row here plus the condition in demux_variant that selects it.
-#define SMX_DEMUX_VARIANTS(P1, P2, P3)                                                                           \
-    P1(64, 0, 0, 0) P1(64, 1, 0, 0) P1(64, 2, 0, 0) P1(64, 3, 0, 0)   /* 64-bit primer words */                  \
-    P1(32, 0, 0, 0) P1(32, 0, 1, 0) P1(32, 0, 2, 0)                   /* per-barcode scan */                     \
-    P2(32, 1, 0, 0) P2(32, 1, 1, 0) P2(32, 1, 2, 0)                   /* bit-sliced scan, k <= 3 */              \
-    P2(32, 2, 0, 0) P2(32, 2, 1, 0) P2(32, 2, 2, 0)                   /* bit-sliced scan, k 4..7 */              \
-    P3(32, 3, 0, 0) P3(32, 3, 1, 0) P3(32, 3, 2, 0)                   /* the tails variant */                    \
-    P3(32, 1, 0, 2) P3(32, 1, 1, 3) P3(32, 1, 1, 1) P3(32, 1, 0, 1)   /* the default-flags kernels */
-struct DemuxVariant { int wbits, bsv, cm, sp; };
-typedef unsigned smx_w32;
-typedef unsigned long long smx_w64;
-#define SMX_ROW_SKIP(W, B, C, S_)
-#define SMX_ROW_FN(W, B, C, S_) \
-    if (v.wbits == W && v.bsv == B && v.cm == C && v.sp == S_) return (const void *)smx::demux_kernel<smx_w##W, 256, B, C, S_>;
-// the kernel of a row of this part (nullptr: the row is not one of them)
-#if SMX_PART == 1
-extern "C" const void *smx_demux_fn_p1(DemuxVariant v) { SMX_DEMUX_VARIANTS(SMX_ROW_FN, SMX_ROW_SKIP, SMX_ROW_SKIP) return nullptr; }
-#elif SMX_PART == 2
-extern "C" const void *smx_demux_fn_p2(DemuxVariant v) { SMX_DEMUX_VARIANTS(SMX_ROW_SKIP, SMX_ROW_FN, SMX_ROW_SKIP) return nullptr; }
-#else
-extern "C" const void *smx_demux_fn_p3(DemuxVariant v) { SMX_DEMUX_VARIANTS(SMX_ROW_SKIP, SMX_ROW_SKIP, SMX_ROW_FN) return nullptr; }
 #endif
-
-#if SMX_PART == 1
-extern "C" const void *smx_demux_fn_p2(DemuxVariant v);
-extern "C" const void *smx_demux_fn_p3(DemuxVariant v);
-namespace {
-// each part knows its rows of the list.  nullptr: no such instantiation; every caller turns that into an error
-const void *demux_fn(DemuxVariant v) {
-    const void *fn = smx_demux_fn_p1(v);
-    if (!fn) fn = smx_demux_fn_p2(v);
-    return fn ? fn : smx_demux_fn_p3(v);
-}
-// The variant a launch with these parameters gets (cm: 0 dense, 1 compact, 2 redo).  Slots mode never uses the bit-sliced
-// scan.  The default-flags specialisation applies to the k <= 3 lean kernel (not its tails variant, not the redo launch)
-// with the tile sizes it is built for.
-DemuxVariant demux_variant(const smx::DevPanel *P, int use64, int use_slots, int cm, int R, int nitems, bool have_prescan) {
-    const int bsv = (use_slots || !P->bs_ok) ? 0 : (P->kidx < 4 ? (P->trim == SMX_TRIM_TAILS ? 3 : 1) : 2);
-    DemuxVariant v = {use64 ? 64 : 32, bsv, cm, 0};
-    const bool flags = have_prescan && !use64 && bsv == 1 && cm != 2 && (cm == 0 || nitems == 256) && !P->cap_hits && !P->cap_ents &&
-                       P->kidx == 3 && P->maxB <= 32 && !P->need_starts && P->trim == SMX_TRIM_BARCODES && P->derep == SMX_DEREP_BEST &&
-                       P->preorient && P->minlen == -1 && P->maxlen == -1 && !P->dbg_phase && !(P->no_sp & 1);
-    if (!flags) return v;
-    if (P->S == 160 && R == 32 && cm == 1) v.sp = 3;                       // wide windows, compact 32-read tiles
-    else if (P->S == 80 && R == SMX_SP2_R && cm == 0 && P->NP == 2 && P->NPAIR == 1 && !(P->no_sp & 2) && P->tile_codes) v.sp = 2;
-    else if (P->S == 80 && R == 64) v.sp = 1;
-    return v;
-}
-}  // namespace
-
-extern "C" int smx_launch_demux(const smx::DevPanel *P, int use64, int use_slots, const smx::TilePlan *plan, int grid,
-                                const smx::DemuxBatch *b, const smx::DemuxAux *aux_in) {
-    smx::DemuxAux aux = *aux_in;
-    smx::DemuxBatch a = *b;
-    int R = plan->R;
-    if (aux.nitems > 0 && (use_slots || !a.pre || !aux.match || !aux.ovf_list || aux.nitems > 256)) return (int)hipErrorInvalidValue;
-    if (aux.redo && (!aux.ovf_list || aux.Rc < 1)) return (int)hipErrorInvalidValue;
-    if ((aux.nitems > 0 || aux.redo) && use64) return (int)hipErrorInvalidValue;   // (the prescan serves primers of <= 31 nt only)
-    if (aux.nitems > 0 && !aux.chain) return (int)hipErrorInvalidValue;              // a compact launch needs its redo launch
-    if (R > 64) return (int)hipErrorInvalidValue;
-    if (aux.codes2 && (aux.tiled != 0) != (P->tile_codes != 0)) return (int)hipErrorInvalidValue;   // (the variant is chosen by the panel's layout)
-    // tile_counter = {tile queue head, overflow tiles, finished workgroups, extra records}: zero at allocation, re-armed
-    // by the last workgroup of every launch (of the last launch of a chain).
-    const void *fn = demux_fn(demux_variant(P, use64, use_slots, aux.nitems > 0 ? 1 : (aux.redo ? 2 : 0), R, aux.nitems,
-                                            aux.codes2 != nullptr && a.pre != nullptr));
-    if (!fn) return (int)hipErrorInvalidDeviceFunction;
-    smx::DevPanel pv = *P;
-    unsigned long long *counts = (unsigned long long *)a.counts;
-    void *args[] = {&pv, &a.windows, &a.lens, &a.n_reads, &R, &a.ops, &a.extra, &a.extra_cap, &a.n_extra, &counts, &a.hits, &a.bdist,
-                    &a.tile_counter, &use_slots, &a.pre, &a.npad, &aux};
-    hipError_t e = hipLaunchKernel(fn, dim3(grid), dim3(256), args, plan->lds, (hipStream_t)a.stream);
-    return (int)(e != hipSuccess ? e : hipGetLastError());
-}
-
-// The layout of a tile of R reads (nitems > 0: a compact tile with that many records) as DemuxTile::setup computes it from the
-// same panel: the default-flags kernels are only selected where their constants are the panel's values.
-static smx::TileLayout panel_layout(const smx::DevPanel *P, int use64, int R, int slots, int nitems, bool test_caps) {
-    const smx::LayoutArgs la = smx::layout_args(P->NP, P->NB, P->n_pbc, P->NPAIR, P->trim);
-    auto layout = [&](auto w) {
-        return smx::make_layout<decltype(w)>(P->NP, P->NB, P->S, R, P->maxB, P->need_starts, la.npmeta, P->kidx, slots, P->bs_ok,
-                                             la.ncand, test_caps ? P->cap_hits : 0, test_caps ? P->cap_ents : 0, nitems, la.tails,
-                                             P->n_bstab);
-    };
-    return use64 ? layout(smx_w64()) : layout(smx_w32());
-}
-
-// LDS bytes of a tile of R reads (nitems > 0: a compact tile with that many records).  The test caps only shrink a tile.
-extern "C" size_t smx_demux_lds_bytes(const smx::DevPanel *P, int use64, int R, int slots, int nitems) {
-    return (size_t)panel_layout(P, use64, R, slots, nitems, false).total;
-}
-
-extern "C" int smx_demux_plan_query(const smx::DevPanel *P, int use64, int use_slots, int cm, int R, int nitems, int have_prescan,
-                                    smx_plan_variant *row, smx_plan_mode *sizes) {
-    const DemuxVariant v = demux_variant(P, use64, use_slots, cm, R, nitems, have_prescan != 0);
-    *row = {v.wbits, v.bsv, v.cm, v.sp};
-    if (sizes) {
-        const smx::TileLayout t = panel_layout(P, use64, R, use_slots, nitems, true);
-        sizes->MBW = t.MBW; sizes->G = t.G; sizes->CAPH = t.CAPH; sizes->CAPE = t.CAPE;
-    }
-    return demux_fn(v) ? 0 : 1;
-}
-
-extern "C" int smx_set_demux_lds_limit(int use64, size_t bytes) {
-    hipError_t e = hipSuccess;
-#define SMX_ROW_LIMIT(W, B, C, S_)                                                                                       \
-    if (W == (use64 ? 64 : 32)) {                                                                                        \
-        const void *fn = demux_fn({W, B, C, S_});                                                                        \
-        hipError_t r = fn ? hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) : hipErrorInvalidDeviceFunction; \
-        if (r != hipSuccess) e = r;                                                                                      \
-    }
-    SMX_DEMUX_VARIANTS(SMX_ROW_LIMIT, SMX_ROW_LIMIT, SMX_ROW_LIMIT)
-    return (int)e;
-}
-
-// resident workgroups per CU of the kernel a launch with these parameters would use (cm: 0 dense, 1 compact, 2 redo)
-extern "C" int smx_query_occupancy(const smx::DevPanel *P, int use64, int use_slots, int cm, int R, int nitems, size_t lds_bytes,
-                                   int *blocks_per_cu, int have_prescan) {
-    const void *fn = demux_fn(demux_variant(P, use64, use_slots, cm, R, nitems, have_prescan != 0));
-    if (!fn) return (int)hipErrorInvalidDeviceFunction;
-    hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, fn, 256, lds_bytes);
-    // The API divides the CU's 163 840 bytes by the request.  The hardware hands LDS out in 512-byte granules from 159 744
-    // bytes (tools/ubench/lds_residency.hip: a 32 256-byte workgroup is resident four times, not five; 54 272 bytes twice,
-    // not three times): workgroups the grid counts on but the CU cannot hold would start after the tile queue has drained.
-    if (e == hipSuccess && lds_bytes > 0) {
-        const int fit = (int)(SMX_LDS_POOL / ((lds_bytes + 511) & ~(size_t)511));
-        if (*blocks_per_cu > fit) *blocks_per_cu = fit < 1 ? 1 : fit;
-    }
-    return (int)e;
-}
-
-extern "C" int smx_launch_align(void *stream, const unsigned long long *d_peq, const unsigned long long *d_rpeq, int m,
-                                const unsigned char *d_tcodes, int n, int k, int mode, int *d_dist,
-                                unsigned char *d_endflag, int *d_starts) {
-    hipLaunchKernelGGL(smx::align_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, d_peq, d_rpeq, m, d_tcodes, n, k,
-                       mode, d_dist, d_endflag, d_starts);
-    return (int)hipGetLastError();
-}
-
-extern "C" int smx_launch_align_batch(void *stream, const unsigned long long *d_qpeq, const int *d_qlen, const unsigned *d_qidx,
-                                      const unsigned char *d_tcodes, const unsigned long long *d_toff, const int *d_k,
-                                      const unsigned char *d_modes, unsigned n, unsigned char *d_ws, int *d_dist, int *d_nloc,
-                                      int *d_starts, int *d_ends, unsigned cap) {
-    if (n == 0) return 0;
-    hipLaunchKernelGGL(smx::align_batch_kernel, dim3((n + 63) / 64), dim3(64), 0, (hipStream_t)stream, d_qpeq, d_qlen, d_qidx,
-                       d_tcodes, d_toff, d_k, d_modes, n, d_ws, d_dist, d_nloc, d_starts, d_ends, cap);
-    return (int)hipGetLastError();
-}
-#endif   // SMX_PART == 1 (glue)

@@ -58,7 +58,7 @@ struct DevPanel {
     unsigned long long *dbg_phase;        // SMX_PHASE_TIMING=1: [grid][16] cycle sums per phase (diagnostic build-in)
 };
 
-// Compact mode and the redo launch behind it (smx_kernels.hip, demux_kernel).
+// Compact mode and the redo launch behind it (smx_demux_tile.h, demux_kernel).
 struct DemuxAux {
     const unsigned *match;   // prescan match words [tile of 1024 reads][alignment][32-read group]; compact mode only
     unsigned *ovf_list;      // compact launch: the tiles it could not hold (appended); redo launch: the tiles to process
@@ -137,8 +137,6 @@ struct InnerArgs {
 }  // namespace smx
 
 extern "C" {
-int smx_launch_demux(const smx::DevPanel *P, int use64, int use_slots, const smx::TilePlan *plan, int grid,
-                     const smx::DemuxBatch *batch, const smx::DemuxAux *aux);
 // primer prescan (smx_prescan.hip)
 size_t smx_prescan_lds_bytes(int S, int tile);
 int smx_launch_prescan(const smx::PreDesc *D, int mr, int nx, int grid_t, size_t lds_t, int grid_d, void *stream,
@@ -147,15 +145,7 @@ int smx_launch_prescan(const smx::PreDesc *D, int mr, int nx, int grid_t, size_t
 int smx_prescan_set_lds_limit(size_t bytes);
 int smx_prescan_occupancy(int S, int mr, int nx, int tile, size_t lds_t, int *blocks_t, int *blocks_d);
 int smx_prescan_transpose_threads(int S);
-size_t smx_demux_lds_bytes(const smx::DevPanel *P, int use64, int R, int slots, int nitems);
-int smx_set_demux_lds_limit(int use64, size_t bytes);
-// The instantiation row (cm: 0 dense, 1 compact, 2 redo) a launch with these parameters gets and, with sizes != nullptr, the
-// MBW, G, CAPH and CAPE of its tile layout (nitems: what the launch passes -- 0 for the dense and redo launches).  For
-// plan_tiles and smx_panel_plan.  Nonzero: the library holds no such instantiation.
-int smx_demux_plan_query(const smx::DevPanel *P, int use64, int use_slots, int cm, int R, int nitems, int have_prescan,
-                         smx_plan_variant *row, smx_plan_mode *sizes);
-int smx_query_occupancy(const smx::DevPanel *P, int use64, int use_slots, int cm, int R, int nitems, size_t lds_bytes,
-                        int *blocks_per_cu, int have_prescan);
+// alignment kernels (smx_align.hip)
 int smx_launch_align(void *stream, const unsigned long long *d_peq, const unsigned long long *d_rpeq, int m,
                      const unsigned char *d_tcodes, int n, int k, int mode, int *d_dist, unsigned char *d_endflag,
                      int *d_starts);

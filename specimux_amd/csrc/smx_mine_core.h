@@ -14,14 +14,7 @@
 #define SMX_MINE_CORE_H
 #include <stddef.h>
 #include <stdint.h>
-
-#ifndef SMX_HD
-#if defined(__HIPCC__)
-#define SMX_HD __host__ __device__ __forceinline__
-#else
-#define SMX_HD inline
-#endif
-#endif
+#include "smx_hd.h"
 
 #if defined(__HIPCC__)
 #define SMX_MINE_HD __host__ __device__

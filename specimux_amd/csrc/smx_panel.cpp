@@ -1,7 +1,10 @@
-// smx_panel.cpp -- the panel of libsmx.so: compilation of a smx_panel_desc into the device blob, the tile plan, and the launch
-// glue of the demux kernel (smx_batch_run_device, smx_batch_run).  Compiled with hipcc together with smx_kernels.hip.
+// smx_panel.cpp -- the panel of libsmx.so: compilation of a smx_panel_desc into the device blob, the choice of the demux kernel's
+// instantiation (demux_variant) and tile plan (plan_tiles), and the launch glue of the demux kernel (smx_launch_demux,
+// smx_batch_run_device, smx_batch_run).  Of the kernel's three headers it includes smx_demux_layout.h alone: the tile
+// layout, the table of instantiations, and the three smx_demux_fn_p* of smx_demux.hip that hand out their addresses.
 #include "smx_host.h"
 #include "smx_barcode_core.h"
+#include "smx_demux_layout.h"
 
 static Switches read_switches() {
     Switches w;
@@ -19,6 +22,114 @@ static Switches read_switches() {
     if (const char *e = getenv("SMX_COMPACT_R")) w.compact_r = std::max(1, std::min(64, atoi(e)));
     if (const char *e = getenv("SMX_BLOCKS_PER_CU")) w.blocks_per_cu = std::max(1, atoi(e));
     return w;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Which instantiation of the demux kernel a launch gets, how much LDS, and the launch itself.
+// each part of smx_demux.hip knows its rows of SMX_DEMUX_VARIANTS.  nullptr: no such instantiation; every caller turns that
+// into an error
+static const void *demux_fn(DemuxVariant v) {
+    const void *fn = smx_demux_fn_p1(v);
+    if (!fn) fn = smx_demux_fn_p2(v);
+    return fn ? fn : smx_demux_fn_p3(v);
+}
+// The variant a launch with these parameters gets (cm: 0 dense, 1 compact, 2 redo).  Slots mode never uses the bit-sliced
+// scan.  The default-flags specialisation applies to the k <= 3 lean kernel (not its tails variant, not the redo launch)
+// with the tile sizes it is built for.
+static DemuxVariant demux_variant(const smx::DevPanel *P, int use64, int use_slots, int cm, int R, int nitems, bool have_prescan) {
+    const int bsv = (use_slots || !P->bs_ok) ? 0 : (P->kidx < 4 ? (P->trim == SMX_TRIM_TAILS ? 3 : 1) : 2);
+    DemuxVariant v = {use64 ? 64 : 32, bsv, cm, 0};
+    const bool flags = have_prescan && !use64 && bsv == 1 && cm != 2 && (cm == 0 || nitems == 256) && !P->cap_hits && !P->cap_ents &&
+                       P->kidx == 3 && P->maxB <= 32 && !P->need_starts && P->trim == SMX_TRIM_BARCODES && P->derep == SMX_DEREP_BEST &&
+                       P->preorient && P->minlen == -1 && P->maxlen == -1 && !P->dbg_phase && !(P->no_sp & 1);
+    if (!flags) return v;
+    if (P->S == 160 && R == 32 && cm == 1) v.sp = 3;                       // wide windows, compact 32-read tiles
+    else if (P->S == 80 && R == SMX_SP2_R && cm == 0 && P->NP == 2 && P->NPAIR == 1 && !(P->no_sp & 2) && P->tile_codes) v.sp = 2;
+    else if (P->S == 80 && R == 64) v.sp = 1;
+    return v;
+}
+
+static int smx_launch_demux(const smx::DevPanel *P, int use64, int use_slots, const smx::TilePlan *plan, int grid,
+                            const smx::DemuxBatch *b, const smx::DemuxAux *aux_in) {
+    smx::DemuxAux aux = *aux_in;
+    smx::DemuxBatch a = *b;
+    int R = plan->R;
+    if (aux.nitems > 0 && (use_slots || !a.pre || !aux.match || !aux.ovf_list || aux.nitems > 256)) return (int)hipErrorInvalidValue;
+    if (aux.redo && (!aux.ovf_list || aux.Rc < 1)) return (int)hipErrorInvalidValue;
+    if ((aux.nitems > 0 || aux.redo) && use64) return (int)hipErrorInvalidValue;   // (the prescan serves primers of <= 31 nt only)
+    if (aux.nitems > 0 && !aux.chain) return (int)hipErrorInvalidValue;              // a compact launch needs its redo launch
+    if (R > 64) return (int)hipErrorInvalidValue;
+    if (aux.codes2 && (aux.tiled != 0) != (P->tile_codes != 0)) return (int)hipErrorInvalidValue;   // (the variant is chosen by the panel's layout)
+    // tile_counter = {tile queue head, overflow tiles, finished workgroups, extra records}: zero at allocation, re-armed
+    // by the last workgroup of every launch (of the last launch of a chain).
+    const void *fn = demux_fn(demux_variant(P, use64, use_slots, aux.nitems > 0 ? 1 : (aux.redo ? 2 : 0), R, aux.nitems,
+                                            aux.codes2 != nullptr && a.pre != nullptr));
+    if (!fn) return (int)hipErrorInvalidDeviceFunction;
+    smx::DevPanel pv = *P;
+    unsigned long long *counts = (unsigned long long *)a.counts;
+    void *args[] = {&pv, &a.windows, &a.lens, &a.n_reads, &R, &a.ops, &a.extra, &a.extra_cap, &a.n_extra, &counts, &a.hits, &a.bdist,
+                    &a.tile_counter, &use_slots, &a.pre, &a.npad, &aux};
+    hipError_t e = hipLaunchKernel(fn, dim3(grid), dim3(256), args, plan->lds, (hipStream_t)a.stream);
+    return (int)(e != hipSuccess ? e : hipGetLastError());
+}
+
+// The layout of a tile of R reads (nitems > 0: a compact tile with that many records) as DemuxTile::setup computes it from the
+// same panel: the default-flags kernels are only selected where their constants are the panel's values.
+static smx::TileLayout panel_layout(const smx::DevPanel *P, int use64, int R, int slots, int nitems, bool test_caps) {
+    const smx::LayoutArgs la = smx::layout_args(P->NP, P->NB, P->n_pbc, P->NPAIR, P->trim);
+    auto layout = [&](auto w) {
+        return smx::make_layout<decltype(w)>(P->NP, P->NB, P->S, R, P->maxB, P->need_starts, la.npmeta, P->kidx, slots, P->bs_ok,
+                                             la.ncand, test_caps ? P->cap_hits : 0, test_caps ? P->cap_ents : 0, nitems, la.tails,
+                                             P->n_bstab);
+    };
+    return use64 ? layout(smx_w64()) : layout(smx_w32());
+}
+
+// LDS bytes of a tile of R reads (nitems > 0: a compact tile with that many records).  The test caps only shrink a tile.
+static size_t smx_demux_lds_bytes(const smx::DevPanel *P, int use64, int R, int slots, int nitems) {
+    return (size_t)panel_layout(P, use64, R, slots, nitems, false).total;
+}
+
+// The instantiation row (cm: 0 dense, 1 compact, 2 redo) a launch with these parameters gets and, with sizes != nullptr, the
+// MBW, G, CAPH and CAPE of its tile layout (nitems: what the launch passes -- 0 for the dense and redo launches).  For
+// plan_tiles and smx_panel_plan.  Nonzero: the library holds no such instantiation.
+static int smx_demux_plan_query(const smx::DevPanel *P, int use64, int use_slots, int cm, int R, int nitems, int have_prescan,
+                                smx_plan_variant *row, smx_plan_mode *sizes) {
+    const DemuxVariant v = demux_variant(P, use64, use_slots, cm, R, nitems, have_prescan != 0);
+    *row = {v.wbits, v.bsv, v.cm, v.sp};
+    if (sizes) {
+        const smx::TileLayout t = panel_layout(P, use64, R, use_slots, nitems, true);
+        sizes->MBW = t.MBW; sizes->G = t.G; sizes->CAPH = t.CAPH; sizes->CAPE = t.CAPE;
+    }
+    return demux_fn(v) ? 0 : 1;
+}
+
+static int smx_set_demux_lds_limit(int use64, size_t bytes) {
+    hipError_t e = hipSuccess;
+#define SMX_ROW_LIMIT(W, B, C, S_)                                                                                       \
+    if (W == (use64 ? 64 : 32)) {                                                                                        \
+        const void *fn = demux_fn({W, B, C, S_});                                                                        \
+        hipError_t r = fn ? hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) : hipErrorInvalidDeviceFunction; \
+        if (r != hipSuccess) e = r;                                                                                      \
+    }
+    SMX_DEMUX_VARIANTS(SMX_ROW_LIMIT, SMX_ROW_LIMIT, SMX_ROW_LIMIT)
+    return (int)e;
+}
+
+// resident workgroups per CU of the kernel a launch with these parameters would use (cm: 0 dense, 1 compact, 2 redo)
+static int smx_query_occupancy(const smx::DevPanel *P, int use64, int use_slots, int cm, int R, int nitems, size_t lds_bytes,
+                               int *blocks_per_cu, int have_prescan) {
+    const void *fn = demux_fn(demux_variant(P, use64, use_slots, cm, R, nitems, have_prescan != 0));
+    if (!fn) return (int)hipErrorInvalidDeviceFunction;
+    hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, fn, 256, lds_bytes);
+    // The API divides the CU's 163 840 bytes by the request.  The hardware hands LDS out in 512-byte granules from 159 744
+    // bytes (tools/ubench/lds_residency.hip: a 32 256-byte workgroup is resident four times, not five; 54 272 bytes twice,
+    // not three times): workgroups the grid counts on but the CU cannot hold would start after the tile queue has drained.
+    if (e == hipSuccess && lds_bytes > 0) {
+        const int fit = (int)(SMX_LDS_POOL / ((lds_bytes + 511) & ~(size_t)511));
+        if (*blocks_per_cu > fit) *blocks_per_cu = fit < 1 ? 1 : fit;
+    }
+    return (int)e;
 }
 
 // The tile plan of a panel (h: every scalar field set): plan[].R / .lds per mode, *nitems > 0 where compact mode is on.

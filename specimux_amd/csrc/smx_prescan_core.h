@@ -37,15 +37,8 @@
 #define SMX_PRESCAN_CORE_H
 #include <stdint.h>
 
+#include "smx_hd.h"
 #include "smx_bitslice_core.h"
-
-#if !defined(SMX_HD)
-#if defined(__HIPCC__)
-#define SMX_HD __host__ __device__ __forceinline__
-#else
-#define SMX_HD inline
-#endif
-#endif
 
 namespace smx {
 

@@ -10,12 +10,7 @@
 #define SMX_STATS_CORE_H
 #include <stdint.h>
 #include "smx.h"
-
-#if defined(__HIPCC__)
-#define SMX_HD __host__ __device__ __forceinline__
-#else
-#define SMX_HD inline
-#endif
+#include "smx_hd.h"
 
 namespace smx {
 

@@ -2,7 +2,7 @@
 
 Reference boundary: src/specimux/demultiplex.py:108-212 (callers multiprocessing_utils.py:89 and
 orchestration.py:513).  Same signature, same return value (write_ops, total_count, matched_count); the
-whole per-read pipeline below it runs inside one HIP kernel (specimux_amd/csrc/smx_kernels.hip) behind
+whole per-read pipeline below it runs inside one HIP kernel (demux_kernel, specimux_amd/csrc/smx_demux_tile.h) behind
 the C ABI of include/smx.h.  There is no CPU implementation here: without libsmx.so or without a GPU
 this raises."""
 import logging

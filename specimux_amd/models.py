@@ -3,7 +3,7 @@
 Only what crosses the process_sequences boundary is kept as Python objects: PrimerInfo (:20),
 MatchParameters (:331), WriteOperation (:341), SequenceBatch (:360), WorkerException (:368).
 AlignmentResult / CandidateMatch (:34-328) have no Python counterpart here: that state lives in
-LDS inside the demux kernel (specimux_amd/csrc/smx_kernels.hip)."""
+LDS inside the demux kernel (specimux_amd/csrc: HitL in smx_demux_layout.h, CandView in smx_scorer.h)."""
 from typing import Dict, List, NamedTuple, Optional, Tuple
 
 from .constants import Primer, ResolutionType

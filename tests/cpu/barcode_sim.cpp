@@ -74,7 +74,7 @@ static std::vector<int> dp_last_row(const std::string &b, const std::vector<int>
     return last;
 }
 
-// The kernel's choice of scan for a uniform barcode length bsm (smx_kernels.hip phase3b_barcodes / phase3c_summary, the
+// The kernel's choice of scan for a uniform barcode length bsm (smx_demux_tile.h phase3b_barcodes / phase3c_summary, the
 // if-chains at the bitsliced_shw* calls): k <= 3 -> pad<3, 13> if bsm == 13, <3, 8> for 4..8, <3, 12> for 9..12, else
 // <3, 16>; k = 4 -> pad<4, 13> if bsm == 13, else <4, 16>; k 5..7 -> bitsliced_shw<8>.  Restated here, not shared, so
 // that the kernel's instructions stay as they were.

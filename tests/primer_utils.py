@@ -1,4 +1,4 @@
-"""Panels, constructed reads and a census for the demux kernel's per-read primer search (primer_item in smx_kernels.hip, fed
+"""Panels, constructed reads and a census for the demux kernel's per-read primer search (primer_item in smx_demux_tile.h, fed
 by prescan_decode).  Plain Python; everything here is computed with the oracle alone.
 
 The synthetic reads of specimux_amd.synth put the primer behind a 0-30 nt tail and a barcode, so nearly every match ends

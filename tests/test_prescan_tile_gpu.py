@@ -1,5 +1,5 @@
 """The primer prescan on tile codes (prescan_tilecodes_kernel, prescan_dp_kernel with TS = 1 and the demux kernel's tile-major
-encode, smx_prescan.hip / smx_kernels.hip) on the GPU: the two-primer panel at search_len 80, batches that mix full-length,
+encode, smx_prescan.hip / smx_demux_tile.h) on the GPU: the two-primer panel at search_len 80, batches that mix full-length,
 short and non-ACGT reads, at the read counts where a 32-read group, a 256-read sub-tile or a 1024-read DP tile is partial.
 Records, totals and hit tables against the CPU oracle; records, extra records, counts and hit tables against the same batch
 run with SMX_PRESCAN_PLANES=1 (the plane buffer and the row-major codes)."""

@@ -1,5 +1,5 @@
 """CPU side of the primer-search tests (no GPU needed): the census that keeps tests/test_primer_cases_gpu.py honest, and the
-rules by which a panel selects the path of primer_item (smx_kernels.hip) that a cell is meant to reach.
+rules by which a panel selects the path of primer_item (smx_demux_tile.h) that a cell is meant to reach.
 
 The census is computed with the oracle alone (tests/primer_utils.py): for every (panel, search_len) cell the constructed
 reads must hold at least 4 matches that end in each 16-column chunk of the target, in its last column, that start in its

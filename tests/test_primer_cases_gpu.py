@@ -1,4 +1,4 @@
-"""The demux kernel's per-read primer search (primer_item in smx_kernels.hip, fed by prescan_decode) against the oracle on the
+"""The demux kernel's per-read primer search (primer_item in smx_demux_tile.h, fed by prescan_decode) against the oracle on the
 panels and constructed reads of tests/primer_utils.py: primer lengths at the word-size edges (31, 32, 33, 63, 64 nt), the
 panels whose whole search falls back (five degenerate letters, SMX_NO_PRESCAN, one long primer among eight), the primer in
 every window column, cut at the window's inner edge, twice in a row, at exactly k and k + 1 edits, reads of every

@@ -1,4 +1,4 @@
-"""The demux kernel's tile loop (smx_kernels.hip: pop_tile, phase1_encode, emit_op, specimen records) on the GPU, at the batch
+"""The demux kernel's tile loop (smx_demux_tile.h: pop_tile, phase1_encode; smx_scorer.h: emit_op, specimen records) on the GPU, at the batch
 sizes and read mixes where the loop takes another path: one, two and three 64-read tiles, a last tile whose size is not a
 multiple of four (the dword-per-lane encode instead of the 16-byte one), an empty next tile, reads the prescan flags (shorter
 than the window, an N, a lower-case base) at every position of a group of four in the first and in the last tile, batches of
