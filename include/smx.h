@@ -27,7 +27,7 @@
  *   smx_best_hits*    <- nothing: naming a consensus from a reference FASTA is left to BLAST or a web form (DESIGN.md
  *           section 17).
  *   smx_cons_*        <- nothing: the reference hands the consensus of a specimen to an external tool (DESIGN.md
- *           section 15).
+ *           section 15), and never asks whether a cluster holds two sequences (smx_cons_phase, section 18).
  *   smx_inner_scan    <- nothing: the reference never looks between the two end windows.
  *   smx_counts_*      <- the parent summing (batch_total, batch_matched) (orchestration.py:203-207).
  *
@@ -46,7 +46,7 @@
 extern "C" {
 #endif
 
-#define SMX_ABI_VERSION 11   /* goes up with every change of this file's declarations, additions included: the binding
+#define SMX_ABI_VERSION 12   /* goes up with every change of this file's declarations, additions included: the binding
                               * (specimux_amd/_lib.py) refuses a library of another number */
 
 typedef enum {
@@ -416,6 +416,41 @@ int smx_cons_pileup(const char *reads, const uint64_t *roff, uint32_t n_reads, c
                     const smx_cons_job *jobs, uint32_t n_jobs, uint32_t *rows, int32_t *dist, float *kernel_ms);
 int smx_cons_votes(const char *reads, const uint64_t *roff, uint32_t n_reads, const int32_t *k,
                    const smx_cons_job *jobs, uint32_t n_jobs, uint32_t *votes, uint32_t *aligned, float *kernel_ms);
+
+/*
+ * variants: after the alignment and the vote of smx_cons_votes, in the same call and over the rows that are still on the
+ * device, the columns of each job where a second allele has support, every member's allele at those columns, and how
+ * the columns go together across the members -- nothing in the reference does this.
+ *   reads .. n_jobs    as for smx_cons_votes; votes / aligned receive exactly what smx_cons_votes returns for them
+ *   min_permille, min_reads   a candidate qualifies when n_minor >= min_reads and 1000 * n_minor >= min_permille * aligned[job]
+ *   max_sites          1 .. SMX_CONS_MAX_SITES: the sites kept per job, and the first dimension of every table below
+ * SMX_ERR_ARG, before anything is launched: max_sites of 0 or above SMX_CONS_MAX_SITES, min_permille above 1000.
+ * Candidates, in the order (p, insertion before base) for the vote-table positions p = 0 .. m:
+ *   kind 1, the insertion site before p: present = the votes of ins[0][0..4], absent = aligned - present; the minor allele
+ *           is the smaller of the two, `present` on a tie; codes 1 = present, 0 = absent
+ *   kind 0, the base site at p < m: over A, C, G, T and deletion (sym[0..3], sym[5]; sym[4] "other" is ignored) major = most
+ *           votes, minor = second most, ties to the lower code in both; codes as in the row: 0-3 and 5
+ * sites[job * max_sites + i], i < n_sites[job]: the first max_sites qualifying candidates; n_qualified[job]: how many
+ * qualified.  Slots past n_sites are zero.
+ * planes: job after job max_sites x 2 x ceil(n / 64) 64-bit words, plane[site][0 = minor | 1 = major][word]: bit i & 63 of
+ * word i >> 6 is set when member i is within its limit and rows[i][pos] holds that allele (kind 1: `present` = the row's
+ * insertion length is not zero).  A member with another symbol there, or above its limit, has neither bit.
+ * link[((job * max_sites + s) * max_sites + t) * 4 ..], s < t < n_sites[job]: the members with (minor, minor), (minor at s,
+ * major at t), (major at s, minor at t), (major, major); every other entry is zero.
+ * No atomics: every table is the same from run to run.  A job of n = 0 has zero tables and n_sites = n_qualified = 0.
+ */
+#define SMX_CONS_MAX_SITES 64
+
+typedef struct smx_cons_site {
+    uint32_t pos;                 /* the vote-table position p */
+    uint8_t kind, major, minor, pad;
+    uint32_t n_major, n_minor;
+} smx_cons_site;
+
+int smx_cons_phase(const char *reads, const uint64_t *roff, uint32_t n_reads, const int32_t *k,
+                   const smx_cons_job *jobs, uint32_t n_jobs, uint32_t min_permille, uint32_t min_reads, uint32_t max_sites,
+                   uint32_t *votes, uint32_t *aligned, smx_cons_site *sites, uint32_t *n_sites, uint32_t *n_qualified,
+                   uint64_t *planes, uint32_t *link, float *kernel_ms);
 
 /*
  * crosstalk: NW (global) edit distances of every read of a run to every consensus (ref) of the run, reduced on the device

@@ -9,7 +9,7 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SMX_LIB") or os.path.join(_HERE, "libsmx.so")   # SMX_LIB: A/B builds (tools/tune.sh)
 
-ABI_VERSION = 11
+ABI_VERSION = 12
 OK, ERR_ARG, ERR_UNSUPPORTED, ERR_DEVICE, ERR_OVERFLOW = 0, -1, -2, -3, -4
 TRIM = {"none": 0, "tails": 1, "barcodes": 2, "primers": 3}
 DEREP = {"none": 0, "best": 1}
@@ -29,7 +29,10 @@ PAIRS_JOB_DTYPE = np.dtype([("r0", "<u4"), ("n", "<u4")])
 assert OP_DTYPE.itemsize == 32 and HIT_DTYPE.itemsize == 24 and MINE_JOB_DTYPE.itemsize == 24
 CONS_JOB_DTYPE = np.dtype([("draft", "<u4"), ("r0", "<u4"), ("n", "<u4")])
 CONS_MAX_INS, CONS_VOTE_WORDS = 4, 26
-assert PAIRS_JOB_DTYPE.itemsize == 8 and CONS_JOB_DTYPE.itemsize == 12
+CONS_MAX_SITES = 64
+CONS_SITE_DTYPE = np.dtype([("pos", "<u4"), ("kind", "u1"), ("major", "u1"), ("minor", "u1"), ("pad", "u1"),
+                            ("n_major", "<u4"), ("n_minor", "<u4")])
+assert PAIRS_JOB_DTYPE.itemsize == 8 and CONS_JOB_DTYPE.itemsize == 12 and CONS_SITE_DTYPE.itemsize == 16
 NEAREST_JOB_DTYPE = np.dtype([("q0", "<u4"), ("nq", "<u4"), ("t0", "<u4"), ("nt", "<u4")])
 assert NEAREST_JOB_DTYPE.itemsize == 16
 HITS_JOB_DTYPE = np.dtype([("q0", "<u4"), ("nq", "<u4"), ("t0", "<u4"), ("nt", "<u4")])
@@ -113,6 +116,8 @@ SYMBOLS = [
                                           C.POINTER(C.c_float)]),
     ("smx_cons_pileup", C.c_int, [C.c_char_p, _P, C.c_uint32, _P, _P, C.c_uint32, _P, _P, C.POINTER(C.c_float)]),
     ("smx_cons_votes", C.c_int, [C.c_char_p, _P, C.c_uint32, _P, _P, C.c_uint32, _P, _P, C.POINTER(C.c_float)]),
+    ("smx_cons_phase", C.c_int, [C.c_char_p, _P, C.c_uint32, _P, _P, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                 _P, _P, _P, _P, _P, _P, _P, C.POINTER(C.c_float)]),
     ("smx_inner_scan", C.c_int, [C.c_char_p, _P, C.c_uint32, _P, _P, _P, C.c_uint32, C.c_int32, C.c_uint32, C.c_uint64,
                                  _P, _P, _P, C.POINTER(C.c_float)]),
     ("smx_inner_scan_batch", C.c_int, [_P, C.c_char_p, _P, C.c_uint32, _P, C.c_int32, C.c_uint32, C.c_uint64, _P, _P, _P,

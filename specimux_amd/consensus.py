@@ -143,18 +143,25 @@ class Polished:
 
 
 def polish(groups: Sequence[Sequence[str]], min_identity: float, rounds: int, min_aligned: int,
-           votes_fn: Callable = votes, kernel_ms: Optional[list] = None) -> Tuple[List[Tuple[str, int, int, str]], int]:
+           votes_fn: Callable = votes, kernel_ms: Optional[list] = None,
+           drafts: Optional[Sequence[str]] = None) -> Tuple[List[Tuple[str, int, int, str]], int]:
     """Polish every group (a cluster's reads, the centre first) of one device call.  A round is one votes_fn call over
-    the groups still running: the read list holds the groups back to back, then the drafts later rounds added.  Returns
-    per group (consensus, aligned, rounds, stop), and the number of votes_fn calls."""
+    the groups still running: the read list holds the groups back to back, then the drafts later rounds added.  Draft 0
+    of a group is its first member, or drafts[g] where `drafts` is given: such a draft is not a member and does not
+    vote.  Returns per group (consensus, aligned, rounds, stop), and the number of votes_fn calls."""
     reads = [r.encode("latin-1") for g in groups for r in g]
-    ks = [specimine.max_distance(len(r), min_identity) for r in reads]
     first, at = [], 0
     for g in groups:
         first.append(at)
         at += len(g)
-    drafts = [g[0] for g in groups]
-    draft_at = list(first)                                     # the centre is the first member
+    if drafts is None:
+        drafts = [g[0] for g in groups]
+        draft_at = list(first)                                 # the centre is the first member
+    else:
+        drafts = list(drafts)
+        draft_at = [len(reads) + g for g in range(len(groups))]
+        reads += [d.encode("latin-1") for d in drafts]
+    ks = [specimine.max_distance(len(r), min_identity) for r in reads]
     state = [[0, 0, "rounds"] for _ in groups]                 # aligned, rounds, stop
     live = list(range(len(groups)))
     n_calls = 0

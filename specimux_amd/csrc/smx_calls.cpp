@@ -564,20 +564,34 @@ struct {
     DevBuf scratch;             // per-lane state of the generic class, one slice per workgroup
     DevBuf hist_pm, hist_s;     // the alignment history, one slice per workgroup
     DevBuf rows, dist, votes, aligned;
+    DevBuf planes_off, sites, n_sites, n_qualified, planes, link;   // smx_cons_phase (smx_phase.hip)
 } g_cons;
 
-// One smx_cons_* call.  rows / dist (pileup) or votes / aligned (votes) receive the result, the others are null.
+struct ConsPhase {      // what smx_cons_phase adds to a votes call
+    uint32_t min_permille, min_reads, max_sites;
+    smx_cons_site *sites;
+    uint32_t *n_sites, *n_qualified;
+    uint64_t *planes;
+    uint32_t *link;
+};
+
+// One smx_cons_* call.  rows / dist (pileup) or votes / aligned (votes) receive the result, the others are null; with
+// `phase` a votes call goes on to the variant kernels over the rows and votes it left on the device.
 int cons_call(const char *reads, const uint64_t *roff, uint32_t n_reads, const int32_t *k, const smx_cons_job *jobs,
-              uint32_t n_jobs, uint32_t *rows, int32_t *dist, uint32_t *votes, uint32_t *aligned, float *kernel_ms) {
+              uint32_t n_jobs, uint32_t *rows, int32_t *dist, uint32_t *votes, uint32_t *aligned, float *kernel_ms,
+              const ConsPhase *phase = nullptr) {
     const bool pileup = rows || dist;
     if (!reads || !roff || !k || (n_jobs && (!jobs || (pileup ? !rows || !dist : !votes || !aligned))))
+        return fail(SMX_ERR_ARG, "null argument");
+    if (phase && n_jobs && (!phase->sites || !phase->n_sites || !phase->n_qualified || !phase->planes || !phase->link))
         return fail(SMX_ERR_ARG, "null argument");
     // every check of the arguments comes before the device is touched
     uint64_t hist_budget = smx::CONS_HIST_BYTES;
     if (const char *env = getenv("SMX_CONS_HIST_BYTES")) hist_budget = strtoull(env, nullptr, 10);   // test hook: few workgroups in flight
     smx::ConsPlan P;
     std::string why;
-    const int rc = smx::cons_plan(reads, roff, n_reads, k, jobs, n_jobs, hist_budget, &P, &why);
+    int rc = smx::cons_plan(reads, roff, n_reads, k, jobs, n_jobs, hist_budget, &P, &why);
+    if (rc == SMX_OK && phase) rc = smx::cons_plan_phase(phase->min_permille, phase->max_sites, &P, &why);
     if (rc != SMX_OK) return fail(rc, "%s", why.c_str());
     if (kernel_ms) *kernel_ms = 0.0f;
     if (n_jobs == 0) return SMX_OK;
@@ -612,6 +626,14 @@ int cons_call(const char *reads, const uint64_t *roff, uint32_t n_reads, const i
         HIP_TRY(W.votes.ensure((size_t)P.votes_words * 4));
         HIP_TRY(W.aligned.ensure((size_t)n_jobs * 4));
     }
+    if (phase) {
+        HIP_TRY(W.planes_off.upload(P.planes_off));
+        HIP_TRY(W.sites.ensure((size_t)P.site_slots * sizeof(smx_cons_site)));
+        HIP_TRY(W.n_sites.ensure((size_t)n_jobs * 4));
+        HIP_TRY(W.n_qualified.ensure((size_t)n_jobs * 4));
+        HIP_TRY(W.planes.ensure((size_t)P.planes_off.back() * 8));
+        HIP_TRY(W.link.ensure((size_t)P.link_words * 4));
+    }
     KernelTimer timer;
     if (kernel_ms) HIP_TRY(timer.start());
     int e = smx::chunk_for_each_class(P.n_align, [&](int c, int wr, uint32_t n, size_t jat, size_t cat) {
@@ -624,6 +646,12 @@ int cons_call(const char *reads, const uint64_t *roff, uint32_t n_reads, const i
     if (e == 0 && !pileup)
         e = smx_launch_cons_vote(nullptr, W.len.as<int32_t>(), W.jobs.p, n_jobs, P.max_words, W.rows.as<uint32_t>(),
                                  W.dist.as<int32_t>(), W.votes.as<uint32_t>(), W.aligned.as<uint32_t>());
+    if (e == 0 && phase)
+        e = smx_launch_cons_phase(nullptr, W.len.as<int32_t>(), W.jobs.p, n_jobs, W.rows.as<uint32_t>(), W.dist.as<int32_t>(),
+                                  W.votes.as<uint32_t>(), W.aligned.as<uint32_t>(), phase->min_permille, phase->min_reads,
+                                  phase->max_sites, P.max_plane_words, W.planes_off.as<uint64_t>(), W.sites.p,
+                                  W.n_sites.as<uint32_t>(), W.n_qualified.as<uint32_t>(), W.planes.as<uint64_t>(),
+                                  W.link.as<uint32_t>());
     if (e != 0) return fail(SMX_ERR_DEVICE, "consensus kernel launch failed: %s", hipGetErrorString((hipError_t)e));
     if (kernel_ms) HIP_TRY(timer.stop(kernel_ms));
     HIP_TRY(hipDeviceSynchronize());
@@ -639,6 +667,13 @@ int cons_call(const char *reads, const uint64_t *roff, uint32_t n_reads, const i
         HIP_TRY(hipMemcpy(votes, W.votes.p, (size_t)P.votes_words * 4, hipMemcpyDeviceToHost));
         HIP_TRY(hipMemcpy(aligned, W.aligned.p, (size_t)n_jobs * 4, hipMemcpyDeviceToHost));
     }
+    if (phase) {
+        HIP_TRY(hipMemcpy(phase->sites, W.sites.p, (size_t)P.site_slots * sizeof(smx_cons_site), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(phase->n_sites, W.n_sites.p, (size_t)n_jobs * 4, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(phase->n_qualified, W.n_qualified.p, (size_t)n_jobs * 4, hipMemcpyDeviceToHost));
+        if (P.planes_off.back()) HIP_TRY(hipMemcpy(phase->planes, W.planes.p, (size_t)P.planes_off.back() * 8, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(phase->link, W.link.p, (size_t)P.link_words * 4, hipMemcpyDeviceToHost));
+    }
     return SMX_OK;
 }
 }  // namespace
@@ -653,6 +688,15 @@ int smx_cons_votes(const char *reads, const uint64_t *roff, uint32_t n_reads, co
                    uint32_t n_jobs, uint32_t *votes, uint32_t *aligned, float *kernel_ms) {
     if (n_jobs && (!votes || !aligned)) return fail(SMX_ERR_ARG, "null argument");
     return cons_call(reads, roff, n_reads, k, jobs, n_jobs, nullptr, nullptr, votes, aligned, kernel_ms);
+}
+
+int smx_cons_phase(const char *reads, const uint64_t *roff, uint32_t n_reads, const int32_t *k, const smx_cons_job *jobs,
+                   uint32_t n_jobs, uint32_t min_permille, uint32_t min_reads, uint32_t max_sites, uint32_t *votes,
+                   uint32_t *aligned, smx_cons_site *sites, uint32_t *n_sites, uint32_t *n_qualified, uint64_t *planes,
+                   uint32_t *link, float *kernel_ms) {
+    if (n_jobs && (!votes || !aligned)) return fail(SMX_ERR_ARG, "null argument");
+    const ConsPhase phase{min_permille, min_reads, max_sites, sites, n_sites, n_qualified, planes, link};
+    return cons_call(reads, roff, n_reads, k, jobs, n_jobs, nullptr, nullptr, votes, aligned, kernel_ms, &phase);
 }
 
 // ---- inner scan: every pattern against the whole read, hits on the internal columns (smx_inner.hip)

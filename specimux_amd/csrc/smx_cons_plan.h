@@ -28,6 +28,11 @@ struct ConsPlan {
     uint64_t rows_words = 0, n_dist = 0, votes_words = 0;
     uint32_t max_words = 0;                // the longest draft's m + 1
     std::vector<int32_t> len;              // per read
+    // the variant tables of an smx_cons_phase call (cons_plan_phase): job j owns the site slots [j * max_sites, (j + 1) *
+    // max_sites), the 64-bit plane words [planes_off[j], planes_off[j + 1]) and the link words [j * max_sites^2 * 4, ...)
+    std::vector<uint64_t> planes_off;      // n_jobs + 1 entries
+    uint64_t site_slots = 0, link_words = 0;
+    uint32_t max_plane_words = 0;          // the largest job's ceil(n / 64)
 };
 
 // Returns SMX_OK, or the status to fail with and why.  hist_budget: CONS_HIST_BYTES, or a test's smaller figure.
@@ -112,6 +117,29 @@ inline int cons_plan(const char *reads, const uint64_t *roff, uint32_t n_reads, 
             P.chunk_start.push_back(P.chunks[c]);
         }
     }
+    return SMX_OK;
+}
+
+// The variant tables of a planned call (smx_cons_phase): the argument checks and the offsets of sites, planes and link.
+inline int cons_plan_phase(uint32_t min_permille, uint32_t max_sites, ConsPlan *plan, std::string *why) {
+    ConsPlan &P = *plan;
+    if (max_sites == 0 || max_sites > SMX_CONS_MAX_SITES) {
+        *why = "max_sites " + std::to_string(max_sites) + " is not in 1.." + std::to_string(SMX_CONS_MAX_SITES);
+        return SMX_ERR_ARG;
+    }
+    if (min_permille > 1000) {
+        *why = "min_permille " + std::to_string(min_permille) + " is above 1000";
+        return SMX_ERR_ARG;
+    }
+    P.planes_off.assign(1, 0);
+    P.max_plane_words = 0;
+    for (const ConsJobDev &J : P.jobs) {
+        const uint32_t words = (J.n + 63) / 64;
+        P.max_plane_words = std::max(P.max_plane_words, words);
+        P.planes_off.push_back(P.planes_off.back() + (uint64_t)max_sites * 2 * words);
+    }
+    P.site_slots = (uint64_t)P.jobs.size() * max_sites;
+    P.link_words = P.site_slots * max_sites * 4;
     return SMX_OK;
 }
 

@@ -180,6 +180,14 @@ int smx_launch_cons_align(void *stream, int wr, const unsigned char *d_bytes, co
 // the votes of jobs[0..n_jobs) (any n) from the rows and distances the alignment left; max_words = the largest m + 1
 int smx_launch_cons_vote(void *stream, const int32_t *d_len, const void *d_jobs, uint32_t n_jobs, uint32_t max_words,
                          const uint32_t *d_rows, const int32_t *d_dist, uint32_t *d_votes, uint32_t *d_aligned);
+// variants (smx_phase.hip), after the two launches above on the same stream: the sites of jobs[0..n_jobs) from d_votes and
+// d_aligned into d_sites (smx_cons_site, max_sites per job) / d_n_sites / d_n_qualified, the allele planes from d_rows and
+// d_dist into d_planes (job j's max_sites x 2 x ceil(n / 64) words at planes_off[j]; max_plane_words = the largest
+// ceil(n / 64)), and the max_sites x max_sites x 4 link words per job into d_link.  Every table is written in full
+int smx_launch_cons_phase(void *stream, const int32_t *d_len, const void *d_jobs, uint32_t n_jobs, const uint32_t *d_rows,
+                          const int32_t *d_dist, const uint32_t *d_votes, const uint32_t *d_aligned, uint32_t min_permille,
+                          uint32_t min_reads, uint32_t max_sites, uint32_t max_plane_words, const uint64_t *d_planes_off,
+                          void *d_sites, uint32_t *d_n_sites, uint32_t *d_n_qualified, uint64_t *d_planes, uint32_t *d_link);
 // crosstalk (smx_nearest.hip); wr, grid, per_block, d_scratch, d_bytes / d_off / d_len / d_k as for smx_launch_pairs;
 // d_group: the group per sequence.  runs[0..n_runs) (NearestRun over the class's ref list d_refs) with
 // chunk_start[0..n_runs] (nonzero each).  dist = 1: d_dist holds int32 distances, job j's nq x nt at its dist_off;
