@@ -26,6 +26,8 @@
  *   smx_nearest*      <- nothing: nor does it ask where a well's foreign reads came from.
  *   smx_best_hits*    <- nothing: naming a consensus from a reference FASTA is left to BLAST or a web form (DESIGN.md
  *           section 17).
+ *   smx_prefix_reach* <- nothing: no tool of the reference asks whether a called sequence is a left piece of one
+ *           sequence of the run and a right piece of another.
  *   smx_cons_*        <- nothing: the reference hands the consensus of a specimen to an external tool (DESIGN.md
  *           section 15), and never asks whether a cluster holds two sequences (smx_cons_phase, section 18).
  *   smx_inner_scan    <- nothing: the reference never looks between the two end windows.
@@ -46,7 +48,7 @@
 extern "C" {
 #endif
 
-#define SMX_ABI_VERSION 12   /* goes up with every change of this file's declarations, additions included: the binding
+#define SMX_ABI_VERSION 13   /* goes up with every change of this file's declarations, additions included: the binding
                               * (specimux_amd/_lib.py) refuses a library of another number */
 
 typedef enum {
@@ -522,6 +524,46 @@ int smx_best_hits(const char *seqs, const uint64_t *off, uint32_t n_seqs, const 
                   uint32_t n_jobs, uint32_t K, uint32_t min_cov_permille, uint64_t *keys, float *kernel_ms);
 int smx_best_hits_distances(const char *seqs, const uint64_t *off, uint32_t n_seqs, const int32_t *k,
                             const smx_hits_job *jobs, uint32_t n_jobs, uint32_t K, uint32_t min_cov_permille, int32_t *dist,
+                            float *kernel_ms);
+
+/*
+ * bimera: how far a prefix (and a suffix) of every called sequence of a run lies within e edits of every candidate
+ * parent, for every e in 0..E -- what a PCR chimera check needs; nothing in the reference does this (DESIGN.md section
+ * 19).  D(i, j) is the unit-cost edit distance (exact byte equality) of q[0:i] and r[0:j], anchored at both starts, and
+ *   reach(q, r, e)    the largest i in 0..len(q) with min over j of D(i, j) <= e: the longest prefix of q within e edits
+ *                     of some prefix of r; non-decreasing in e
+ *   reach_r(q, r, e)  reach(reversed q, reversed r, e): the same for suffixes
+ * computed exactly by furthest-reaching diagonals (HIP kernel smx_reach.hip), not by a bit-vector scan.
+ *   seqs / off         n_seqs sequences (concatenated, n_seqs + 1 offsets): queries and targets share one array.  No
+ *                      query or target may be empty (SMX_ERR_ARG); none longer than 2^30 - 1 (SMX_ERR_UNSUPPORTED)
+ *   weight / need      per sequence.  Target t counts for query q iff t != q (index in seqs) and weight[t] >= need[q]
+ *   jobs               each job compares the queries [q0, q0 + nq) with the targets [t0, t0 + nt).  nq = 0 and nt = 0 are
+ *                      legal.  Target ranges of different jobs may overlap; query ranges may not (SMX_ERR_ARG: every
+ *                      query has one output row)
+ *   E                  0..SMX_REACH_MAX_E (SMX_ERR_ARG)
+ * Every refusal comes before anything is launched.
+ * smx_prefix_reach: job after job, per query, per side (0 = prefix / left, 1 = suffix / right), per e in 0..E, 2 keys in
+ * ascending order, padded with UINT64_MAX:
+ *   bits 63-32  0xFFFFFFFF - reach
+ *   bits 31-0   t, the target's index in seqs
+ * so that unsigned order is "longer reach, then lower index".  Every eligible target is offered at every e.  The device
+ * keeps the slots and inserts with atomicMin over this total order: the keys are the same from run to run, and device
+ * and host memory are bounded by the sequences and sum(nq) * 4 (E + 1) keys -- nothing is sized by sum(nq * nt).  The
+ * top two of a union are the top two of its pieces' top twos, so calls over pieces of a parent pool merge exactly.
+ * smx_prefix_reach_matrix, kept for tests and inspection, writes job after job its nq x nt x 2 x (E + 1) values (query,
+ * target, side, e), UINT32_MAX where the target is not eligible.
+ * kernel_ms (may be NULL) receives the device time of the kernel (HIP events).
+ */
+#define SMX_REACH_MAX_E 15
+
+typedef struct smx_reach_job {
+    uint32_t q0, nq, t0, nt;   /* queries [q0, q0 + nq), targets [t0, t0 + nt): indices into seqs */
+} smx_reach_job;
+
+int smx_prefix_reach(const char *seqs, const uint64_t *off, uint32_t n_seqs, const uint32_t *weight, const uint32_t *need,
+                     const smx_reach_job *jobs, uint32_t n_jobs, uint32_t E, uint64_t *keys, float *kernel_ms);
+int smx_prefix_reach_matrix(const char *seqs, const uint64_t *off, uint32_t n_seqs, const uint32_t *weight,
+                            const uint32_t *need, const smx_reach_job *jobs, uint32_t n_jobs, uint32_t E, uint32_t *reach,
                             float *kernel_ms);
 
 /*

@@ -9,7 +9,7 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SMX_LIB") or os.path.join(_HERE, "libsmx.so")   # SMX_LIB: A/B builds (tools/tune.sh)
 
-ABI_VERSION = 12
+ABI_VERSION = 13
 OK, ERR_ARG, ERR_UNSUPPORTED, ERR_DEVICE, ERR_OVERFLOW = 0, -1, -2, -3, -4
 TRIM = {"none": 0, "tails": 1, "barcodes": 2, "primers": 3}
 DEREP = {"none": 0, "best": 1}
@@ -38,6 +38,9 @@ assert NEAREST_JOB_DTYPE.itemsize == 16
 HITS_JOB_DTYPE = np.dtype([("q0", "<u4"), ("nq", "<u4"), ("t0", "<u4"), ("nt", "<u4")])
 HITS_MAX_K = 16
 assert HITS_JOB_DTYPE.itemsize == 16
+REACH_JOB_DTYPE = np.dtype([("q0", "<u4"), ("nq", "<u4"), ("t0", "<u4"), ("nt", "<u4")])
+REACH_MAX_E = 15
+assert REACH_JOB_DTYPE.itemsize == 16
 
 
 class PanelDesc(C.Structure):
@@ -113,6 +116,9 @@ SYMBOLS = [
     ("smx_nearest_distances", C.c_int, [C.c_char_p, _P, C.c_uint32, _P, _P, _P, C.c_uint32, _P, C.POINTER(C.c_float)]),
     ("smx_best_hits", C.c_int, [C.c_char_p, _P, C.c_uint32, _P, _P, C.c_uint32, C.c_uint32, C.c_uint32, _P, C.POINTER(C.c_float)]),
     ("smx_best_hits_distances", C.c_int, [C.c_char_p, _P, C.c_uint32, _P, _P, C.c_uint32, C.c_uint32, C.c_uint32, _P,
+                                          C.POINTER(C.c_float)]),
+    ("smx_prefix_reach", C.c_int, [C.c_char_p, _P, C.c_uint32, _P, _P, _P, C.c_uint32, C.c_uint32, _P, C.POINTER(C.c_float)]),
+    ("smx_prefix_reach_matrix", C.c_int, [C.c_char_p, _P, C.c_uint32, _P, _P, _P, C.c_uint32, C.c_uint32, _P,
                                           C.POINTER(C.c_float)]),
     ("smx_cons_pileup", C.c_int, [C.c_char_p, _P, C.c_uint32, _P, _P, C.c_uint32, _P, _P, C.POINTER(C.c_float)]),
     ("smx_cons_votes", C.c_int, [C.c_char_p, _P, C.c_uint32, _P, _P, C.c_uint32, _P, _P, C.POINTER(C.c_float)]),

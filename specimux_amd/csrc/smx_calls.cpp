@@ -1,9 +1,10 @@
 // smx_calls.cpp -- the one-shot calls of libsmx.so over host buffers: alignments (smx_align, smx_align_batch), specimine
-// (smx_mine.hip), clusters (smx_pairs.hip), consensus (smx_cons.hip), crosstalk (smx_nearest.hip), identify (smx_hits.hip) and the inner scan (smx_inner.hip).  Each keeps one grow-only device workspace; its calls are serialised.
+// (smx_mine.hip), clusters (smx_pairs.hip), consensus (smx_cons.hip), crosstalk (smx_nearest.hip), identify (smx_hits.hip), bimera (smx_reach.hip) and the inner scan (smx_inner.hip).  Each keeps one grow-only device workspace; its calls are serialised.
 #include "smx_host.h"
 #include "smx_cons_plan.h"
 #include "smx_nearest_plan.h"
 #include "smx_hits_plan.h"
+#include "smx_reach_plan.h"
 
 int smx_align(const char *query, int qlen, const char *target, int tlen, int k, int mode, int *dist, int *starts,
               int *ends, int cap, int *nloc) {
@@ -553,6 +554,77 @@ int smx_best_hits_distances(const char *seqs, const uint64_t *off, uint32_t n_se
                             const smx_hits_job *jobs, uint32_t n_jobs, uint32_t K, uint32_t min_cov_permille, int32_t *dist,
                             float *kernel_ms) {
     return hits_call(true, seqs, off, n_seqs, k, jobs, n_jobs, K, min_cov_permille, nullptr, dist, kernel_ms);
+}
+
+// ---- bimera: every query of a job against every eligible target of the job by furthest-reaching diagonals, both
+// sides, reduced to the two furthest-reaching targets per (query, side, e) (smx_reach.hip); a workspace of its own
+namespace {
+struct {
+    std::mutex mutex;
+    DevBuf seqs, doff, len, weight, need, recs, chunk_start, jobs;
+    DevBuf out;         // the keys, or the matrix
+} g_reach;
+
+// One smx_prefix_reach* call.  matrix: reach receives job after job its nq x nt x 2 x (E + 1) values; else keys receives
+// sum(nq) x 2 x (E + 1) x 2 keys.
+int reach_call(bool matrix, const char *seqs, const uint64_t *off, uint32_t n_seqs, const uint32_t *weight,
+               const uint32_t *need, const smx_reach_job *jobs, uint32_t n_jobs, uint32_t E, uint64_t *keys, uint32_t *reach,
+               float *kernel_ms) {
+    if (!seqs || !off || !weight || !need || (n_jobs && (!jobs || (matrix ? !reach : !keys)))) return fail(SMX_ERR_ARG, "null argument");
+    // every check of the arguments comes before the device is touched
+    smx::ReachPlan P;
+    std::string why;
+    int rc = smx::reach_plan(off, n_seqs, jobs, n_jobs, E, &P, &why);
+    if (rc != SMX_OK) return fail(rc, "%s", why.c_str());
+    std::lock_guard<std::mutex> guard(g_reach.mutex);
+    SMX_TRY(require_device());
+    if (kernel_ms) *kernel_ms = 0.0f;
+    const uint64_t n_out = matrix ? P.n_values : P.n_keys;
+    if (n_out == 0) return SMX_OK;
+    const size_t out_bytes = (size_t)n_out * (matrix ? 4 : 8);
+    // "empty slot" / "not eligible" until a lane says otherwise: all-ones is UINT64_MAX as a key and UINT32_MAX as a value
+    if (P.recs.empty()) {
+        memset(matrix ? (void *)reach : (void *)keys, 0xff, out_bytes);
+        return SMX_OK;
+    }
+    std::vector<uint64_t> doff;
+    std::vector<unsigned char> pad;
+    rc = smx::reach_sequences(seqs, off, n_seqs, &doff, &pad, &why);
+    if (rc != SMX_OK) return fail(rc, "%s", why.c_str());
+    auto &W = g_reach;
+    HIP_TRY(W.seqs.upload(pad));
+    HIP_TRY(W.doff.upload(doff));
+    HIP_TRY(W.len.upload(P.len));
+    HIP_TRY(W.weight.upload(weight, (size_t)n_seqs * 4));
+    HIP_TRY(W.need.upload(need, (size_t)n_seqs * 4));
+    HIP_TRY(W.recs.upload(P.recs));
+    HIP_TRY(W.chunk_start.upload(P.chunk_start));
+    HIP_TRY(W.jobs.upload(P.jobs));
+    HIP_TRY(W.out.ensure(out_bytes));
+    HIP_TRY(hipMemset(W.out.p, 0xff, out_bytes));
+    KernelTimer timer;
+    if (kernel_ms) HIP_TRY(timer.start());
+    const int e = smx_launch_reach(nullptr, matrix, W.seqs.as<unsigned char>(), W.doff.as<uint64_t>(), W.len.as<int32_t>(),
+                                   W.weight.as<uint32_t>(), W.need.as<uint32_t>(), W.recs.p, W.chunk_start.as<uint64_t>(),
+                                   (uint32_t)P.recs.size(), W.jobs.p, (int)P.grid, P.per_block, (int)E, n_seqs,
+                                   W.out.as<unsigned long long>(), W.out.as<uint32_t>());
+    if (e != 0) return fail(SMX_ERR_DEVICE, "reach kernel launch failed: %s", hipGetErrorString((hipError_t)e));
+    if (kernel_ms) HIP_TRY(timer.stop(kernel_ms));
+    HIP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipMemcpy(matrix ? (void *)reach : (void *)keys, W.out.p, out_bytes, hipMemcpyDeviceToHost));
+    return SMX_OK;
+}
+}  // namespace
+
+int smx_prefix_reach(const char *seqs, const uint64_t *off, uint32_t n_seqs, const uint32_t *weight, const uint32_t *need,
+                     const smx_reach_job *jobs, uint32_t n_jobs, uint32_t E, uint64_t *keys, float *kernel_ms) {
+    return reach_call(false, seqs, off, n_seqs, weight, need, jobs, n_jobs, E, keys, nullptr, kernel_ms);
+}
+
+int smx_prefix_reach_matrix(const char *seqs, const uint64_t *off, uint32_t n_seqs, const uint32_t *weight,
+                            const uint32_t *need, const smx_reach_job *jobs, uint32_t n_jobs, uint32_t E, uint32_t *reach,
+                            float *kernel_ms) {
+    return reach_call(true, seqs, off, n_seqs, weight, need, jobs, n_jobs, E, nullptr, reach, kernel_ms);
 }
 
 // ---- consensus: every member read of a job aligned to the job's draft with traceback, the rows reduced to votes

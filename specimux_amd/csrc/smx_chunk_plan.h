@@ -1,8 +1,9 @@
 // smx_chunk_plan.h -- what the host side of every chunked long-read call shares (specimine, clusters, consensus,
 // crosstalk, identify): the state class of a pattern, the LDS bytes of its Peq table, the grid of a
 // class's chunk list, the scratch of the generic class, the padded copy of the sequences and the walk over the classes
-// of a call.  Host only and free of HIP calls, like the plans that use it (smx_cons_plan.h, smx_nearest_plan.h,
-// smx_hits_plan.h), so that the CPU simulations and the sanitizer drivers compile it as it is.
+// of a call.  The bimera call (smx_reach_plan.h) takes the grid and the padded copy from here and has no classes.
+// Host only and free of HIP calls, like the plans that use it (smx_cons_plan.h, smx_nearest_plan.h,
+// smx_hits_plan.h, smx_reach_plan.h), so that the CPU simulations and the sanitizer drivers compile it as it is.
 #ifndef SMX_CHUNK_PLAN_H
 #define SMX_CHUNK_PLAN_H
 #include <algorithm>

@@ -205,6 +205,15 @@ int smx_launch_hits(void *stream, int wr, int dist, const unsigned char *d_bytes
                     const int32_t *d_k, const uint32_t *d_ord, const void *d_recs, const uint64_t *d_chunk_start,
                     uint32_t n_recs, const void *d_jobs, int grid, uint64_t per_block, size_t lds_bytes, int K,
                     unsigned long long *d_keys, int32_t *d_dist, unsigned long long *d_scratch, int scratch_words);
+// bimera (smx_reach.hip).  d_bytes / d_doff: the padded sequences forwards at [0, n_seqs) and reversed at
+// [n_seqs, 2 n_seqs) (smx_reach_plan.h reach_sequences); d_len / d_weight / d_need per sequence.  recs[0..n_recs)
+// (ReachRec, smx_reach_core.h) with chunk_start[0..n_recs] (nonzero each); grid, per_block as for smx_launch_mine.
+// matrix = 0: d_keys holds 2 x (E + 1) x 2 keys per query (filled with 0xFF bytes by the caller), job j's rows from its
+// row_off; matrix = 1: d_values holds 2 x (E + 1) values per pair (filled with 0xFF bytes), job j's from its mat_off
+int smx_launch_reach(void *stream, int matrix, const unsigned char *d_bytes, const uint64_t *d_doff, const int32_t *d_len,
+                     const uint32_t *d_weight, const uint32_t *d_need, const void *d_recs, const uint64_t *d_chunk_start,
+                     uint32_t n_recs, const void *d_jobs, int grid, uint64_t per_block, int E, uint32_t n_seqs,
+                     unsigned long long *d_keys, uint32_t *d_values);
 // inner scan (smx_inner.hip): the scan over A->n_units units x npass passes of G (4 or 8) patterns, w64 = 64-bit words;
 // then one merge launch over n_reads x A->Q (read, pattern) pairs once every class has left its records
 int smx_launch_inner_scan(void *stream, int w64, int G, int npass, const smx::InnerArgs *A);

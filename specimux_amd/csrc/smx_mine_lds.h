@@ -1,7 +1,7 @@
 // smx_mine_lds.h -- device code the chunked long-read kernels share (smx_mine.hip, smx_pairs.hip, smx_cons.hip,
 // smx_nearest.hip, smx_hits.hip): the LDS carve, the Peq table of one query in LDS, a workgroup's walk
 // over its chunks (chunk_span, chunk_owner), the per-lane state of a class (chunk_lane_state) and the launch
-// (chunk_launch).  Device only; the per-pair code that runs on the host too is in smx_mine_core.h / smx_pairs_core.h /
+// (chunk_launch).  The bimera kernel (smx_reach.hip) builds no table and takes the chunk walk alone.  Device only; the per-pair code that runs on the host too is in smx_mine_core.h / smx_pairs_core.h /
 // smx_cons_core.h, the host side of the calls in smx_chunk_plan.h.
 #ifndef SMX_MINE_LDS_H
 #define SMX_MINE_LDS_H
