@@ -5,6 +5,9 @@
 #include "smx_nearest_plan.h"
 #include "smx_hits_plan.h"
 #include "smx_reach_plan.h"
+#include "smx_mine_plan.h"
+#include "smx_pairs_plan.h"
+#include "smx_inner_plan.h"
 
 int smx_align(const char *query, int qlen, const char *target, int tlen, int k, int mode, int *dist, int *starts,
               int *ends, int cap, int *nloc) {
@@ -116,25 +119,6 @@ struct {
     DevBuf jobs_out;    // the jobs, then the output
 } g_mine;
 
-// per query: LDS bytes of its Peq table and the state class of its per-lane state (smx_chunk_plan.h)
-int mine_queries(const char *queries, const uint64_t *qoff, uint32_t n_queries, std::vector<size_t> *qlds_out,
-                 std::vector<int> *qclass_out, bool allow_empty = false) {
-    std::vector<size_t> &qlds = *qlds_out;
-    std::vector<int> &qclass = *qclass_out;
-    qlds.assign(n_queries, 0);
-    qclass.assign(n_queries, 0);
-    for (uint32_t q = 0; q < n_queries; q++) {
-        if (qoff[q + 1] < qoff[q] || (qoff[q + 1] == qoff[q] && !allow_empty)) return fail(SMX_ERR_ARG, "query %u is empty", q);
-        const uint64_t m = qoff[q + 1] - qoff[q];
-        if (m > (uint64_t)INT32_MAX) return fail(SMX_ERR_UNSUPPORTED, "query %u: length %llu", q, (unsigned long long)m);
-        const smx::ChunkTable T = smx::chunk_table(queries + qoff[q], m);
-        if (!T.fits()) return fail(SMX_ERR_UNSUPPORTED, "%s", T.refusal("query " + std::to_string(q) + ": ").c_str());
-        qlds[q] = T.lds;
-        qclass[q] = T.cls;
-    }
-    return SMX_OK;
-}
-
 // the padded copy of the targets (smx_chunk_plan.h), failing the call's way
 int mine_targets(const char *targets, const uint64_t *toff, uint32_t n_targets, std::vector<uint64_t> *tdoff,
                  std::vector<int32_t> *tlen, std::vector<unsigned char> *tpad) {
@@ -153,86 +137,39 @@ int mine_call(bool distances, const char *queries, const uint64_t *qoff, uint32_
     if (!queries || !qoff || !k || !targets || !toff || (n_jobs && !jobs)) return fail(SMX_ERR_ARG, "null argument");
     std::lock_guard<std::mutex> guard(g_mine.mutex);
     SMX_TRY(require_device());
-    std::vector<size_t> qlds;
-    std::vector<int> qclass;
-    SMX_TRY(mine_queries(queries, qoff, n_queries, &qlds, &qclass));
-    std::vector<uint64_t> tdoff;
-    std::vector<int32_t> tlen;
-    std::vector<unsigned char> tpad;
-    SMX_TRY(mine_targets(targets, toff, n_targets, &tdoff, &tlen, &tpad));
-    // jobs -> (job, query) pairs with at least one target, grouped by register class, in query order within a class
-    // (a workgroup rebuilds the Peq table only when the query changes)
-    std::vector<smx::MineJobDev> djobs(n_jobs);
-    std::vector<smx::MinePair> pairs[6];
-    size_t lds_max[6] = {0, 0, 0, 0, 0, 0};
-    int words_max0 = 0;
-    uint64_t dist_off = 0, best_off = 0;
-    for (uint32_t j = 0; j < n_jobs; j++) {
-        const smx_mine_job &J = jobs[j];
-        if ((uint64_t)J.q0 + J.nq > n_queries || (uint64_t)J.t0 + J.nt > n_targets)
-            return fail(SMX_ERR_ARG, "job %u: query or target range out of bounds", j);
-        djobs[j] = smx::MineJobDev{J.q0, J.nq, J.t0, J.nt, dist_off, best_off, J.min_identity};
-        dist_off += (uint64_t)J.nq * J.nt;
-        best_off += J.nt;
-        if (J.nt == 0) continue;
-        for (uint32_t i = 0; i < J.nq; i++) {
-            const uint32_t q = J.q0 + i;
-            const int c = qclass[q];
-            lds_max[c] = std::max(lds_max[c], qlds[q]);
-            if (c == 0) words_max0 = std::max(words_max0, (int)((qoff[q + 1] - qoff[q] + 63) / 64));
-            pairs[c].push_back(smx::MinePair{j, q, k[q], 0});
-        }
-    }
-    const uint64_t n_out = distances ? dist_off : best_off;
+    // the checks, the padded targets, the jobs, the (job, query) records by class and the grids: smx_mine_plan.h
+    smx::MinePlan P;
+    std::string why;
+    const int rc = smx::mine_plan(queries, qoff, n_queries, k, targets, toff, n_targets, jobs, n_jobs, smx::CHUNK_SCRATCH_BYTES,
+                                  &P, &why);
+    if (rc != SMX_OK) return fail(rc, "%s", why.c_str());
+    const uint64_t n_out = distances ? P.n_dist : P.n_best;
     if (n_out == 0) {
         if (kernel_ms) *kernel_ms = 0.0f;
         return SMX_OK;
     }
     const size_t out_bytes = n_out * (distances ? sizeof(int32_t) : sizeof(double));
-    std::vector<uint64_t> chunk_start;            // per class: n + 1 prefix entries, one after the other
-    uint64_t chunks[6] = {0, 0, 0, 0, 0, 0};
-    for (int c = 0; c < 6; c++) {
-        std::stable_sort(pairs[c].begin(), pairs[c].end(),
-                         [](const smx::MinePair &a, const smx::MinePair &b) { return a.q < b.q; });
-        if (pairs[c].empty()) continue;
-        chunk_start.push_back(0);
-        for (const smx::MinePair &P : pairs[c]) {
-            chunks[c] += (djobs[P.job].nt + MINE_THREADS - 1) / MINE_THREADS;
-            chunk_start.push_back(chunks[c]);
-        }
-    }
-    // a workgroup takes MINE_BLOCK_CHUNKS chunks in a row (more where the grid is capped): the pair search and the
-    // Peq build of a query's run of chunks are paid once.  Measured on MI355X: one chunk per
-    // workgroup loses 1.5x on runs of cheap (decoy) chunks, runs of 8 lose ~11 % to balance on costly chunks
-    constexpr uint64_t MINE_BLOCK_CHUNKS = 8;
-    smx::ChunkGrid G[6];
-    uint32_t n_pairs[6];
-    for (int c = 0; c < 6; c++) {
-        n_pairs[c] = (uint32_t)pairs[c].size();
-        G[c] = smx::chunk_class_grid(c, chunks[c], MINE_BLOCK_CHUNKS, words_max0);
-    }
     auto &W = g_mine;
-    std::vector<smx::MinePair> all_pairs;   // class after class
-    for (int c = 0; c < 6; c++) all_pairs.insert(all_pairs.end(), pairs[c].begin(), pairs[c].end());
     const size_t jobs_bytes = n_jobs * sizeof(smx::MineJobDev);
     HIP_TRY(W.queries.upload(queries, (size_t)qoff[n_queries]));
     HIP_TRY(W.qoff.upload(qoff, ((size_t)n_queries + 1) * 8));
-    HIP_TRY(W.targets.upload(tpad));
-    HIP_TRY(W.tdoff.upload(tdoff));
-    HIP_TRY(W.tlen.upload(tlen));
-    HIP_TRY(W.pairs.upload(all_pairs));
-    HIP_TRY(W.chunk_start.upload(chunk_start));
-    if (n_pairs[0]) HIP_TRY(W.scratch.ensure((size_t)smx::chunk_scratch_words(G[0].grid, words_max0) * 8));
-    HIP_TRY(W.jobs_out.upload(djobs.data(), jobs_bytes, out_bytes));
+    HIP_TRY(W.targets.upload(P.tpad));
+    HIP_TRY(W.tdoff.upload(P.tdoff));
+    HIP_TRY(W.tlen.upload(P.tlen));
+    HIP_TRY(W.pairs.upload(P.pairs));
+    HIP_TRY(W.chunk_start.upload(P.chunk_start));
+    if (P.n_pairs[0]) HIP_TRY(W.scratch.ensure((size_t)P.scratch_words * 8));
+    HIP_TRY(W.jobs_out.upload(P.jobs.data(), jobs_bytes, out_bytes));
     void *d_out = W.jobs_out.as<char>() + jobs_bytes;
     if (!distances) HIP_TRY(hipMemset(d_out, 0, out_bytes));       // +0.0: "no pair counts"
     KernelTimer timer;
     if (kernel_ms) HIP_TRY(timer.start());
-    const int e = smx::chunk_for_each_class(n_pairs, [&](int c, int wr, uint32_t n, size_t pat, size_t cat) {
+    const int e = smx::chunk_for_each_class(P.n_pairs, [&](int c, int wr, uint32_t n, size_t pat, size_t cat) {
         return smx_launch_mine(nullptr, wr, distances, W.queries.as<unsigned char>(), W.qoff.as<uint64_t>(),
                                W.targets.as<unsigned char>(), W.tdoff.as<uint64_t>(), W.tlen.as<int32_t>(),
                                W.pairs.as<smx::MinePair>() + pat, W.chunk_start.as<uint64_t>() + cat, n, W.jobs_out.p,
-                               (int)G[c].grid, G[c].per_block, lds_max[c], d_out, W.scratch.as<unsigned long long>(), words_max0);
+                               (int)P.grid[c], P.per_block[c], P.lds_max[c], d_out, W.scratch.as<unsigned long long>(),
+                               P.words_max0);
     });
     if (e != 0) return fail(SMX_ERR_DEVICE, "mining kernel launch failed: %s", hipGetErrorString((hipError_t)e));
     if (kernel_ms) HIP_TRY(timer.stop(kernel_ms));
@@ -271,107 +208,43 @@ int pairs_call(bool distances, const char *reads, const uint64_t *roff, uint32_t
     if (!reads || !roff || !k || (n_jobs && (!jobs || !out))) return fail(SMX_ERR_ARG, "null argument");
     std::lock_guard<std::mutex> guard(g_pairs.mutex);
     SMX_TRY(require_device());
-    std::vector<size_t> qlds;
-    std::vector<int> qclass;
-    SMX_TRY(mine_queries(reads, roff, n_reads, &qlds, &qclass, true));
-    std::vector<uint64_t> doff;
-    std::vector<int32_t> len;
-    std::vector<unsigned char> pad;
-    SMX_TRY(mine_targets(reads, roff, n_reads, &doff, &len, &pad));
-    // the jobs' ranges may not overlap: every read is a row of at most one matrix
-    std::vector<uint32_t> order;
-    for (uint32_t j = 0; j < n_jobs; j++) {
-        if ((uint64_t)jobs[j].r0 + jobs[j].n > n_reads) return fail(SMX_ERR_ARG, "job %u: read range out of bounds", j);
-        if (jobs[j].n) order.push_back(j);
-    }
-    std::sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return jobs[a].r0 < jobs[b].r0; });
-    for (size_t i = 1; i < order.size(); i++)
-        if (jobs[order[i - 1]].r0 + jobs[order[i - 1]].n > jobs[order[i]].r0)
-            return fail(SMX_ERR_ARG, "jobs %u and %u overlap", order[i - 1], order[i]);
-    // jobs -> rows with at least one j > i, grouped by the register class of the row's read, in read order
-    std::vector<smx::PairsJobDev> djobs(n_jobs);
-    std::vector<smx::PairsRow> rows[6];
-    std::vector<uint64_t> chunk_start;            // per class: n + 1 prefix entries, one after the other
-    uint64_t chunks[6] = {0, 0, 0, 0, 0, 0};
-    size_t lds_max[6] = {0, 0, 0, 0, 0, 0};
-    int words_max0 = 0;
-    uint64_t n_out = 0;
-    for (uint32_t j = 0; j < n_jobs; j++) {
-        const uint64_t n = jobs[j].n;
-        djobs[j] = smx::PairsJobDev{jobs[j].r0, jobs[j].n, n_out};
-        n_out += distances ? n * (n - (n ? 1 : 0)) / 2 : n * ((n + 31) / 32);
-        for (uint32_t i = 0; i + 1 < n; i++) {
-            const uint32_t r = jobs[j].r0 + i;
-            const int c = qclass[r];
-            lds_max[c] = std::max(lds_max[c], qlds[r]);
-            if (c == 0) words_max0 = std::max(words_max0, (len[r] + 63) / 64);
-            rows[c].push_back(smx::PairsRow{j, r});
-        }
-    }
+    // the checks, the padded reads, the jobs, the rows by class and the grids: smx_pairs_plan.h
+    smx::PairsPlan P;
+    std::string why;
+    const int rc = smx::pairs_plan(distances, reads, roff, n_reads, jobs, n_jobs, smx::CHUNK_SCRATCH_BYTES, &P, &why);
+    if (rc != SMX_OK) return fail(rc, "%s", why.c_str());
     if (kernel_ms) *kernel_ms = 0.0f;
-    if (n_out == 0) return SMX_OK;
-    const size_t out_bytes = n_out * 4;
-    uint64_t n_rows = 0;
-    for (int c = 0; c < 6; c++) {
-        if (rows[c].empty()) continue;
-        n_rows += rows[c].size();
-        chunk_start.push_back(0);
-        for (const smx::PairsRow &R : rows[c]) {
-            const uint32_t n = djobs[R.job].n, i = R.read - djobs[R.job].r0;
-            chunks[c] += (n + MINE_THREADS - 1) / MINE_THREADS - (i + 1) / MINE_THREADS;
-            chunk_start.push_back(chunks[c]);
-        }
-    }
-    if (n_rows == 0) {                            // only jobs of one read: a zero word each
+    if (P.n_out == 0) return SMX_OK;
+    const size_t out_bytes = P.n_out * 4;
+    if (P.rows.empty()) {                         // only jobs of one read: a zero word each
         memset(out, 0, out_bytes);
         return SMX_OK;
     }
-    // runs of chunks per workgroup and the generic class's grid bound: as mine_call
-    constexpr uint64_t PAIRS_BLOCK_CHUNKS = 8;
-    smx::ChunkGrid G[6];
-    uint32_t n_class[6];
-    for (int c = 0; c < 6; c++) {
-        n_class[c] = (uint32_t)rows[c].size();
-        G[c] = smx::chunk_class_grid(c, chunks[c], PAIRS_BLOCK_CHUNKS, words_max0);
-    }
     auto &W = g_pairs;
-    std::vector<smx::PairsRow> all_rows;          // class after class
-    for (int c = 0; c < 6; c++) all_rows.insert(all_rows.end(), rows[c].begin(), rows[c].end());
     const size_t jobs_bytes = (n_jobs * sizeof(smx::PairsJobDev) + 15) & ~(size_t)15;
-    HIP_TRY(W.reads.upload(pad));
-    HIP_TRY(W.doff.upload(doff));
-    HIP_TRY(W.len.upload(len));
+    HIP_TRY(W.reads.upload(P.pad));
+    HIP_TRY(W.doff.upload(P.doff));
+    HIP_TRY(W.len.upload(P.len));
     HIP_TRY(W.k.upload(k, (size_t)n_reads * 4));
-    HIP_TRY(W.rows.upload(all_rows));
-    HIP_TRY(W.chunk_start.upload(chunk_start));
-    if (n_class[0]) HIP_TRY(W.scratch.ensure((size_t)smx::chunk_scratch_words(G[0].grid, words_max0) * 8));
-    HIP_TRY(W.jobs_out.upload(djobs.data(), n_jobs * sizeof(smx::PairsJobDev), jobs_bytes - n_jobs * sizeof(smx::PairsJobDev) + out_bytes));
+    HIP_TRY(W.rows.upload(P.rows));
+    HIP_TRY(W.chunk_start.upload(P.chunk_start));
+    if (P.n_rows[0]) HIP_TRY(W.scratch.ensure((size_t)P.scratch_words * 8));
+    HIP_TRY(W.jobs_out.upload(P.jobs.data(), n_jobs * sizeof(smx::PairsJobDev), jobs_bytes - n_jobs * sizeof(smx::PairsJobDev) + out_bytes));
     void *d_out = W.jobs_out.as<char>() + jobs_bytes;
     if (!distances) HIP_TRY(hipMemset(d_out, 0, out_bytes));
     KernelTimer timer;
     if (kernel_ms) HIP_TRY(timer.start());
-    const int e = smx::chunk_for_each_class(n_class, [&](int c, int wr, uint32_t n, size_t rat, size_t cat) {
+    const int e = smx::chunk_for_each_class(P.n_rows, [&](int c, int wr, uint32_t n, size_t rat, size_t cat) {
         return smx_launch_pairs(nullptr, wr, distances, W.reads.as<unsigned char>(), W.doff.as<uint64_t>(),
                                 W.len.as<int32_t>(), W.k.as<int32_t>(), W.rows.as<smx::PairsRow>() + rat,
-                                W.chunk_start.as<uint64_t>() + cat, n, W.jobs_out.p, (int)G[c].grid, G[c].per_block, lds_max[c],
-                                d_out, W.scratch.as<unsigned long long>(), words_max0);
+                                W.chunk_start.as<uint64_t>() + cat, n, W.jobs_out.p, (int)P.grid[c], P.per_block[c],
+                                P.lds_max[c], d_out, W.scratch.as<unsigned long long>(), P.words_max0);
     });
     if (e != 0) return fail(SMX_ERR_DEVICE, "pairs kernel launch failed: %s", hipGetErrorString((hipError_t)e));
     if (kernel_ms) HIP_TRY(timer.stop(kernel_ms));
     HIP_TRY(hipDeviceSynchronize());
     HIP_TRY(hipMemcpy(out, d_out, out_bytes, hipMemcpyDeviceToHost));
-    if (!distances)                               // mirror the triangle: bit i of row j for every bit j > i of row i
-        for (const smx::PairsJobDev &J : djobs) {
-            const uint32_t nw = (J.n + 31) / 32;
-            uint32_t *adj = out + J.out_off;
-            for (uint32_t i = 0; i < J.n; i++)
-                for (uint32_t w = i / 32; w < nw; w++) {
-                    uint32_t bits = adj[(size_t)i * nw + w];
-                    if (w == i / 32) bits &= i % 32 == 31 ? 0u : ~0u << (i % 32 + 1);   // the bits right of the diagonal
-                    for (; bits; bits &= bits - 1)
-                        adj[(size_t)(w * 32 + (uint32_t)__builtin_ctz(bits)) * nw + i / 32] |= 1u << (i % 32);
-                }
-        }
+    if (!distances) smx::pairs_mirror(P, out);    // bit i of row j for every bit j > i of row i
     return SMX_OK;
 }
 }  // namespace
@@ -780,151 +653,71 @@ struct {
     DevBuf bases, roff, ustart, unit_read, recs, out, tables;
 } g_inner;
 
-struct InnerClass {      // the patterns of one word width, in passes of G
-    int w64 = 0, G = 4, npass = 0;
-    std::vector<uint32_t> idx;        // pattern indices of the call
-    size_t peq_at = 0, tab_at = 0;    // offsets into the table blob: match words; pm, pk, jmap (npass * G ints each)
-};
-
-constexpr uint64_t INNER_DEFAULT_BUDGET = (uint64_t)1 << 30;
-
 // The reads are seq[i][0 .. len[i]); with `flat` they also lie back to back from flat (seq[i] = flat + flat_off[i]).
 int inner_call(const char *patterns, const uint32_t *poff, uint32_t Q, const int32_t *k, const char *const *seq,
                const uint32_t *len, const uint8_t *flat, uint32_t n_reads, int32_t margin, uint32_t H,
                uint64_t budget, uint8_t *nhit, int8_t *hit_dist, int32_t *hit_end, float *kernel_ms) {
     if (!patterns || !poff || !k) return fail(SMX_ERR_ARG, "null argument");
     if (n_reads && (!seq || !len || !nhit || !hit_dist || !hit_end)) return fail(SMX_ERR_ARG, "null argument");
-    if (Q < 1 || Q > INNER_MAX_PATTERNS) return fail(SMX_ERR_ARG, "n_patterns %u outside 1..%d", Q, INNER_MAX_PATTERNS);
-    if (H < 1 || H > INNER_MAX_HITS) return fail(SMX_ERR_ARG, "max_hits %u outside 1..%d", H, INNER_MAX_HITS);
-    if (margin < 0) return fail(SMX_ERR_ARG, "margin %d is negative", margin);
-    std::vector<unsigned long long> peq((size_t)Q * 16);
-    std::vector<int> pm(Q);
-    InnerClass cls[2];
-    cls[1].w64 = 1;
-    int lead = 1;
-    for (uint32_t j = 0; j < Q; j++) {
-        if (poff[j + 1] <= poff[j] || poff[j + 1] - poff[j] > 64)
-            return fail(SMX_ERR_ARG, "pattern %u: length outside 1..64", j);
-        const int m = (int)(poff[j + 1] - poff[j]);
-        if (k[j] < 0 || k[j] >= m) return fail(SMX_ERR_ARG, "pattern %u: threshold %d outside 0..%d", j, k[j], m - 1);
-        std::string bad;
-        if (!build_peq(patterns + poff[j], m, &peq[(size_t)j * 16], &bad)) return fail(SMX_ERR_ARG, "pattern %u: %s", j, bad.c_str());
-        pm[j] = m;
-        lead = std::max(lead, m + k[j]);
-        cls[m > 32 ? 1 : 0].idx.push_back(j);
-    }
-    const int PL = smx::inner_piece_len(lead), RW = smx::inner_rec_words((int)H);
+    // the pattern checks, lead / PL / RW, the table blob and the launch groups: smx_inner_plan.h
+    smx::InnerPlan P;
+    std::string why;
+    int rc = smx::inner_plan(patterns, poff, Q, k, margin, H, budget, smx::INNER_DEFAULT_BUDGET,
+                             smx::InnerAlphabet{code_of, build_peq}, &P, &why);
+    if (rc != SMX_OK) return fail(rc, "%s", why.c_str());
     std::lock_guard<std::mutex> guard(g_inner.mutex);
     SMX_TRY(require_device());
     if (kernel_ms) *kernel_ms = 0.0f;
     if (n_reads == 0) return SMX_OK;
-    // pattern tables: byte -> code map, then per class the match words [pass][code][G] and pm / pk / jmap
-    std::vector<unsigned char> blob(256);
-    for (int c = 0; c < 256; c++) blob[c] = (unsigned char)code_of((unsigned char)c);
-    for (InnerClass &C : cls) {
-        if (C.idx.empty()) continue;
-        C.G = C.idx.size() <= 4 ? 4 : 8;
-        C.npass = (int)((C.idx.size() + C.G - 1) / C.G);
-        const size_t slots = (size_t)C.npass * C.G;
-        std::vector<int> tab(3 * slots);
-        for (size_t s = 0; s < slots; s++) {
-            const bool real = s < C.idx.size();
-            tab[s] = real ? pm[C.idx[s]] : 1;
-            tab[slots + s] = real ? k[C.idx[s]] : -1;
-            tab[2 * slots + s] = real ? (int)C.idx[s] : -1;
-        }
-        if (C.w64) {
-            std::vector<uint64_t> w(slots * 16, 0);
-            for (size_t s = 0; s < C.idx.size(); s++)
-                for (int c = 0; c < 16; c++) w[((s / C.G) * 16 + c) * C.G + s % C.G] = peq[(size_t)C.idx[s] * 16 + c];
-            C.peq_at = blob_add(blob, w);
-        } else {
-            std::vector<uint32_t> w(slots * 16, 0);
-            for (size_t s = 0; s < C.idx.size(); s++)
-                for (int c = 0; c < 16; c++) w[((s / C.G) * 16 + c) * C.G + s % C.G] = (uint32_t)peq[(size_t)C.idx[s] * 16 + c];
-            C.peq_at = blob_add(blob, w);
-        }
-        C.tab_at = blob_add(blob, tab);
-    }
     auto &W = g_inner;
-    HIP_TRY(W.tables.upload(blob));
-    if (budget == 0) budget = INNER_DEFAULT_BUDGET;
-    auto pieces_of = [&](uint32_t n) -> uint64_t {
-        return (uint64_t)n > 2 * (uint64_t)margin ? ((uint64_t)n - 2 * (uint64_t)margin + PL - 1) / PL : 0;
-    };
-    const uint64_t out_per_read = (uint64_t)Q * (1 + 5 * (uint64_t)H);
+    HIP_TRY(W.tables.upload(P.blob));
     KernelTimer timer;
-    std::vector<uint64_t> roff;
-    std::vector<uint32_t> ustart, unit_read;
+    smx::InnerGroup g;
     std::vector<unsigned char> stage, out;
-    // chunks of whole reads: everything one launch group keeps on the device fits the budget (one read always goes)
-    for (uint32_t r0 = 0; r0 < n_reads;) {
-        uint64_t bytes = 64, units = 0, nb = 0;
-        uint32_t r1 = r0;
-        while (r1 < n_reads) {
-            if (len[r1] > (uint32_t)INT32_MAX) return fail(SMX_ERR_ARG, "read %u: longer than 2^31 - 1 bases", r1);
-            const uint64_t np = pieces_of(len[r1]);
-            const uint64_t cost = (uint64_t)len[r1] + 12 + np * (4 + (uint64_t)Q * RW * 4) + out_per_read;
-            if (r1 > r0 && (bytes + cost > budget || units + np > 0x7fffffffull)) break;
-            bytes += cost;
-            units += np;
-            nb += len[r1];
-            r1++;
-        }
-        if (units > 0xffffffffull) return fail(SMX_ERR_UNSUPPORTED, "read %u: too many pieces for one launch", r0);
-        const uint32_t nr = r1 - r0;
-        roff.resize((size_t)nr + 1);
-        ustart.resize((size_t)nr + 1);
-        unit_read.resize((size_t)units);
-        roff[0] = 0;
-        ustart[0] = 0;
-        for (uint32_t i = 0; i < nr; i++) {
-            const uint32_t np = (uint32_t)pieces_of(len[r0 + i]);
-            roff[i + 1] = roff[i] + len[r0 + i];
-            for (uint32_t p = 0; p < np; p++) unit_read[(size_t)ustart[i] + p] = i;
-            ustart[i + 1] = ustart[i] + np;
-        }
+    // groups of whole reads: everything one launch group keeps on the device fits the budget (one read always goes)
+    for (uint32_t r0 = 0; r0 < n_reads; r0 = g.r1) {
+        rc = P.next_group(len, n_reads, r0, &g, &why);
+        if (rc != SMX_OK) return fail(rc, "%s", why.c_str());
+        const uint32_t nr = g.nr();
         const unsigned char *src;
         if (flat) {
             src = (const unsigned char *)seq[r0];
         } else {
-            stage.resize((size_t)nb);
+            stage.resize(g.nb);
             for (uint32_t i = 0; i < nr; i++)
-                if (len[r0 + i]) memcpy(stage.data() + roff[i], seq[r0 + i], len[r0 + i]);
+                if (len[r0 + i]) memcpy(stage.data() + g.roff[i], seq[r0 + i], len[r0 + i]);
             src = stage.data();
         }
-        const size_t he_bytes = (size_t)nr * Q * H * 4, hd_bytes = (size_t)nr * Q * H, nh_bytes = (size_t)nr * Q;
-        HIP_TRY(W.bases.upload(src, (size_t)nb, 32));
-        HIP_TRY(W.roff.upload(roff));
-        HIP_TRY(W.ustart.upload(ustart));
-        HIP_TRY(W.unit_read.upload(unit_read));
-        HIP_TRY(W.recs.ensure((size_t)units * Q * RW * 4));
-        HIP_TRY(W.out.ensure(he_bytes + hd_bytes + nh_bytes));
+        HIP_TRY(W.bases.upload(src, g.nb, g.bases_bytes - g.nb));    // readable to the end of the last byte's 16-byte word
+        HIP_TRY(W.roff.upload(g.roff));
+        HIP_TRY(W.ustart.upload(g.ustart));
+        HIP_TRY(W.unit_read.upload(g.unit_read));
+        HIP_TRY(W.recs.ensure(g.rec_bytes));
+        HIP_TRY(W.out.ensure(g.out_bytes()));
         smx::InnerArgs A{};
         A.lut = W.tables.as<unsigned char>();
         A.bases = W.bases.as<smx::mine_u4>();
         A.roff = W.roff.as<uint64_t>();
         A.ustart = W.ustart.as<uint32_t>();
         A.unit_read = W.unit_read.as<uint32_t>();
-        A.n_units = (uint32_t)units;
+        A.n_units = (uint32_t)g.units;
         A.Q = (int)Q;
         A.H = (int)H;
         A.margin = margin;
-        A.PL = PL;
-        A.lead = lead;
+        A.PL = P.PL;
+        A.lead = P.lead;
         A.recs = W.recs.as<uint32_t>();
         int32_t *d_he = W.out.as<int32_t>();
-        int8_t *d_hd = W.out.as<int8_t>() + he_bytes;
-        uint8_t *d_nh = W.out.as<uint8_t>() + he_bytes + hd_bytes;
+        int8_t *d_hd = W.out.as<int8_t>() + g.he_bytes;
+        uint8_t *d_nh = W.out.as<uint8_t>() + g.he_bytes + g.hd_bytes;
         if (kernel_ms) HIP_TRY(timer.start());
         int e = 0;
-        for (const InnerClass &C : cls) {
-            if (C.idx.empty() || units == 0 || e != 0) continue;
-            const size_t slots = (size_t)C.npass * C.G;
+        for (const smx::InnerClass &C : P.cls) {
+            if (C.idx.empty() || g.units == 0 || e != 0) continue;
             A.peq = W.tables.as<char>() + C.peq_at;
             A.pm = (const int *)(W.tables.as<char>() + C.tab_at);
-            A.pk = A.pm + slots;
-            A.jmap = A.pm + 2 * slots;
+            A.pk = A.pm + C.slots();
+            A.jmap = A.pm + 2 * C.slots();
             e = smx_launch_inner_scan(nullptr, C.w64, C.G, C.npass, &A);
         }
         if (e == 0) e = smx_launch_inner_merge(nullptr, &A, nr, d_nh, d_hd, d_he);
@@ -935,12 +728,11 @@ int inner_call(const char *patterns, const uint32_t *poff, uint32_t Q, const int
             *kernel_ms += ms;
         }
         HIP_TRY(hipDeviceSynchronize());
-        out.resize(he_bytes + hd_bytes + nh_bytes);
+        out.resize(g.out_bytes());
         HIP_TRY(hipMemcpy(out.data(), W.out.p, out.size(), hipMemcpyDeviceToHost));
-        memcpy(hit_end + (size_t)r0 * Q * H, out.data(), he_bytes);
-        memcpy(hit_dist + (size_t)r0 * Q * H, out.data() + he_bytes, hd_bytes);
-        memcpy(nhit + (size_t)r0 * Q, out.data() + he_bytes + hd_bytes, nh_bytes);
-        r0 = r1;
+        memcpy(hit_end + (size_t)r0 * Q * H, out.data(), g.he_bytes);
+        memcpy(hit_dist + (size_t)r0 * Q * H, out.data() + g.he_bytes, g.hd_bytes);
+        memcpy(nhit + (size_t)r0 * Q, out.data() + g.he_bytes + g.hd_bytes, g.nh_bytes);
     }
     return SMX_OK;
 }

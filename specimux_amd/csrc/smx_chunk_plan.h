@@ -65,14 +65,44 @@ inline ChunkGrid chunk_grid(uint64_t chunks, uint64_t floor, uint64_t cap) {
 // words_max0 = the class's longest pattern in words.  Its grid is capped so that the slices fit CHUNK_SCRATCH_BYTES,
 // and the scratch is grid[0] slices: the kernels index it by blockIdx.x.
 inline uint64_t chunk_slice_words(int words_max0) { return (uint64_t)3 * words_max0 * MINE_THREADS; }
-inline uint64_t chunk_scratch_cap(int words_max0) {
-    return std::max<uint64_t>(1, CHUNK_SCRATCH_BYTES / std::max<uint64_t>(chunk_slice_words(words_max0) * 8, 1));
+// `budget` is CHUNK_SCRATCH_BYTES in production; a test passes less to cap the grid without gigabytes (one slice always goes).
+inline uint64_t chunk_scratch_cap(int words_max0, uint64_t budget = CHUNK_SCRATCH_BYTES) {
+    return std::max<uint64_t>(1, budget / std::max<uint64_t>(chunk_slice_words(words_max0) * 8, 1));
 }
 inline uint64_t chunk_scratch_words(uint64_t grid0, int words_max0) { return grid0 * chunk_slice_words(words_max0); }
 
 // The grid of class c of a call: chunk_grid, the generic class's capped by its scratch as well.
-inline ChunkGrid chunk_class_grid(int c, uint64_t chunks, uint64_t floor, int words_max0) {
-    return chunk_grid(chunks, floor, c == 0 ? chunk_scratch_cap(words_max0) : CHUNK_GRID_MAX);
+inline ChunkGrid chunk_class_grid(int c, uint64_t chunks, uint64_t floor, int words_max0, uint64_t budget = CHUNK_SCRATCH_BYTES) {
+    return chunk_grid(chunks, floor, c == 0 ? chunk_scratch_cap(words_max0, budget) : CHUNK_GRID_MAX);
+}
+
+// Per query (specimine) or read (clusters, which allows empty ones): the LDS bytes of its Peq table and its state class.
+// Returns SMX_OK, or the status to fail with and why.
+inline int mine_queries(const char *queries, const uint64_t *qoff, uint32_t n_queries, bool allow_empty, std::vector<size_t> *qlds_out,
+                        std::vector<int> *qclass_out, std::string *why) {
+    std::vector<size_t> &qlds = *qlds_out;
+    std::vector<int> &qclass = *qclass_out;
+    qlds.assign(n_queries, 0);
+    qclass.assign(n_queries, 0);
+    for (uint32_t q = 0; q < n_queries; q++) {
+        if (qoff[q + 1] < qoff[q] || (qoff[q + 1] == qoff[q] && !allow_empty)) {
+            *why = "query " + std::to_string(q) + " is empty";
+            return SMX_ERR_ARG;
+        }
+        const uint64_t m = qoff[q + 1] - qoff[q];
+        if (m > (uint64_t)INT32_MAX) {
+            *why = "query " + std::to_string(q) + ": length " + std::to_string(m);
+            return SMX_ERR_UNSUPPORTED;
+        }
+        const ChunkTable T = chunk_table(queries + qoff[q], m);
+        if (!T.fits()) {
+            *why = T.refusal("query " + std::to_string(q) + ": ");
+            return SMX_ERR_UNSUPPORTED;
+        }
+        qlds[q] = T.lds;
+        qclass[q] = T.cls;
+    }
+    return SMX_OK;
 }
 
 // The sequences as the kernels read them: 16-byte aligned copies, 16 bytes of slack at the end (a lane loads 16 bytes at

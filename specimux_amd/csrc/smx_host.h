@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "smx.h"
+#include "smx_blob.h"       // blob_add
 #include "smx_internal.h"
 
 // smx_api.cpp (smx_io.cpp uses it too): set the thread-local message and return `code`
@@ -44,15 +45,6 @@ int code_of(unsigned char ch);                         // index in smx::kCodeCha
 unsigned char complement_of(unsigned char ch);
 // bit i of peq[c] = eq(pattern[i], char of code c); code 15 never matches
 bool build_peq(const char *pat, int m, unsigned long long *peq16, std::string *bad);
-
-// Appends a table to a blob that goes to the device in one piece: 16-byte aligned, at least 16 bytes.  Returns its offset.
-template <typename T>
-size_t blob_add(std::vector<unsigned char> &blob, const std::vector<T> &v) {
-    size_t off = (blob.size() + 15) & ~(size_t)15;
-    blob.resize(off + std::max<size_t>(v.size() * sizeof(T), 16));
-    if (!v.empty()) memcpy(blob.data() + off, v.data(), v.size() * sizeof(T));
-    return off;
-}
 
 struct DevBuf {   // grow-only device buffer of the host-buffer convenience paths; released by hand (some live in globals)
     void *p = nullptr;

@@ -125,7 +125,7 @@ struct InnerArgs {
     const void *peq;               // [pass][16 codes][G] match words, 32 or 64 bits wide
     const int *pm, *pk, *jmap;     // [pass * G]: pattern length, threshold (-1: padding slot), index in the call (-1: padding)
     const unsigned char *lut;      // 256: read byte -> code
-    const mine_u4 *bases;          // the chunk's reads back to back, 16 spare bytes behind them
+    const mine_u4 *bases;          // the chunk's reads back to back, readable to the end of the last byte's 16-byte word
     const uint64_t *roff;          // n_reads + 1 byte offsets into bases
     const uint32_t *unit_read;     // per unit: its read
     const uint32_t *ustart;        // n_reads + 1: first unit of each read

@@ -54,6 +54,18 @@ SMX_HD int mine_min(int a, int b) {
 #endif
 }
 
+// The arithmetic of the owner search of a chunk walk (chunk_owner, smx_mine_lds.h), which keeps the ballot: the record
+// is in [p, p + n).  A round probes 64 records step = chunk_owner_step(n) apart, lane l the record
+// chunk_owner_probe(p, step, l) if that is below p + n; "chunk_start[probe] <= lo" holds on a prefix of the lanes (lane
+// 0 always), and with `count` lanes holding, the record is in the step-wide range of the last of them.  The host twin
+// (tests/cpu/chunk_owner_host.h) runs the same functions over 64 emulated lanes.
+SMX_HD uint32_t chunk_owner_step(uint32_t n) { return (n + 63) / 64; }
+SMX_HD uint32_t chunk_owner_probe(uint32_t p, uint32_t step, unsigned lane) { return p + lane * step; }
+// the range after the round: it starts chunk_owner_advance(step, count) records further on and holds
+// chunk_owner_left(step, end, p) records, p the new start and end the old p + n
+SMX_HD uint32_t chunk_owner_advance(uint32_t step, uint32_t count) { return (count - 1) * step; }
+SMX_HD uint32_t chunk_owner_left(uint32_t step, uint32_t end, uint32_t p) { return step < end - p ? step : end - p; }
+
 // Hyyro's block step with a horizontal carry in and out (hin, hout in {-1, 0, +1}).
 SMX_HD int mine_step(u64 Eq, u64 &Pv, u64 &Mv, int hin) {
     const u64 hneg = hin < 0 ? 1ull : 0ull, hpos = hin > 0 ? 1ull : 0ull;

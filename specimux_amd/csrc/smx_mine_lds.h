@@ -69,12 +69,12 @@ __device__ __forceinline__ ChunkSpan chunk_span(const uint64_t *__restrict__ chu
 __device__ __forceinline__ uint32_t chunk_owner(const uint64_t *__restrict__ chunk_start, uint32_t n, uint64_t lo) {
     uint32_t p = 0;                                // the record is in [p, p + n)
     while (n > 1) {
-        const uint32_t step = (n + 63) / 64, idx = p + (threadIdx.x & 63) * step;
+        const uint32_t step = chunk_owner_step(n), idx = chunk_owner_probe(p, step, threadIdx.x & 63);
         const bool le = idx < p + n && chunk_start[idx] <= lo;    // true on a prefix of the lanes (lane 0 always)
-        const uint32_t below = (uint32_t)__popcll(__ballot(le)) - 1;
+        const uint32_t count = (uint32_t)__popcll(__ballot(le));
         const uint32_t end = p + n;
-        p += below * step;
-        n = min(step, end - p);
+        p += chunk_owner_advance(step, count);
+        n = chunk_owner_left(step, end, p);
     }
     return p;
 }
