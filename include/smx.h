@@ -29,7 +29,8 @@
  *   smx_prefix_reach* <- nothing: no tool of the reference asks whether a called sequence is a left piece of one
  *           sequence of the run and a right piece of another.
  *   smx_cons_*        <- nothing: the reference hands the consensus of a specimen to an external tool (DESIGN.md
- *           section 15), and never asks whether a cluster holds two sequences (smx_cons_phase, section 18).
+ *           section 15), and never asks whether a cluster holds two sequences (smx_cons_phase, section 18) or how far
+ *           a called sequence can be trusted (smx_cons_resample, section 20).
  *   smx_inner_scan    <- nothing: the reference never looks between the two end windows.
  *   smx_counts_*      <- the parent summing (batch_total, batch_matched) (orchestration.py:203-207).
  *
@@ -48,8 +49,10 @@
 extern "C" {
 #endif
 
-#define SMX_ABI_VERSION 13   /* goes up with every change of this file's declarations, additions included: the binding
-                              * (specimux_amd/_lib.py) refuses a library of another number */
+#define SMX_ABI_VERSION 13   /* goes up when an existing declaration of this file changes: the binding
+                              * (specimux_amd/_lib.py) refuses a library of another number.  A declaration that is only
+                              * added needs no new number: the binding looks every symbol up and refuses a library that
+                              * lacks one */
 
 typedef enum {
     SMX_OK = 0,
@@ -453,6 +456,32 @@ int smx_cons_phase(const char *reads, const uint64_t *roff, uint32_t n_reads, co
                    const smx_cons_job *jobs, uint32_t n_jobs, uint32_t min_permille, uint32_t min_reads, uint32_t max_sites,
                    uint32_t *votes, uint32_t *aligned, smx_cons_site *sites, uint32_t *n_sites, uint32_t *n_qualified,
                    uint64_t *planes, uint32_t *link, float *kernel_ms);
+
+/*
+ * support: after the alignment and the vote of smx_cons_votes, in the same call and over the rows that are still on the
+ * device, the vote taken again over SMX_CONS_REPLICATES subsets of each job's members at once, for up to
+ * SMX_CONS_MAX_LEVELS sets of subsets (levels): which subsets would call each column as the draft has it (DESIGN.md
+ * section 20) -- nothing in the reference does this.
+ *   reads .. n_jobs    as for smx_cons_votes; votes / aligned receive exactly what smx_cons_votes returns for them
+ *   masks              n_levels x (the sum of the jobs' n) 64-bit words: level after level, within a level job after job in
+ *                      the order given, one word per member.  Replicate b (0..63) of a level is the set of members whose
+ *                      word has bit b set; its voters are those of them within their limit
+ * SMX_ERR_ARG, before the device is asked for and also where n_jobs is 0: n_levels of 0 or above SMX_CONS_MAX_LEVELS, a null
+ * masks while some job has members.
+ * Over the voters of replicate b at column p of a draft of m bases: a[0..3] the row words with symbol A, C, G, T, del those
+ * with symbol 5, ins those with an insertion before p, n_b the voters.  With dc the code of the draft's byte at p (0-3, 4 =
+ * any other byte), replicate b keeps column p iff
+ *     !(2 ins > n_b)  &&  ( p == m  ||  ( !(2 del > n_b)  &&  ( max a == 0  ||  (dc < 4 && a[dc] == max a) ) ) )
+ * agree: job after job, level after level, m + 1 words: bit b of word p is set iff replicate b keeps column p.
+ * sub_aligned[(job * n_levels + level) * 64 + b]: n_b.  A replicate without voters keeps every column: the caller decides
+ * what that means.  A job of n = 0 has all-ones words and zero counts.  No atomics: the same from run to run.
+ */
+#define SMX_CONS_REPLICATES 64
+#define SMX_CONS_MAX_LEVELS 16
+
+int smx_cons_resample(const char *reads, const uint64_t *roff, uint32_t n_reads, const int32_t *k,
+                      const smx_cons_job *jobs, uint32_t n_jobs, const uint64_t *masks, uint32_t n_levels,
+                      uint32_t *votes, uint32_t *aligned, uint64_t *agree, uint32_t *sub_aligned, float *kernel_ms);
 
 /*
  * crosstalk: NW (global) edit distances of every read of a run to every consensus (ref) of the run, reduced on the device

@@ -30,6 +30,7 @@ assert OP_DTYPE.itemsize == 32 and HIT_DTYPE.itemsize == 24 and MINE_JOB_DTYPE.i
 CONS_JOB_DTYPE = np.dtype([("draft", "<u4"), ("r0", "<u4"), ("n", "<u4")])
 CONS_MAX_INS, CONS_VOTE_WORDS = 4, 26
 CONS_MAX_SITES = 64
+CONS_REPLICATES, CONS_MAX_LEVELS = 64, 16
 CONS_SITE_DTYPE = np.dtype([("pos", "<u4"), ("kind", "u1"), ("major", "u1"), ("minor", "u1"), ("pad", "u1"),
                             ("n_major", "<u4"), ("n_minor", "<u4")])
 assert PAIRS_JOB_DTYPE.itemsize == 8 and CONS_JOB_DTYPE.itemsize == 12 and CONS_SITE_DTYPE.itemsize == 16
@@ -124,6 +125,8 @@ SYMBOLS = [
     ("smx_cons_votes", C.c_int, [C.c_char_p, _P, C.c_uint32, _P, _P, C.c_uint32, _P, _P, C.POINTER(C.c_float)]),
     ("smx_cons_phase", C.c_int, [C.c_char_p, _P, C.c_uint32, _P, _P, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
                                  _P, _P, _P, _P, _P, _P, _P, C.POINTER(C.c_float)]),
+    ("smx_cons_resample", C.c_int, [C.c_char_p, _P, C.c_uint32, _P, _P, C.c_uint32, _P, C.c_uint32, _P, _P, _P, _P,
+                                    C.POINTER(C.c_float)]),
     ("smx_inner_scan", C.c_int, [C.c_char_p, _P, C.c_uint32, _P, _P, _P, C.c_uint32, C.c_int32, C.c_uint32, C.c_uint64,
                                  _P, _P, _P, C.POINTER(C.c_float)]),
     ("smx_inner_scan_batch", C.c_int, [_P, C.c_char_p, _P, C.c_uint32, _P, C.c_int32, C.c_uint32, C.c_uint64, _P, _P, _P,

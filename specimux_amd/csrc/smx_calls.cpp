@@ -510,6 +510,7 @@ struct {
     DevBuf hist_pm, hist_s;     // the alignment history, one slice per workgroup
     DevBuf rows, dist, votes, aligned;
     DevBuf planes_off, sites, n_sites, n_qualified, planes, link;   // smx_cons_phase (smx_phase.hip)
+    DevBuf masks, member_off, agree_off, agree, sub_aligned;        // smx_cons_resample (smx_resample.hip)
 } g_cons;
 
 struct ConsPhase {      // what smx_cons_phase adds to a votes call
@@ -520,16 +521,25 @@ struct ConsPhase {      // what smx_cons_phase adds to a votes call
     uint32_t *link;
 };
 
+struct ConsResample {   // what smx_cons_resample adds to a votes call
+    const uint64_t *masks;
+    uint32_t n_levels;
+    uint64_t *agree;
+    uint32_t *sub_aligned;
+};
+
 // One smx_cons_* call.  rows / dist (pileup) or votes / aligned (votes) receive the result, the others are null; with
-// `phase` a votes call goes on to the variant kernels over the rows and votes it left on the device.
+// `phase` a votes call goes on to the variant kernels over the rows and votes it left on the device, with `resample` to
+// the resampling kernel over the rows and distances.
 int cons_call(const char *reads, const uint64_t *roff, uint32_t n_reads, const int32_t *k, const smx_cons_job *jobs,
               uint32_t n_jobs, uint32_t *rows, int32_t *dist, uint32_t *votes, uint32_t *aligned, float *kernel_ms,
-              const ConsPhase *phase = nullptr) {
+              const ConsPhase *phase = nullptr, const ConsResample *resample = nullptr) {
     const bool pileup = rows || dist;
     if (!reads || !roff || !k || (n_jobs && (!jobs || (pileup ? !rows || !dist : !votes || !aligned))))
         return fail(SMX_ERR_ARG, "null argument");
     if (phase && n_jobs && (!phase->sites || !phase->n_sites || !phase->n_qualified || !phase->planes || !phase->link))
         return fail(SMX_ERR_ARG, "null argument");
+    if (resample && n_jobs && (!resample->agree || !resample->sub_aligned)) return fail(SMX_ERR_ARG, "null argument");
     // every check of the arguments comes before the device is touched
     uint64_t hist_budget = smx::CONS_HIST_BYTES;
     if (const char *env = getenv("SMX_CONS_HIST_BYTES")) hist_budget = strtoull(env, nullptr, 10);   // test hook: few workgroups in flight
@@ -537,6 +547,7 @@ int cons_call(const char *reads, const uint64_t *roff, uint32_t n_reads, const i
     std::string why;
     int rc = smx::cons_plan(reads, roff, n_reads, k, jobs, n_jobs, hist_budget, &P, &why);
     if (rc == SMX_OK && phase) rc = smx::cons_plan_phase(phase->min_permille, phase->max_sites, &P, &why);
+    if (rc == SMX_OK && resample) rc = smx::cons_plan_resample(resample->masks != nullptr, resample->n_levels, &P, &why);
     if (rc != SMX_OK) return fail(rc, "%s", why.c_str());
     if (kernel_ms) *kernel_ms = 0.0f;
     if (n_jobs == 0) return SMX_OK;
@@ -579,6 +590,13 @@ int cons_call(const char *reads, const uint64_t *roff, uint32_t n_reads, const i
         HIP_TRY(W.planes.ensure((size_t)P.planes_off.back() * 8));
         HIP_TRY(W.link.ensure((size_t)P.link_words * 4));
     }
+    if (resample) {
+        HIP_TRY(W.masks.upload(resample->masks, (size_t)P.mask_words * 8));
+        HIP_TRY(W.member_off.upload(P.member_off));
+        HIP_TRY(W.agree_off.upload(P.agree_off));
+        HIP_TRY(W.agree.ensure((size_t)P.agree_off.back() * 8));
+        HIP_TRY(W.sub_aligned.ensure((size_t)P.sub_words * 4));
+    }
     KernelTimer timer;
     if (kernel_ms) HIP_TRY(timer.start());
     int e = smx::chunk_for_each_class(P.n_align, [&](int c, int wr, uint32_t n, size_t jat, size_t cat) {
@@ -597,6 +615,11 @@ int cons_call(const char *reads, const uint64_t *roff, uint32_t n_reads, const i
                                   phase->max_sites, P.max_plane_words, W.planes_off.as<uint64_t>(), W.sites.p,
                                   W.n_sites.as<uint32_t>(), W.n_qualified.as<uint32_t>(), W.planes.as<uint64_t>(),
                                   W.link.as<uint32_t>());
+    if (e == 0 && resample)
+        e = smx_launch_cons_resample(nullptr, W.reads.as<unsigned char>(), W.doff.as<uint64_t>(), W.len.as<int32_t>(), W.jobs.p,
+                                     n_jobs, resample->n_levels, P.max_words, W.rows.as<uint32_t>(), W.dist.as<int32_t>(),
+                                     W.masks.as<uint64_t>(), W.member_off.as<uint64_t>(), W.agree_off.as<uint64_t>(),
+                                     P.member_off.back(), W.agree.as<uint64_t>(), W.sub_aligned.as<uint32_t>());
     if (e != 0) return fail(SMX_ERR_DEVICE, "consensus kernel launch failed: %s", hipGetErrorString((hipError_t)e));
     if (kernel_ms) HIP_TRY(timer.stop(kernel_ms));
     HIP_TRY(hipDeviceSynchronize());
@@ -618,6 +641,10 @@ int cons_call(const char *reads, const uint64_t *roff, uint32_t n_reads, const i
         HIP_TRY(hipMemcpy(phase->n_qualified, W.n_qualified.p, (size_t)n_jobs * 4, hipMemcpyDeviceToHost));
         if (P.planes_off.back()) HIP_TRY(hipMemcpy(phase->planes, W.planes.p, (size_t)P.planes_off.back() * 8, hipMemcpyDeviceToHost));
         HIP_TRY(hipMemcpy(phase->link, W.link.p, (size_t)P.link_words * 4, hipMemcpyDeviceToHost));
+    }
+    if (resample) {
+        HIP_TRY(hipMemcpy(resample->agree, W.agree.p, (size_t)P.agree_off.back() * 8, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(resample->sub_aligned, W.sub_aligned.p, (size_t)P.sub_words * 4, hipMemcpyDeviceToHost));
     }
     return SMX_OK;
 }
@@ -642,6 +669,14 @@ int smx_cons_phase(const char *reads, const uint64_t *roff, uint32_t n_reads, co
     if (n_jobs && (!votes || !aligned)) return fail(SMX_ERR_ARG, "null argument");
     const ConsPhase phase{min_permille, min_reads, max_sites, sites, n_sites, n_qualified, planes, link};
     return cons_call(reads, roff, n_reads, k, jobs, n_jobs, nullptr, nullptr, votes, aligned, kernel_ms, &phase);
+}
+
+int smx_cons_resample(const char *reads, const uint64_t *roff, uint32_t n_reads, const int32_t *k, const smx_cons_job *jobs,
+                      uint32_t n_jobs, const uint64_t *masks, uint32_t n_levels, uint32_t *votes, uint32_t *aligned,
+                      uint64_t *agree, uint32_t *sub_aligned, float *kernel_ms) {
+    if (n_jobs && (!votes || !aligned)) return fail(SMX_ERR_ARG, "null argument");
+    const ConsResample resample{masks, n_levels, agree, sub_aligned};
+    return cons_call(reads, roff, n_reads, k, jobs, n_jobs, nullptr, nullptr, votes, aligned, kernel_ms, nullptr, &resample);
 }
 
 // ---- inner scan: every pattern against the whole read, hits on the internal columns (smx_inner.hip)

@@ -1,6 +1,7 @@
 // smx_cons_plan.h -- the host-side plan of one smx_cons_* call (smx_calls.cpp): argument checks, the jobs with their
 // offsets, the alignment's job list by register class with its chunk prefix, and the size of the history workspace.
-// Host only and free of HIP calls, so that the sanitizer driver (tests/asan/cons_driver.cpp) runs it as it is.
+// Host only and free of HIP calls, so that the sanitizer drivers (tests/asan/cons_driver.cpp, phase_driver.cpp,
+// resample_driver.cpp) and the CPU simulations run it as it is.
 #ifndef SMX_CONS_PLAN_H
 #define SMX_CONS_PLAN_H
 #include <algorithm>
@@ -33,6 +34,11 @@ struct ConsPlan {
     std::vector<uint64_t> planes_off;      // n_jobs + 1 entries
     uint64_t site_slots = 0, link_words = 0;
     uint32_t max_plane_words = 0;          // the largest job's ceil(n / 64)
+    // the tables of an smx_cons_resample call (cons_plan_resample): job j's members own the mask words [member_off[j],
+    // member_off[j + 1]) of every level, level l starting at l * member_off[n_jobs]; its agree words are [agree_off[j],
+    // agree_off[j + 1]), level after level m + 1 each; sub_aligned holds SMX_CONS_REPLICATES counts per (job, level)
+    std::vector<uint64_t> member_off, agree_off;   // n_jobs + 1 entries each
+    uint64_t mask_words = 0, sub_words = 0;
 };
 
 // Returns SMX_OK, or the status to fail with and why.  hist_budget: CONS_HIST_BYTES, or a test's smaller figure.
@@ -140,6 +146,35 @@ inline int cons_plan_phase(uint32_t min_permille, uint32_t max_sites, ConsPlan *
     }
     P.site_slots = (uint64_t)P.jobs.size() * max_sites;
     P.link_words = P.site_slots * max_sites * 4;
+    return SMX_OK;
+}
+
+// The tables of a planned call with resampling (smx_cons_resample): the argument checks and the offsets of the members'
+// mask words and of the agree words.  have_masks: the caller's mask pointer is not null.
+inline int cons_plan_resample(bool have_masks, uint32_t n_levels, ConsPlan *plan, std::string *why) {
+    ConsPlan &P = *plan;
+    if (n_levels == 0 || n_levels > SMX_CONS_MAX_LEVELS) {
+        *why = "n_levels " + std::to_string(n_levels) + " is not in 1.." + std::to_string(SMX_CONS_MAX_LEVELS);
+        return SMX_ERR_ARG;
+    }
+    if (!have_masks && P.n_dist != 0) {
+        *why = "masks is null and the jobs have " + std::to_string(P.n_dist) + " members";
+        return SMX_ERR_ARG;
+    }
+    // the launch: a workgroup row per (job, level), four columns per workgroup
+    if ((uint64_t)P.jobs.size() * n_levels > (uint64_t)INT32_MAX || P.max_words > 4u * 65535u) {
+        *why = "resampling: " + std::to_string(P.jobs.size()) + " jobs x " + std::to_string(n_levels) + " levels or a draft of " +
+               std::to_string(P.max_words) + " words is more than one launch holds: split the call";
+        return SMX_ERR_UNSUPPORTED;
+    }
+    P.member_off.assign(1, 0);
+    P.agree_off.assign(1, 0);
+    for (const ConsJobDev &J : P.jobs) {
+        P.member_off.push_back(P.member_off.back() + J.n);
+        P.agree_off.push_back(P.agree_off.back() + (uint64_t)n_levels * ((uint64_t)P.len[J.draft] + 1));
+    }
+    P.mask_words = (uint64_t)n_levels * P.member_off.back();
+    P.sub_words = (uint64_t)P.jobs.size() * n_levels * SMX_CONS_REPLICATES;
     return SMX_OK;
 }
 

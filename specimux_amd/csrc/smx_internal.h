@@ -188,6 +188,14 @@ int smx_launch_cons_phase(void *stream, const int32_t *d_len, const void *d_jobs
                           const int32_t *d_dist, const uint32_t *d_votes, const uint32_t *d_aligned, uint32_t min_permille,
                           uint32_t min_reads, uint32_t max_sites, uint32_t max_plane_words, const uint64_t *d_planes_off,
                           void *d_sites, uint32_t *d_n_sites, uint32_t *d_n_qualified, uint64_t *d_planes, uint32_t *d_link);
+// support (smx_resample.hip), after smx_launch_cons_align and smx_launch_cons_vote on the same stream: per (job, level,
+// column) the 64 replicates that keep the column, from d_rows, d_dist and the n_levels x level_stride mask words (job j's
+// members at member_off[j] of every level), into d_agree (job j's n_levels x (m + 1) words at agree_off[j]) and the
+// replicates' voters into d_sub_aligned ([job][level][64]).  max_words = the largest m + 1.  Every word is written
+int smx_launch_cons_resample(void *stream, const unsigned char *d_bytes, const uint64_t *d_off, const int32_t *d_len,
+                             const void *d_jobs, uint32_t n_jobs, uint32_t n_levels, uint32_t max_words, const uint32_t *d_rows,
+                             const int32_t *d_dist, const uint64_t *d_masks, const uint64_t *d_member_off,
+                             const uint64_t *d_agree_off, uint64_t level_stride, uint64_t *d_agree, uint32_t *d_sub_aligned);
 // crosstalk (smx_nearest.hip); wr, grid, per_block, d_scratch, d_bytes / d_off / d_len / d_k as for smx_launch_pairs;
 // d_group: the group per sequence.  runs[0..n_runs) (NearestRun over the class's ref list d_refs) with
 // chunk_start[0..n_runs] (nonzero each).  dist = 1: d_dist holds int32 distances, job j's nq x nt at its dist_off;
