@@ -313,6 +313,10 @@ int smx_lane_wait(smx_lane *lane, const smx_op **ops, const smx_op **extra, uint
  * One edlib-equivalent alignment on the device (Myers bit-vector kernel), for unit parity with the oracle.
  * mode 0 = HW (infix), 1 = SHW (prefix); IUPAC equalities always on; qlen <= 64.
  * *dist = -1 if the best distance exceeds k.  Up to cap (start,end) pairs are written, *nloc = true count.
+ * Any k >= 0 (k >= qlen: every alignment is "within k") and any tlen >= 1; k < 0 gives *dist = -1.  In SHW mode no
+ * optimal end lies beyond column qlen + min(k, qlen), and the device scans no further.
+ * SMX_ERR_UNSUPPORTED for qlen outside 1..64, a query letter outside the IUPAC DNA alphabet, a mode other than 0 / 1 and
+ * tlen < 1: refused by host code, before the device is asked.
  */
 int smx_align(const char *query, int qlen, const char *target, int tlen, int k, int mode,
               int *dist, int *starts, int *ends, int cap, int *nloc);
@@ -321,9 +325,13 @@ int smx_align(const char *query, int qlen, const char *target, int tlen, int k, 
  * N alignments in one launch (trace level 3 and --color ask for thousands per batch; device workspace is cached).
  *   queries / qoff      n_queries distinct query strings (concatenated, n_queries + 1 offsets), each 1..64 letters
  *   targets / toff      n targets (concatenated, n + 1 offsets), each >= 1 letter
- *   qidx, k, mode       per alignment: query index, max distance, 0 = HW / 1 = SHW
+ *   qidx, k, mode       per alignment: query index, max distance 0..250 (k >= the query's length: every alignment is
+ *                       "within k"), 0 = HW / 1 = SHW
  *   dist, nloc          per alignment: best distance (-1: above k) and number of optimal locations
- *   starts, ends        n x cap; the first min(nloc, cap) locations of alignment i at [i * cap ..)
+ *   starts, ends        n x cap; the first min(nloc, cap) locations of alignment i at [i * cap ..); may be NULL if cap == 0
+ * n == 0 is SMX_OK.  Otherwise, from host code before the device is asked: SMX_ERR_UNSUPPORTED for a query length outside
+ * 1..64, a query letter outside the IUPAC DNA alphabet and an empty target; SMX_ERR_ARG for qidx >= n_queries, a mode above
+ * 1 and k outside 0..250.
  */
 int smx_align_batch(const char *queries, const uint32_t *qoff, uint32_t n_queries, const char *targets,
                     const uint64_t *toff, const uint32_t *qidx, const int32_t *k, const uint8_t *mode, uint32_t n,

@@ -119,9 +119,12 @@ def align_seq(query, target, max_distance: int, start: int, end: int, mode: str 
     if len(query) < 1 or len(query) > 64:
         raise ValueError("query length must be 1..64 for the device aligner")
     if not t:
-        # edlib on an empty target reports editDistance = len(query); align_seq then clamps it
-        d = len(query) if len(query) <= max_distance else -1
-        return AlignmentResult(d, [(None, -1)] if d != -1 else [])
+        # edlib on an empty target reports editDistance = len(query) and the one location (None, -1), whatever k is
+        # (SURVEY A.4); the reference clamps the distance and keeps the location (alignment.py:44-49).  Its shift is a
+        # no-op after the clamp and a TypeError (None + s) where len(query) <= max_distance: the same here
+        m = AlignmentResult(len(query) if len(query) <= max_distance else -1, [(None, -1)])
+        m.adjust_start(s)
+        return m
     if mode == AlignMode.PREFIX:
         t = t[:len(query) + int(max_distance)]   # exact: a prefix alignment within k ends inside the first len + k bases
     if _active_cache is not None:

@@ -1,6 +1,7 @@
 // smx_calls.cpp -- the one-shot calls of libsmx.so over host buffers: alignments (smx_align, smx_align_batch), specimine
 // (smx_mine.hip), clusters (smx_pairs.hip), consensus (smx_cons.hip), crosstalk (smx_nearest.hip), identify (smx_hits.hip), bimera (smx_reach.hip) and the inner scan (smx_inner.hip).  Each keeps one grow-only device workspace; its calls are serialised.
 #include "smx_host.h"
+#include "smx_align_lane.h"   // align_collect
 #include "smx_cons_plan.h"
 #include "smx_nearest_plan.h"
 #include "smx_hits_plan.h"
@@ -15,11 +16,11 @@ int smx_align(const char *query, int qlen, const char *target, int tlen, int k, 
     if (qlen < 1 || qlen > 64) return fail(SMX_ERR_UNSUPPORTED, "query length %d outside 1..64", qlen);
     if (mode != 0 && mode != 1) return fail(SMX_ERR_UNSUPPORTED, "mode %d (0 = HW, 1 = SHW)", mode);
     if (tlen < 1) return fail(SMX_ERR_UNSUPPORTED, "empty target");
-    SMX_TRY(require_device());
     unsigned long long peq[32];
     std::string bad, q(query, qlen), rq(q.rbegin(), q.rend());
     if (!build_peq(q.data(), qlen, peq, &bad) || !build_peq(rq.data(), qlen, peq + 16, &bad))
         return fail(SMX_ERR_UNSUPPORTED, "%s", bad.c_str());
+    SMX_TRY(require_device());   // every argument check is above: a bad call is refused without a device
     std::vector<unsigned char> codes(tlen);
     for (int i = 0; i < tlen; i++) codes[i] = (unsigned char)code_of((unsigned char)target[i]);
     DevMem<unsigned char> d;
@@ -38,14 +39,7 @@ int smx_align(const char *query, int qlen, const char *target, int tlen, int k, 
     if (e == hipSuccess) e = hipMemcpy(flag.data(), d + o_flag, tlen, hipMemcpyDeviceToHost);
     if (e == hipSuccess) e = hipMemcpy(st.data(), d + o_starts, (size_t)tlen * 4, hipMemcpyDeviceToHost);
     if (e != hipSuccess) return fail(SMX_ERR_DEVICE, "smx_align: %s", hipGetErrorString(e));
-    int cnt = 0;
-    if (*dist >= 0)
-        for (int j = 0; j < tlen; j++)
-            if (flag[j]) {
-                if (cnt < cap && starts && ends) { starts[cnt] = st[j]; ends[cnt] = j; }
-                cnt++;
-            }
-    *nloc = cnt;
+    *nloc = smx::align_collect(*dist, flag.data(), st.data(), tlen, starts, ends, cap);
     return SMX_OK;
 }
 
@@ -62,7 +56,6 @@ int smx_align_batch(const char *queries, const uint32_t *qoff, uint32_t n_querie
     if (!queries || !qoff || !targets || !toff || !qidx || !k || !mode || !dist || !nloc || (cap && (!starts || !ends)))
         return fail(SMX_ERR_ARG, "null argument");
     if (n == 0) return SMX_OK;
-    SMX_TRY(require_device());
     std::vector<unsigned long long> qpeq((size_t)n_queries * 32);
     std::vector<int> qlen(n_queries);
     std::string bad;
@@ -74,13 +67,14 @@ int smx_align_batch(const char *queries, const uint32_t *qoff, uint32_t n_querie
             return fail(SMX_ERR_UNSUPPORTED, "query %u: %s", q, bad.c_str());
         qlen[q] = m;
     }
-    const uint64_t tbytes = toff[n];
-    std::vector<unsigned char> codes(tbytes);
     for (uint32_t i = 0; i < n; i++) {
         if (toff[i + 1] <= toff[i]) return fail(SMX_ERR_UNSUPPORTED, "alignment %u: empty target", i);
         if (qidx[i] >= n_queries || mode[i] > 1) return fail(SMX_ERR_ARG, "alignment %u: bad query index or mode", i);
         if (k[i] < 0 || k[i] > 250) return fail(SMX_ERR_ARG, "alignment %u: bad max distance", i);
     }
+    SMX_TRY(require_device());   // every argument check is above: a bad call is refused without a device
+    const uint64_t tbytes = toff[n];
+    std::vector<unsigned char> codes(tbytes);
     for (uint64_t j = 0; j < tbytes; j++) codes[j] = (unsigned char)code_of((unsigned char)targets[j]);
     std::lock_guard<std::mutex> guard(g_align.mutex);
     auto &W = g_align;

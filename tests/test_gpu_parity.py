@@ -969,6 +969,59 @@ def test_packed_windows_unpack_on_device(lib, c2, search_len):
     assert np.array_equal(got, np.where(inside, windows, 0)) and np.array_equal(pl, wl)
 
 
+def _unpack_on_device(lib, c2, search_len, n, fill):
+    """n reads of 1 .. 3 S + 5 letters through smx_pack_windows4 and smx_unpack_windows_device into a buffer that held `fill`;
+    returns (the whole buffer, padding bytes included; what smx_pack_windows gives with letters outside the alphabet as 0)."""
+    import torch
+    from specimux_amd import _lib
+    from specimux_amd.demultiplex import compiled_panel
+    pan, (pf, sf) = c2
+    both = Both(pf, sf, search_len=search_len)
+    cp = compiled_panel(both.specimens, both.parameters, both.args, both.prefilter)
+    rng = np.random.default_rng(1000 * search_len + fill)
+    alphabet = np.frombuffer(b"ACGTACGTACGTACGTNRYKMSWBDHVacgtn?X", dtype=np.uint8)
+    lens = rng.integers(1, 3 * search_len + 6, n)
+    lens[:min(n, 3 * search_len + 5)] = np.arange(1, 3 * search_len + 6)[:n]          # every length once
+    bases = alphabet[rng.integers(0, len(alphabet), int(lens.sum()))]
+    off = np.zeros(n + 1, dtype=np.uint64)
+    off[1:] = np.cumsum(lens)
+    windows, wl = cp.pack_windows(bases, off)
+    ps = int(lib.smx_packed_stride(cp.handle))
+    packed, pl = np.zeros((n, ps), dtype=np.uint8), np.zeros(n, dtype=np.int32)
+    _lib.check(lib.smx_pack_windows4(_lib.ptr(bases), _lib.ptr(off), n, search_len, _lib.ptr(packed), _lib.ptr(pl), None))
+    assert np.array_equal(pl, wl) and windows.shape == (n, cp.window_stride)
+    d_packed = torch.from_numpy(packed).cuda()
+    d_windows = torch.full((n, cp.window_stride), fill, dtype=torch.uint8, device="cuda")
+    _lib.check(lib.smx_unpack_windows_device(cp.handle, None, C.c_void_p(d_packed.data_ptr()), n, C.c_void_p(d_windows.data_ptr())))
+    torch.cuda.synchronize()
+    inside = np.isin(windows, np.frombuffer(b"ACGTNRYKMSWBDHV", dtype=np.uint8))
+    return d_windows.cpu().numpy(), np.where(inside, windows, 0), cp.window_stride
+
+
+@pytest.mark.parametrize("search_len", [1, 7, 8, 9, 15, 16, 17])
+def test_packed_windows_unpack_at_the_fast_path_switch(lib, c2, search_len):
+    """The smallest search_len smx_panel_create admits, the smallest fast-path unit count (8 = one unit per end) and the
+    values either side of the switch between the 8-base kernel (search_len a multiple of 8) and the byte-wise one."""
+    got, want, _ = _unpack_on_device(lib, c2, search_len, 300, 0x55)
+    assert np.array_equal(got, want)
+
+
+@pytest.mark.parametrize("search_len,fill", [(80, 0x55), (81, 0xC3)])
+def test_packed_windows_unpack_past_the_grid(lib, c2, search_len, fill):
+    """Both unpack kernels are grid-stride loops over at most n_cu * 16 workgroups of 256 lanes: with half again as many
+    units as that (search_len / 4 per read for the 8-base kernel, the window stride for the byte-wise one) lanes take a
+    second trip, as they do on production batches of 131 072 reads.  The whole buffer, padding bytes included."""
+    import torch
+    lanes = torch.cuda.get_device_properties(0).multi_processor_count * 16 * 256
+    stride = (2 * search_len + 15) // 16 * 16
+    per_read = search_len // 4 if search_len % 8 == 0 else stride
+    n = (3 * lanes + 2 * per_read - 1) // (2 * per_read) + 1
+    got, want, wstride = _unpack_on_device(lib, c2, search_len, n, fill)
+    assert wstride == stride and n * per_read >= 1.5 * lanes
+    assert np.array_equal(got, want)
+    assert wstride == 2 * search_len or not got[:, 2 * search_len:].any()      # the padding is written, not left as it was
+
+
 def test_pipeline_packed_lanes_equal_ascii_lanes(lib, c2, tmp_path, monkeypatch):
     """The streaming pipeline ships 4-bit windows by default; SMX_LANES_ASCII=1 ships 8-bit ones.  Same tree, same counts --
     also for reads with N, lower-case bases and other characters in the windows, and for a batch with a 'U' (which falls
