@@ -10,6 +10,7 @@ import ctypes as C
 from typing import List, Optional, Tuple
 
 from . import _lib
+from .calls import offsets
 from .constants import AlignMode
 
 _MODE = {AlignMode.INFIX: 0, AlignMode.PREFIX: 1}
@@ -63,11 +64,9 @@ def align_batch(requests):
             raise ValueError("query length must be 1..64 for the device aligner")
         qidx[i] = qtab.setdefault(q, len(qtab))
     queries = list(qtab)
-    qoff = np.zeros(len(queries) + 1, dtype=np.uint32)
-    qoff[1:] = np.cumsum([len(q) for q in queries])
+    qoff = offsets(queries, np.uint32)
     qblob = "".join(queries).encode("ascii")
-    toff = np.zeros(len(requests) + 1, dtype=np.uint64)
-    toff[1:] = np.cumsum([len(t) for _q, t, _k, _m in requests], dtype=np.uint64)
+    toff = offsets([t for _q, t, _k, _m in requests])
     tblob = "".join(t for _q, t, _k, _m in requests).encode("latin-1", "replace")
     k = np.array([int(r[2]) for r in requests], dtype=np.int32)
     mode = np.array([_MODE[r[3]] for r in requests], dtype=np.uint8)

@@ -36,18 +36,17 @@ import json
 import logging
 import os
 import re
-import sys
 from typing import Callable, Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
-from . import clusters, crosstalk, identify
+from . import calls, clusters, crosstalk, identify, specimine
 
 NONE = 2**64 - 1                           # smx.h: an empty slot
 NOT_ELIGIBLE = 2**32 - 1                   # smx.h: the matrix call's value for a target that does not count
 MAX_E = 15                                 # SMX_REACH_MAX_E
-SLOTS = 2                                  # keys per (query, side, e)
-ALWAYS = 2**32 - 1                         # the weight of a --parents record
+SLOTS = calls.REACH_SLOTS                  # keys per (query, side, e)
+ALWAYS = calls.ALWAYS                      # the weight of a --parents record
 Job = Tuple[int, int, int, int]            # (q0, nq, t0, nt): indices into the call's sequence list
 COLUMNS = ("name", "specimen", "size", "status", "d1", "d2", "parent_left", "parent_right", "edits_left", "edits_right",
            "break_lo", "break_hi", "length")
@@ -117,54 +116,8 @@ def called_from_fasta(path: str) -> List[Called]:
 
 
 # ------------------------------------------------------------------------------------------------ the device call
-def _arrays(seqs: Sequence[bytes], weights: Sequence[int], needs: Sequence[int], jobs: Sequence[Job]):
-    from . import _lib
-    off = np.zeros(len(seqs) + 1, dtype=np.uint64)
-    off[1:] = np.cumsum([len(s) for s in seqs], dtype=np.uint64)
-    warr = np.array([min(int(w), ALWAYS) for w in weights], dtype=np.uint32)
-    narr = np.array([min(int(n), ALWAYS) for n in needs], dtype=np.uint32)
-    jarr = np.array(list(jobs), dtype=_lib.REACH_JOB_DTYPE) if jobs else np.zeros(0, dtype=_lib.REACH_JOB_DTYPE)
-    return off, warr, narr, jarr
-
-
-def reach(seqs: Sequence[bytes], weights: Sequence[int], needs: Sequence[int], jobs: Sequence[Job], E: int,
-          kernel_ms: Optional[list] = None) -> np.ndarray:
-    """One smx_prefix_reach call: job after job, per query, per side (0 left, 1 right), per e in 0..E, two keys in
-    ascending order, padded with 2^64 - 1 (include/smx.h: 0xFFFFFFFF - reach in bits 63-32, the target's index in
-    `seqs` below)."""
-    from . import _lib
-    lib = _lib.load()
-    off, warr, narr, jarr = _arrays(seqs, weights, needs, jobs)
-    n = sum(j[1] for j in jobs) * 2 * (max(E, 0) + 1) * SLOTS
-    keys = np.full(max(n, 1), 0x5A5A5A5A5A5A5A5A, dtype=np.uint64)     # a sentinel: the library writes every entry
-    ms = _lib.C.c_float(0.0)
-    _lib.check(lib.smx_prefix_reach(b"".join(seqs), _lib.ptr(off), len(seqs), _lib.ptr(warr), _lib.ptr(narr), _lib.ptr(jarr),
-                                    len(jobs), E, _lib.ptr(keys), _lib.C.byref(ms)))
-    if kernel_ms is not None:
-        kernel_ms.append(ms.value)
-    return keys[:n]
-
-
-def reach_matrix(seqs: Sequence[bytes], weights: Sequence[int], needs: Sequence[int], jobs: Sequence[Job], E: int,
-                 kernel_ms: Optional[list] = None) -> List[np.ndarray]:
-    """One smx_prefix_reach_matrix call: per job an array [nq, nt, 2, E + 1] (2^32 - 1: the target is not eligible).
-    For tests and inspection."""
-    from . import _lib
-    lib = _lib.load()
-    off, warr, narr, jarr = _arrays(seqs, weights, needs, jobs)
-    per = 2 * (max(E, 0) + 1)
-    n = sum(j[1] * j[3] for j in jobs) * per
-    vals = np.full(max(n, 1), 0x5A5A5A5A, dtype=np.uint32)
-    ms = _lib.C.c_float(0.0)
-    _lib.check(lib.smx_prefix_reach_matrix(b"".join(seqs), _lib.ptr(off), len(seqs), _lib.ptr(warr), _lib.ptr(narr),
-                                           _lib.ptr(jarr), len(jobs), E, _lib.ptr(vals), _lib.C.byref(ms)))
-    if kernel_ms is not None:
-        kernel_ms.append(ms.value)
-    out, at = [], 0
-    for _, nq, _, nt in jobs:
-        out.append(vals[at:at + nq * nt * per].reshape(nq, nt, 2, per // 2))
-        at += nq * nt * per
-    return out
+reach = calls.prefix_reach
+reach_matrix = calls.prefix_reach_matrix
 
 
 def pack_key(reach_: int, target: int) -> int:
@@ -359,24 +312,13 @@ def run(args, reach_fn: Callable = reach, kernel_ms: Optional[list] = None) -> i
                                reach_fn=reach_fn, kernel_ms=kernel_ms)
     logging.info(summary_line(summary))
     rows = rows_of(called, parents, verdicts, args.max_edits + args.min_gain)
-    for dest, text in ((args.report, tsv_text(rows)), (args.json, json_text(rows, summary)), (args.clean, clean_text(called, verdicts))):
-        if dest:
-            with open(dest, "w", encoding="latin-1") as fh:
-                fh.write(text)
+    specimine.write_texts(((args.report, lambda: tsv_text(rows)), (args.json, lambda: json_text(rows, summary)),
+                           (args.clean, lambda: clean_text(called, verdicts))))
     return 0
 
 
 def main(argv=None):
-    args = build_parser().parse_args(argv)
-    logging.basicConfig(level=logging.DEBUG if args.debug else logging.INFO,
-                        format="%(asctime)s - %(levelname)s - %(message)s")
-    try:
-        status = run(args)
-    except ValueError as e:
-        logging.error(str(e))
-        status = 2
-    if status:
-        sys.exit(status)
+    specimine.tool_main(build_parser, run, argv, value_error_status=2)
 
 
 if __name__ == "__main__":

@@ -17,7 +17,6 @@ reverse-complemented one, so a junction is a `-` hit followed closely by a `+` h
 The file streams through the native reader in batches; nothing here grows with the file.  The clean / flagged files
 are written by libsmx from the batch, whole header lines included."""
 import argparse
-import ctypes as C
 import logging
 import sys
 import timeit
@@ -25,7 +24,7 @@ from typing import NamedTuple
 
 import numpy as np
 
-from . import _lib
+from . import calls
 
 BATCH_READS = 65536         # reads per scan call on the file path
 BATCH_BYTES = 64 << 20      # and at most about this many bases
@@ -51,53 +50,18 @@ def panel_patterns(specimens, parameters, inner_k):
     return out
 
 
-def _pattern_args(patterns, k):
-    seqs = [p.seq if isinstance(p, PatternInfo) else p for p in patterns]
-    enc = [s.encode("ascii") for s in seqs]
-    poff = np.zeros(len(enc) + 1, dtype=np.uint32)
-    if enc:
-        poff[1:] = np.cumsum([len(e) for e in enc])
-    return b"".join(enc), poff, np.ascontiguousarray(k, dtype=np.int32)
-
-
-def _outputs(n, q, h):
-    return (np.empty((n, q), dtype=np.uint8), np.empty((n, q, h), dtype=np.int8), np.empty((n, q, h), dtype=np.int32))
+def _seqs(patterns):
+    return [p.seq if isinstance(p, PatternInfo) else p for p in patterns]
 
 
 def scan(bases, offsets, patterns, k, margin, max_hits=4, budget_bytes=0, kernel_ms=None):
-    """smx_inner_scan over reads given as one uint8 array and n + 1 offsets.  Returns (nhit [n, Q] uint8, hit_dist [n, Q, H]
-    int8, hit_end [n, Q, H] int32): per read and pattern the number of hits on the internal columns
-    margin <= c < len - margin (saturating at 255) and the first max_hits of them in column order (-1 / 0 where unused).
-    `kernel_ms` (a list) receives the device time of the call."""
-    lib = _lib.load()
-    bases = np.ascontiguousarray(bases, dtype=np.uint8)
-    offsets = np.ascontiguousarray(offsets, dtype=np.uint64)
-    n = len(offsets) - 1
-    blob, poff, kk = _pattern_args(patterns, k)
-    nhit, dist, end = _outputs(n, len(patterns), int(max_hits))
-    ms = C.c_float()
-    _lib.check(lib.smx_inner_scan(blob, _lib.ptr(poff), len(patterns), _lib.ptr(kk), _lib.ptr(bases), _lib.ptr(offsets), n,
-                                  int(margin), int(max_hits), int(budget_bytes), _lib.ptr(nhit), _lib.ptr(dist),
-                                  _lib.ptr(end), C.byref(ms)))
-    if kernel_ms is not None:
-        kernel_ms.append(ms.value)
-    return nhit, dist, end
+    """calls.inner_scan; a pattern may be a PatternInfo or its sequence."""
+    return calls.inner_scan(bases, offsets, _seqs(patterns), k, margin, max_hits, budget_bytes, kernel_ms)
 
 
 def scan_batch(batch, patterns, k, margin, max_hits=4, budget_bytes=0, kernel_ms=None):
-    """The same over a native reader batch (native_io.Batch): libsmx gathers each chunk's sequences from the batch into one
-    host staging buffer (one copy per record) and uploads that; no per-record Python work."""
-    lib = _lib.load()
-    n = len(batch)
-    blob, poff, kk = _pattern_args(patterns, k)
-    nhit, dist, end = _outputs(n, len(patterns), int(max_hits))
-    ms = C.c_float()
-    _lib.check(lib.smx_inner_scan_batch(batch.handle, blob, _lib.ptr(poff), len(patterns), _lib.ptr(kk), int(margin),
-                                        int(max_hits), int(budget_bytes), _lib.ptr(nhit), _lib.ptr(dist), _lib.ptr(end),
-                                        C.byref(ms)))
-    if kernel_ms is not None:
-        kernel_ms.append(ms.value)
-    return nhit, dist, end
+    """calls.inner_scan_batch; a pattern may be a PatternInfo or its sequence."""
+    return calls.inner_scan_batch(batch, _seqs(patterns), k, margin, max_hits, budget_bytes, kernel_ms)
 
 
 def flag_reads(nhit, hit_dist, hit_end, pattern_info, rule="junction", gap=100):

@@ -22,12 +22,11 @@ import argparse
 import json
 import logging
 import os
-import sys
 from typing import Callable, Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
-from . import specimine
+from . import calls, specimine
 
 Specimen = Tuple[List[bytes], List[int]]   # one specimen's sampled reads and their limits k
 
@@ -126,32 +125,13 @@ def pair_count(specimens: Sequence[Specimen]) -> int:
 def adjacency(specimens: Sequence[Specimen], kernel_ms: Optional[list] = None) -> List[np.ndarray]:
     """One smx_pairs_neighbours call: per specimen the symmetric boolean n x n matrix "NW distance of reads i and j
     <= max(k[i], k[j])", with a false diagonal."""
-    from . import _lib
-    lib = _lib.load()
-    reads = [r for rs, _ in specimens for r in rs]
-    roff = np.zeros(len(reads) + 1, dtype=np.uint64)
-    roff[1:] = np.cumsum([len(r) for r in reads], dtype=np.uint64)
-    karr = np.array([min(k, 2**31 - 1) if k >= 0 else -1 for _, ks in specimens for k in ks], dtype=np.int32)
-    jobs = np.zeros(len(specimens), dtype=_lib.PAIRS_JOB_DTYPE)
-    at = 0
-    for j, (rs, _) in enumerate(specimens):
-        jobs[j] = (at, len(rs))
+    jobs, at = [], 0
+    for rs, _ in specimens:
+        jobs.append((at, len(rs)))
         at += len(rs)
-    words = [len(rs) * ((len(rs) + 31) // 32) for rs, _ in specimens]
-    adj = np.zeros(max(sum(words), 1), dtype=np.uint32)
-    ms = _lib.C.c_float(0.0)
-    _lib.check(lib.smx_pairs_neighbours(b"".join(reads), _lib.ptr(roff), len(reads), _lib.ptr(karr), _lib.ptr(jobs),
-                                        len(specimens), _lib.ptr(adj), _lib.C.byref(ms)))
-    if kernel_ms is not None:
-        kernel_ms.append(ms.value)
-    out, at = [], 0
-    for (rs, _), nwords in zip(specimens, words):
-        n = len(rs)
-        rows = adj[at:at + nwords].reshape(n, -1) if n else adj[:0].reshape(0, 0)
-        at += nwords
-        bits = np.unpackbits(rows.view(np.uint8), axis=1, bitorder="little") if n else np.zeros((0, 0), np.uint8)
-        out.append(bits[:, :n].astype(bool))
-    return out
+    words = calls.pairs_neighbours([r for rs, _ in specimens for r in rs], [k for _, ks in specimens for k in ks], jobs, kernel_ms)
+    return [np.unpackbits(rows.view(np.uint8), axis=1, bitorder="little")[:, :len(rows)].astype(bool) if len(rows)
+            else np.zeros((0, 0), dtype=bool) for rows in words]
 
 
 def adjacency_oracle(specimens: Sequence[Specimen], kernel_ms: Optional[list] = None) -> List[np.ndarray]:
@@ -351,12 +331,7 @@ def run(args, adjacency_fn: Callable = adjacency, kernel_ms: Optional[list] = No
 
 
 def main(argv=None):
-    args = build_parser().parse_args(argv)
-    logging.basicConfig(level=logging.DEBUG if args.debug else logging.INFO,
-                        format="%(asctime)s - %(levelname)s - %(message)s")
-    status = run(args)
-    if status:
-        sys.exit(status)
+    specimine.tool_main(build_parser, run, argv)
 
 
 if __name__ == "__main__":

@@ -23,12 +23,11 @@ import argparse
 import json
 import logging
 import os
-import sys
 from typing import Callable, Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
-from . import clusters, specimine
+from . import calls, clusters, specimine
 
 MAX_INS, VOTE_WORDS = 4, 26                # smx.h: SMX_CONS_MAX_INS, SMX_CONS_VOTE_WORDS
 BASES = "ACGT"
@@ -61,29 +60,7 @@ def build_parser() -> argparse.ArgumentParser:
 
 
 # ------------------------------------------------------------------------------------------------ votes
-def votes(reads: Sequence[bytes], ks: Sequence[int], jobs: Sequence[Job],
-          kernel_ms: Optional[list] = None) -> Tuple[List[np.ndarray], List[int]]:
-    """One smx_cons_votes call: per job the (len(draft) + 1) x 26 vote table of its members [r0, r0 + n) aligned to its
-    draft, and the number of members that aligned within their limit."""
-    from . import _lib
-    lib = _lib.load()
-    roff = np.zeros(len(reads) + 1, dtype=np.uint64)
-    roff[1:] = np.cumsum([len(r) for r in reads], dtype=np.uint64)
-    karr = np.array([min(k, 2**31 - 1) if k >= 0 else -1 for k in ks], dtype=np.int32)
-    jarr = np.array(list(jobs), dtype=_lib.CONS_JOB_DTYPE) if jobs else np.zeros(0, dtype=_lib.CONS_JOB_DTYPE)
-    words = [(len(reads[d]) + 1) * VOTE_WORDS for d, _, _ in jobs]
-    table = np.zeros(max(sum(words), 1), dtype=np.uint32)
-    aligned = np.zeros(max(len(jobs), 1), dtype=np.uint32)
-    ms = _lib.C.c_float(0.0)
-    _lib.check(lib.smx_cons_votes(b"".join(reads), _lib.ptr(roff), len(reads), _lib.ptr(karr), _lib.ptr(jarr), len(jobs),
-                                  _lib.ptr(table), _lib.ptr(aligned), _lib.C.byref(ms)))
-    if kernel_ms is not None:
-        kernel_ms.append(ms.value)
-    out, at = [], 0
-    for w in words:
-        out.append(table[at:at + w].reshape(-1, VOTE_WORDS))
-        at += w
-    return out, [int(a) for a in aligned[:len(jobs)]]
+votes = calls.cons_votes
 
 
 # ------------------------------------------------------------------------------------------------ the call rule
@@ -291,21 +268,13 @@ def run(args, adjacency_fn: Callable = clusters.adjacency, votes_fn: Callable = 
                 logging.warning(f"{res.path}: cluster {pc.rank}: only {pc.aligned} of {pc.size} reads aligned to the draft of "
                                 f"round {pc.rounds}; the draft is kept as it was")
     logging.info(summary_line(summary))
-    for dest, text in ((args.fasta, fasta_text(results, polished)), (args.report, tsv_text(results, polished)),
-                       (args.json, json_text(results, polished, summary))):
-        if dest:
-            with open(dest, "w", encoding="latin-1") as fh:
-                fh.write(text)
+    specimine.write_texts(((args.fasta, lambda: fasta_text(results, polished)), (args.report, lambda: tsv_text(results, polished)),
+                           (args.json, lambda: json_text(results, polished, summary))))
     return 0
 
 
 def main(argv=None):
-    args = build_parser().parse_args(argv)
-    logging.basicConfig(level=logging.DEBUG if args.debug else logging.INFO,
-                        format="%(asctime)s - %(levelname)s - %(message)s")
-    status = run(args)
-    if status:
-        sys.exit(status)
+    specimine.tool_main(build_parser, run, argv)
 
 
 if __name__ == "__main__":

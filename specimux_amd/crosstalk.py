@@ -28,12 +28,11 @@ import json
 import logging
 import os
 import re
-import sys
 from typing import Callable, Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
-from . import clusters, consensus, specimine
+from . import calls, clusters, consensus, specimine
 
 NONE = 2**64 - 1                           # smx.h: a key without a ref
 Key = Optional[Tuple[int, int]]            # (distance, ref index) or None
@@ -144,52 +143,8 @@ def ref_groups(refs: Sequence[Ref], n_files: int) -> List[int]:
 
 
 # ------------------------------------------------------------------------------------------------ the device call
-def _arrays(seqs: Sequence[bytes], ks: Sequence[int], groups: Sequence[int], jobs: Sequence[Job]):
-    from . import _lib
-    off = np.zeros(len(seqs) + 1, dtype=np.uint64)
-    off[1:] = np.cumsum([len(s) for s in seqs], dtype=np.uint64)
-    karr = np.array([min(k, 2**31 - 1) if k >= 0 else -1 for k in ks], dtype=np.int32)
-    garr = np.array(groups, dtype=np.uint32)
-    jarr = np.array(list(jobs), dtype=_lib.NEAREST_JOB_DTYPE) if jobs else np.zeros(0, dtype=_lib.NEAREST_JOB_DTYPE)
-    return off, karr, garr, jarr
-
-
-def nearest(seqs: Sequence[bytes], ks: Sequence[int], groups: Sequence[int], jobs: Sequence[Job],
-            kernel_ms: Optional[list] = None) -> Tuple[np.ndarray, np.ndarray]:
-    """One smx_nearest call: job after job, per read the key ((d << 32) | ref, 2^64 - 1: none) of the nearest ref of the
-    read's own group and of the nearest ref of any other group."""
-    from . import _lib
-    lib = _lib.load()
-    off, karr, garr, jarr = _arrays(seqs, ks, groups, jobs)
-    n = sum(j[3] for j in jobs)
-    own = np.full(max(n, 1), 0x5A5A5A5A5A5A5A5A, dtype=np.uint64)      # never a key the library leaves: it writes every entry
-    other = np.full(max(n, 1), 0x5A5A5A5A5A5A5A5A, dtype=np.uint64)
-    ms = _lib.C.c_float(0.0)
-    _lib.check(lib.smx_nearest(b"".join(seqs), _lib.ptr(off), len(seqs), _lib.ptr(karr), _lib.ptr(garr), _lib.ptr(jarr),
-                               len(jobs), _lib.ptr(own), _lib.ptr(other), _lib.C.byref(ms)))
-    if kernel_ms is not None:
-        kernel_ms.append(ms.value)
-    return own[:n], other[:n]
-
-
-def nearest_distances(seqs: Sequence[bytes], ks: Sequence[int], groups: Sequence[int], jobs: Sequence[Job],
-                      kernel_ms: Optional[list] = None) -> List[np.ndarray]:
-    """One smx_nearest_distances call: per job its nq x nt distances (-1 above the limit).  For tests and inspection."""
-    from . import _lib
-    lib = _lib.load()
-    off, karr, garr, jarr = _arrays(seqs, ks, groups, jobs)
-    n = sum(j[1] * j[3] for j in jobs)
-    dist = np.full(max(n, 1), -7, dtype=np.int32)
-    ms = _lib.C.c_float(0.0)
-    _lib.check(lib.smx_nearest_distances(b"".join(seqs), _lib.ptr(off), len(seqs), _lib.ptr(karr), _lib.ptr(garr),
-                                         _lib.ptr(jarr), len(jobs), _lib.ptr(dist), _lib.C.byref(ms)))
-    if kernel_ms is not None:
-        kernel_ms.append(ms.value)
-    out, at = [], 0
-    for _, nq, _, nt in jobs:
-        out.append(dist[at:at + nq * nt].reshape(nq, nt))
-        at += nq * nt
-    return out
+nearest = calls.nearest
+nearest_distances = calls.nearest_distances
 
 
 def reduce_distances(dist: np.ndarray, q0: int, ref_groups_: Sequence[int], read_groups: Sequence[int]) -> Tuple[np.ndarray, np.ndarray]:
@@ -436,25 +391,13 @@ def run(args, nearest_fn: Callable = nearest, kernel_ms: Optional[list] = None) 
         for s in res.sources:
             logging.info(f"flagged: {res.path} <- {s['source']}: {s['reads']} read(s) nearest to {s['source_ref']}")
     logging.info(summary_line(summary))
-    for dest, text in ((args.report, tsv_text(results)), (args.json, json_text(results, summary)),
-                       (args.reads, reads_text(results, refs))):
-        if dest:
-            with open(dest, "w", encoding="latin-1") as fh:
-                fh.write(text)
+    specimine.write_texts(((args.report, lambda: tsv_text(results)), (args.json, lambda: json_text(results, summary)),
+                           (args.reads, lambda: reads_text(results, refs))))
     return 0
 
 
 def main(argv=None):
-    args = build_parser().parse_args(argv)
-    logging.basicConfig(level=logging.DEBUG if args.debug else logging.INFO,
-                        format="%(asctime)s - %(levelname)s - %(message)s")
-    try:
-        status = run(args)
-    except ValueError as e:
-        logging.error(str(e))
-        status = 2
-    if status:
-        sys.exit(status)
+    specimine.tool_main(build_parser, run, argv, value_error_status=2)
 
 
 if __name__ == "__main__":

@@ -23,12 +23,11 @@ import gzip
 import json
 import logging
 import os
-import sys
 from typing import Callable, Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
-from . import clusters, crosstalk, specimine
+from . import calls, clusters, crosstalk, specimine
 
 NONE = 2**64 - 1                           # smx.h: an empty slot
 MAX_K = 16                                 # SMX_HITS_MAX_K
@@ -108,51 +107,8 @@ def revcomp(seq: bytes) -> bytes:
 
 
 # ------------------------------------------------------------------------------------------------ the device call
-def _arrays(seqs: Sequence[bytes], ks: Sequence[int], jobs: Sequence[Job]):
-    from . import _lib
-    off = np.zeros(len(seqs) + 1, dtype=np.uint64)
-    off[1:] = np.cumsum([len(s) for s in seqs], dtype=np.uint64)
-    karr = np.array([min(k, 2**31 - 1) if k >= 0 else -1 for k in ks], dtype=np.int32)
-    jarr = np.array(list(jobs), dtype=_lib.HITS_JOB_DTYPE) if jobs else np.zeros(0, dtype=_lib.HITS_JOB_DTYPE)
-    return off, karr, jarr
-
-
-def best_hits(seqs: Sequence[bytes], ks: Sequence[int], jobs: Sequence[Job], K: int, min_cov_permille: int,
-              kernel_ms: Optional[list] = None) -> np.ndarray:
-    """One smx_best_hits call: job after job, per query K keys in ascending order, padded with 2^64 - 1
-    (include/smx.h: (d << 20) // len(pattern) in bits 63-43, d in bits 42-24, the target's index in its job below)."""
-    from . import _lib
-    lib = _lib.load()
-    off, karr, jarr = _arrays(seqs, ks, jobs)
-    n = sum(j[1] for j in jobs) * max(K, 0)
-    keys = np.full(max(n, 1), 0x5A5A5A5A5A5A5A5A, dtype=np.uint64)     # a sentinel: the library writes every entry
-    ms = _lib.C.c_float(0.0)
-    _lib.check(lib.smx_best_hits(b"".join(seqs), _lib.ptr(off), len(seqs), _lib.ptr(karr), _lib.ptr(jarr), len(jobs), K,
-                                 min_cov_permille, _lib.ptr(keys), _lib.C.byref(ms)))
-    if kernel_ms is not None:
-        kernel_ms.append(ms.value)
-    return keys[:n]
-
-
-def best_hits_distances(seqs: Sequence[bytes], ks: Sequence[int], jobs: Sequence[Job], K: int, min_cov_permille: int,
-                        kernel_ms: Optional[list] = None) -> List[np.ndarray]:
-    """One smx_best_hits_distances call: per job its nq x nt distances (-1: above the limit, or excluded by coverage).
-    For tests and inspection."""
-    from . import _lib
-    lib = _lib.load()
-    off, karr, jarr = _arrays(seqs, ks, jobs)
-    n = sum(j[1] * j[3] for j in jobs)
-    dist = np.full(max(n, 1), -7, dtype=np.int32)
-    ms = _lib.C.c_float(0.0)
-    _lib.check(lib.smx_best_hits_distances(b"".join(seqs), _lib.ptr(off), len(seqs), _lib.ptr(karr), _lib.ptr(jarr), len(jobs),
-                                           K, min_cov_permille, _lib.ptr(dist), _lib.C.byref(ms)))
-    if kernel_ms is not None:
-        kernel_ms.append(ms.value)
-    out, at = [], 0
-    for _, nq, _, nt in jobs:
-        out.append(dist[at:at + nq * nt].reshape(nq, nt))
-        at += nq * nt
-    return out
+best_hits = calls.best_hits
+best_hits_distances = calls.best_hits_distances
 
 
 def pair_rule(len_q: int, len_t: int, min_cov_permille: int) -> Tuple[bool, bool]:
@@ -328,24 +284,12 @@ def run(args, hits_fn: Callable = best_hits, kernel_ms: Optional[list] = None) -
     results, summary = identify(queries, db, args.min_identity, args.top, args.min_coverage, args.strand, hits_fn=hits_fn,
                                 kernel_ms=kernel_ms)
     logging.info(summary_line(summary))
-    for dest, text in ((args.report, tsv_text(results, db)), (args.json, json_text(results, db, summary))):
-        if dest:
-            with open(dest, "w", encoding="latin-1") as fh:
-                fh.write(text)
+    specimine.write_texts(((args.report, lambda: tsv_text(results, db)), (args.json, lambda: json_text(results, db, summary))))
     return 0
 
 
 def main(argv=None):
-    args = build_parser().parse_args(argv)
-    logging.basicConfig(level=logging.DEBUG if args.debug else logging.INFO,
-                        format="%(asctime)s - %(levelname)s - %(message)s")
-    try:
-        status = run(args)
-    except ValueError as e:
-        logging.error(str(e))
-        status = 2
-    if status:
-        sys.exit(status)
+    specimine.tool_main(build_parser, run, argv, value_error_status=2)
 
 
 if __name__ == "__main__":

@@ -27,6 +27,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
+from . import calls
 from .io_utils import SeqRecord, parse_fastq
 
 def build_parser() -> argparse.ArgumentParser:
@@ -212,27 +213,7 @@ def _plan(lookup, fastq, partial_forward, no_partial_reverse, min_identity) -> O
     return MineJob(fastq, partial_files, min_identity)
 
 
-def _best_identity(queries: List[bytes], ks: List[int], targets: List[bytes], djobs, kernel_ms=None) -> np.ndarray:
-    """One smx_mine_best_identity call: the full reads (queries) with their limits k (max_distance), the partial reads
-    (targets) and the device jobs (q0, nq, t0, nt, min_identity).  Returns the best identity of every job's targets,
-    job after job."""
-    from . import _lib
-    lib = _lib.load()
-    jarr = np.array(djobs, dtype=_lib.MINE_JOB_DTYPE)
-    qoff = np.zeros(len(queries) + 1, dtype=np.uint64)
-    qoff[1:] = np.cumsum([len(q) for q in queries], dtype=np.uint64)
-    toff = np.zeros(len(targets) + 1, dtype=np.uint64)
-    toff[1:] = np.cumsum([len(t) for t in targets], dtype=np.uint64)
-    # a negative k means "no limit"; a limit that does not fit 32 bits is no limit either (d <= len(full) always)
-    karr = np.array([min(k, 2**31 - 1) if k >= 0 else -1 for k in ks], dtype=np.int32)
-    best = np.zeros(max(int(jarr["nt"].sum()), 1), dtype=np.float64)
-    ms = _lib.C.c_float(0.0)
-    _lib.check(lib.smx_mine_best_identity(b"".join(queries), _lib.ptr(qoff), len(queries), _lib.ptr(karr),
-                                          b"".join(targets), _lib.ptr(toff), len(targets), _lib.ptr(jarr), len(djobs),
-                                          _lib.ptr(best), _lib.C.byref(ms)))
-    if kernel_ms is not None:
-        kernel_ms.append(ms.value)
-    return best
+_best_identity = calls.mine_best_identity
 
 
 def _mine(jobs: Sequence[MineJob], kernel_ms=None):
@@ -532,6 +513,36 @@ def mine_sequences(full_match_file: str, partial_match_files: Dict[str, List[str
     """The mined records of one specimen as (title, record) pairs, in the reference's order (types in dict order,
     files in discovery order, records in file order)."""
     return next(_mine([MineJob(full_match_file, partial_match_files, min_identity)])) or []
+
+
+# ------------------------------------------------------------------------------------------------ shared by the tools
+def permille(share: float) -> int:
+    return int(round(share * 1000))
+
+
+def write_texts(pairs) -> None:
+    """Write each (path, function that returns the text) whose path is set, one character per byte."""
+    for dest, text in pairs:
+        if dest:
+            with open(dest, "w", encoding="latin-1") as fh:
+                fh.write(text())
+
+
+def tool_main(build_parser, run, argv=None, value_error_status=None) -> None:
+    """The main() the tools share: parse, set the logging up, run(args) and exit with its status if that is not 0.  With
+    value_error_status a ValueError out of run() is logged and becomes that status."""
+    args = build_parser().parse_args(argv)
+    logging.basicConfig(level=logging.DEBUG if args.debug else logging.INFO,
+                        format="%(asctime)s - %(levelname)s - %(message)s")
+    try:
+        status = run(args)
+    except ValueError as e:
+        if value_error_status is None:
+            raise
+        logging.error(str(e))
+        status = value_error_status
+    if status:
+        sys.exit(status)
 
 
 def main(argv=None):

@@ -36,13 +36,12 @@ support is relative to the final alignment: a replicate is not re-aligned to a d
 compare bytes: give them the unmasked FASTA (--fasta).  One GPU."""
 import json
 import logging
-import sys
 import zlib
 from typing import Callable, Dict, List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 
-from . import clusters, consensus, specimine, variants
+from . import calls, clusters, consensus, specimine, variants
 
 Job = consensus.Job
 VOTE_WORDS = consensus.VOTE_WORDS
@@ -138,40 +137,13 @@ class JobSupport(NamedTuple):
 
 def resample(reads: Sequence[bytes], ks: Sequence[int], jobs: Sequence[Job], masks: np.ndarray,
              kernel_ms: Optional[list] = None) -> List[JobSupport]:
-    """One smx_cons_resample call.  masks: n_levels x (the sum of the jobs' n) uint64, the jobs' members in job order."""
-    from . import _lib
-    lib = _lib.load()
-    roff = np.zeros(len(reads) + 1, dtype=np.uint64)
-    roff[1:] = np.cumsum([len(r) for r in reads], dtype=np.uint64)
-    karr = np.array([min(k, 2**31 - 1) if k >= 0 else -1 for k in ks], dtype=np.int32)
-    jarr = np.array(list(jobs), dtype=_lib.CONS_JOB_DTYPE) if jobs else np.zeros(0, dtype=_lib.CONS_JOB_DTYPE)
-    masks = np.ascontiguousarray(masks, dtype=np.uint64)
-    n_levels = int(masks.shape[0])
-    if masks.ndim != 2 or masks.shape[1] != sum(n for _, _, n in jobs):
-        raise ValueError("masks must be n_levels x the number of members")
-    words = [len(reads[d]) + 1 for d, _, _ in jobs]
-    table = np.zeros(max(sum(words) * VOTE_WORDS, 1), dtype=np.uint32)
-    aligned = np.zeros(max(len(jobs), 1), dtype=np.uint32)
-    agree = np.zeros(max(sum(words) * n_levels, 1), dtype=np.uint64)
-    sub = np.zeros(max(len(jobs) * n_levels * REPLICATES, 1), dtype=np.uint32)
-    ms = _lib.C.c_float(0.0)
-    _lib.check(lib.smx_cons_resample(b"".join(reads), _lib.ptr(roff), len(reads), _lib.ptr(karr), _lib.ptr(jarr), len(jobs),
-                                     _lib.ptr(masks) if masks.size else None, n_levels, _lib.ptr(table), _lib.ptr(aligned),
-                                     _lib.ptr(agree), _lib.ptr(sub), _lib.C.byref(ms)))
-    if kernel_ms is not None:
-        kernel_ms.append(ms.value)
-    out, at = [], 0
-    for j, w in enumerate(words):
-        out.append(JobSupport(table[at * VOTE_WORDS:(at + w) * VOTE_WORDS].reshape(-1, VOTE_WORDS), int(aligned[j]),
-                              agree[at * n_levels:(at + w) * n_levels].reshape(n_levels, w),
-                              sub[j * n_levels * REPLICATES:(j + 1) * n_levels * REPLICATES].reshape(n_levels, REPLICATES)))
-        at += w
-    return out
+    """One smx_cons_resample call.  masks: n_levels x (the sum of the jobs' n) uint64, the jobs' members in job order
+    (ValueError for another shape)."""
+    return [JobSupport(*job) for job in calls.cons_resample(reads, ks, jobs, masks, kernel_ms)]
 
 
 # ------------------------------------------------------------------------------------------------ the numbers
-def permille(share: float) -> int:
-    return int(round(share * 1000))
+permille = specimine.permille
 
 
 def need_of(share: float) -> int:
@@ -432,23 +404,15 @@ def run(args, adjacency_fn: Callable = clusters.adjacency, votes_fn: Callable = 
         return 1
     logging.info(summary_line(summary))
     need_support = need_of(args.min_support)
-    for dest, text in ((args.fasta, lambda: fasta_text(called)), (args.report, lambda: tsv_text(called, need_support)),
-                       (args.json, lambda: json_text(called, summary, args, depths)), (args.columns, lambda: columns_text(called)),
-                       (args.masked, lambda: masked_text(called, need_support)),
-                       (args.sites if phased is not None else None, lambda: variants.sites_text(results, phased))):
-        if dest:
-            with open(dest, "w", encoding="latin-1") as fh:
-                fh.write(text())
+    specimine.write_texts(((args.fasta, lambda: fasta_text(called)), (args.report, lambda: tsv_text(called, need_support)),
+                           (args.json, lambda: json_text(called, summary, args, depths)), (args.columns, lambda: columns_text(called)),
+                           (args.masked, lambda: masked_text(called, need_support)),
+                           (args.sites if phased is not None else None, lambda: variants.sites_text(results, phased))))
     return 0
 
 
 def main(argv=None):
-    args = build_parser().parse_args(argv)
-    logging.basicConfig(level=logging.DEBUG if args.debug else logging.INFO,
-                        format="%(asctime)s - %(levelname)s - %(message)s")
-    status = run(args)
-    if status:
-        sys.exit(status)
+    specimine.tool_main(build_parser, run, argv)
 
 
 if __name__ == "__main__":

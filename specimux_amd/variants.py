@@ -31,12 +31,11 @@ specimux-crosstalk --consensus and specimux-identify --consensus read it as it i
 import argparse
 import json
 import logging
-import sys
 from typing import Callable, Dict, List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 
-from . import clusters, consensus, specimine
+from . import calls, clusters, consensus, specimine
 
 Job = consensus.Job
 VOTE_WORDS = consensus.VOTE_WORDS
@@ -83,8 +82,7 @@ def build_parser() -> argparse.ArgumentParser:
     return parser
 
 
-def permille(share: float) -> int:
-    return int(round(share * 1000))
+permille = specimine.permille
 
 
 # ------------------------------------------------------------------------------------------------ the device call
@@ -92,39 +90,10 @@ def phase(reads: Sequence[bytes], ks: Sequence[int], jobs: Sequence[Job], min_pe
           kernel_ms: Optional[list] = None) -> List[JobPhase]:
     """One smx_cons_phase call: per job what consensus.votes returns for it, its kept sites, its allele planes and its
     link table."""
-    from . import _lib
-    lib = _lib.load()
-    roff = np.zeros(len(reads) + 1, dtype=np.uint64)
-    roff[1:] = np.cumsum([len(r) for r in reads], dtype=np.uint64)
-    karr = np.array([min(k, 2**31 - 1) if k >= 0 else -1 for k in ks], dtype=np.int32)
-    jarr = np.array(list(jobs), dtype=_lib.CONS_JOB_DTYPE) if jobs else np.zeros(0, dtype=_lib.CONS_JOB_DTYPE)
-    vwords = [(len(reads[d]) + 1) * VOTE_WORDS for d, _, _ in jobs]
-    pwords = [(n + 63) // 64 for _, _, n in jobs]
-    slots = max_sites
-    table = np.zeros(max(sum(vwords), 1), dtype=np.uint32)
-    aligned = np.zeros(max(len(jobs), 1), dtype=np.uint32)
-    sites = np.zeros(max(len(jobs) * slots, 1), dtype=_lib.CONS_SITE_DTYPE)
-    n_sites = np.zeros(max(len(jobs), 1), dtype=np.uint32)
-    n_qualified = np.zeros(max(len(jobs), 1), dtype=np.uint32)
-    planes = np.zeros(max(sum(pwords) * 2 * slots, 1), dtype=np.uint64)
-    link = np.zeros(max(len(jobs) * slots * slots * 4, 1), dtype=np.uint32)
-    ms = _lib.C.c_float(0.0)
-    _lib.check(lib.smx_cons_phase(b"".join(reads), _lib.ptr(roff), len(reads), _lib.ptr(karr), _lib.ptr(jarr), len(jobs),
-                                  min_permille, min_reads, max_sites, _lib.ptr(table), _lib.ptr(aligned), _lib.ptr(sites),
-                                  _lib.ptr(n_sites), _lib.ptr(n_qualified), _lib.ptr(planes), _lib.ptr(link),
-                                  _lib.C.byref(ms)))
-    if kernel_ms is not None:
-        kernel_ms.append(ms.value)
-    out, vat, pat = [], 0, 0
-    for j, (vw, pw) in enumerate(zip(vwords, pwords)):
-        kept = [Site(int(s["pos"]), int(s["kind"]), int(s["major"]), int(s["minor"]), int(s["n_major"]), int(s["n_minor"]))
-                for s in sites[j * slots:j * slots + int(n_sites[j])]]
-        out.append(JobPhase(table[vat:vat + vw].reshape(-1, VOTE_WORDS), int(aligned[j]), kept, int(n_qualified[j]),
-                            planes[pat:pat + slots * 2 * pw].reshape(slots, 2, pw),
-                            link[j * slots * slots * 4:(j + 1) * slots * slots * 4].reshape(slots, slots, 4)))
-        vat += vw
-        pat += slots * 2 * pw
-    return out
+    return [JobPhase(table, aligned, [Site(int(s["pos"]), int(s["kind"]), int(s["major"]), int(s["minor"]), int(s["n_major"]),
+                                           int(s["n_minor"])) for s in kept], n_qualified, planes, link)
+            for table, aligned, kept, n_qualified, planes, link
+            in calls.cons_phase(reads, ks, jobs, min_permille, min_reads, max_sites, kernel_ms)]
 
 
 # ------------------------------------------------------------------------------------------------ the decisions
@@ -376,21 +345,14 @@ def run(args, adjacency_fn: Callable = clusters.adjacency, votes_fn: Callable = 
                 logging.warning(f"{res.path}: cluster {ph.pc.rank}: {ph.n_qualified} sites qualified, the first "
                                 f"{len(ph.sites)} were kept (--max-sites)")
     logging.info(summary_line(summary))
-    for dest, text in ((args.fasta, lambda: fasta_text(results, phased)), (args.report, lambda: tsv_text(results, phased)),
-                       (args.json, lambda: json_text(results, phased, summary)), (args.sites, lambda: sites_text(results, phased))):
-        if dest:
-            with open(dest, "w", encoding="latin-1") as fh:
-                fh.write(text())
+    specimine.write_texts(((args.fasta, lambda: fasta_text(results, phased)), (args.report, lambda: tsv_text(results, phased)),
+                           (args.json, lambda: json_text(results, phased, summary)),
+                           (args.sites, lambda: sites_text(results, phased))))
     return 0
 
 
 def main(argv=None):
-    args = build_parser().parse_args(argv)
-    logging.basicConfig(level=logging.DEBUG if args.debug else logging.INFO,
-                        format="%(asctime)s - %(levelname)s - %(message)s")
-    status = run(args)
-    if status:
-        sys.exit(status)
+    specimine.tool_main(build_parser, run, argv)
 
 
 if __name__ == "__main__":

@@ -115,7 +115,7 @@ def test_bad_alignment_arguments_are_refused_before_the_device_is_asked():
     """Each refusal of smx_align and smx_align_batch comes from host code with its documented status (include/smx.h); on a
     machine without a GPU the same calls with good arguments are the ones that fail, with SMX_ERR_DEVICE."""
     import torch
-    from specimux_amd import _lib
+    from specimux_amd import _lib, calls
     lib = _lib.load()
     valid = _lib.OK if torch.cuda.is_available() else _lib.ERR_DEVICE
 
@@ -139,8 +139,7 @@ def test_bad_alignment_arguments_are_refused_before_the_device_is_asked():
     assert single(b"A" * 64, b"C")[0] == valid
 
     def batch(queries, targets, qidx, ks, modes, n=None):
-        qoff = np.concatenate([[0], np.cumsum([len(q) for q in queries])]).astype(np.uint32)
-        toff = np.concatenate([[0], np.cumsum([len(t) for t in targets])]).astype(np.uint64)
+        qoff, toff = calls.offsets(queries, np.uint32), calls.offsets(targets)
         qidx, ks, modes = np.array(qidx, dtype=np.uint32), np.array(ks, dtype=np.int32), np.array(modes, dtype=np.uint8)
         n = len(targets) if n is None else n
         dist, nloc = np.zeros(max(n, 1), dtype=np.int32), np.zeros(max(n, 1), dtype=np.int32)

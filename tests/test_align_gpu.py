@@ -50,11 +50,10 @@ def single(lib, q, t, k, mode, cap=None):
 
 def batch(lib, reqs, cap):
     """smx_align_batch over (q, t, k, mode) -> per request (dist, nloc, the pairs written); cap 0: NULL buffers."""
-    from specimux_amd import _lib
+    from specimux_amd import _lib, calls
     qtab = {}
     qidx = np.array([qtab.setdefault(r[0], len(qtab)) for r in reqs], dtype=np.uint32)
-    qoff = np.concatenate([[0], np.cumsum([len(q) for q in qtab])]).astype(np.uint32)
-    toff = np.concatenate([[0], np.cumsum([len(r[1]) for r in reqs])]).astype(np.uint64)
+    qoff, toff = calls.offsets(list(qtab), np.uint32), calls.offsets([r[1] for r in reqs])
     k, mode = np.array([r[2] for r in reqs], dtype=np.int32), np.array([r[3] for r in reqs], dtype=np.uint8)
     n = len(reqs)
     dist, nloc = np.full(n, -7, dtype=np.int32), np.full(n, -7, dtype=np.int32)

@@ -16,7 +16,7 @@ import pytest
 
 from clusters_utils import mutate, rand_seq
 from oracle.edlib_semantics import HW, NW, align_c
-from specimux_amd import _lib
+from specimux_amd import _lib, calls
 from variants_utils import phase_reference
 
 pytestmark = pytest.mark.gpu
@@ -85,14 +85,14 @@ def mine_call(args, best):
     lib = _lib.load()
     n_out = int(args["jobs"]["nt"].sum())          # one query per job: both modes have sum(nt) outputs
     out = np.full(n_out, -5.0, dtype=np.float64) if best else np.full(n_out, -7, dtype=np.int32)
-    ms = _lib.C.c_float(-1.0)
-    fn = lib.smx_mine_best_identity if best else lib.smx_mine_distances
+    ms = []
     t = time.perf_counter()
-    rc = fn(args["queries"], _lib.ptr(args["qoff"]), 48, _lib.ptr(args["ks"]), args["targets"], _lib.ptr(args["toff"]), 700,
-            _lib.ptr(args["jobs"]), len(args["jobs"]), _lib.ptr(out), _lib.C.byref(ms))
+    rc = calls.invoke("smx_mine_best_identity" if best else "smx_mine_distances", args["queries"], _lib.ptr(args["qoff"]), 48,
+                      _lib.ptr(args["ks"]), args["targets"], _lib.ptr(args["toff"]), 700, _lib.ptr(args["jobs"]), len(args["jobs"]),
+                      _lib.ptr(out), kernel_ms=ms, check=False)
     assert rc == _lib.OK, lib.smx_last_error()
     print(f"\nsmx_mine_{'best_identity' if best else 'distances'}: {len(args['jobs'])} records, {n_out} outputs, "
-          f"kernel {ms.value:.2f} ms, call {time.perf_counter() - t:.2f} s")
+          f"kernel {ms[0]:.2f} ms, call {time.perf_counter() - t:.2f} s")
     return out
 
 
@@ -155,14 +155,14 @@ def pairs_rows():
 def pairs_call(args, n_out, neighbours):
     lib = _lib.load()
     out = np.full(n_out, 0xDEADBEEF, dtype=np.uint32) if neighbours else np.full(n_out, -7, dtype=np.int32)
-    ms = _lib.C.c_float(-1.0)
-    fn = lib.smx_pairs_neighbours if neighbours else lib.smx_pairs_distances
+    ms = []
     t = time.perf_counter()
-    rc = fn(args["reads"], _lib.ptr(args["roff"]), args["n_reads"], _lib.ptr(args["ks"]), _lib.ptr(args["jobs"]), len(args["jobs"]),
-            _lib.ptr(out), _lib.C.byref(ms))
+    rc = calls.invoke("smx_pairs_neighbours" if neighbours else "smx_pairs_distances", args["reads"], _lib.ptr(args["roff"]),
+                      args["n_reads"], _lib.ptr(args["ks"]), _lib.ptr(args["jobs"]), len(args["jobs"]), _lib.ptr(out), kernel_ms=ms,
+                      check=False)
     assert rc == _lib.OK, lib.smx_last_error()
     print(f"\nsmx_pairs_{'neighbours' if neighbours else 'distances'}: {len(args['jobs'])} jobs, {n_out} outputs, "
-          f"kernel {ms.value:.2f} ms, call {time.perf_counter() - t:.2f} s")
+          f"kernel {ms[0]:.2f} ms, call {time.perf_counter() - t:.2f} s")
     return out
 
 
@@ -223,13 +223,14 @@ def test_cons_phase_over_65535_jobs():
     planes = np.full((n_jobs, max_sites, 2, 1), 0xDEADBEEFDEADBEEF, dtype=np.uint64)
     link = np.full((n_jobs, max_sites, max_sites, 4), 0xDEADBEEF, dtype=np.uint32)
     lib = _lib.load()
-    ms = _lib.C.c_float(-1.0)
+    ms = []
     t = time.perf_counter()
-    rc = lib.smx_cons_phase(b"".join(reads), _lib.ptr(offsets([8] * len(reads))), len(reads), _lib.ptr(np.full(len(reads), k, dtype=np.int32)),
-                            _lib.ptr(jobs), n_jobs, min_permille, min_reads, max_sites, _lib.ptr(votes), _lib.ptr(aligned),
-                            _lib.ptr(sites), _lib.ptr(n_sites), _lib.ptr(n_qualified), _lib.ptr(planes), _lib.ptr(link), _lib.C.byref(ms))
+    rc = calls.invoke("smx_cons_phase", b"".join(reads), _lib.ptr(offsets([8] * len(reads))), len(reads),
+                      _lib.ptr(np.full(len(reads), k, dtype=np.int32)), _lib.ptr(jobs), n_jobs, min_permille, min_reads, max_sites,
+                      _lib.ptr(votes), _lib.ptr(aligned), _lib.ptr(sites), _lib.ptr(n_sites), _lib.ptr(n_qualified), _lib.ptr(planes),
+                      _lib.ptr(link), kernel_ms=ms, check=False)
     assert rc == _lib.OK, lib.smx_last_error()
-    print(f"\nsmx_cons_phase: {n_jobs} jobs, kernel {ms.value:.2f} ms, call {time.perf_counter() - t:.2f} s")
+    print(f"\nsmx_cons_phase: {n_jobs} jobs, kernel {ms[0]:.2f} ms, call {time.perf_counter() - t:.2f} s")
     assert n_jobs > GRID_DIM_CAP
     assert np.array_equal(aligned, ref_aligned[combo]), differing(aligned, ref_aligned[combo])
     assert np.array_equal(votes, ref_votes[combo]), np.argwhere(votes != ref_votes[combo])[:5]

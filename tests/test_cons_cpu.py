@@ -81,10 +81,10 @@ def test_bad_jobs_are_refused_before_the_device_is_asked():
     machine without a GPU the same call with good jobs is the one that fails, with SMX_ERR_DEVICE."""
     import numpy as np
     import torch
-    from specimux_amd import _lib
+    from specimux_amd import _lib, calls
     lib = _lib.load()
     reads = [b"ACGTACGT", b"ACGAACGT", b"", b"ACGT", b"ACGTT"]
-    roff = np.concatenate([[0], np.cumsum([len(r) for r in reads])]).astype(np.uint64)
+    roff = calls.offsets(reads)
     ks = np.array([2] * len(reads), dtype=np.int32)
 
     def call(jobs, fn):

@@ -9,7 +9,7 @@ import pytest
 
 from clusters_utils import mutate, rand_seq
 from cons_utils import NO_ROW, pileup_reference, reduce_rows, row_reference
-from specimux_amd import _lib
+from specimux_amd import _lib, calls
 
 pytestmark = pytest.mark.gpu
 
@@ -19,24 +19,23 @@ ALL_BYTES = "".join(map(chr, range(256)))
 def cons_raw(reads, ks, jobs, votes=False):
     """One smx_cons_pileup / smx_cons_votes call on bytes reads; jobs are (draft, r0, n).  The outputs are filled with
     a sentinel first.  -> (status, rows or votes, dist or aligned, kernel ms)."""
-    lib = _lib.load()
-    roff = np.concatenate([[0], np.cumsum([len(r) for r in reads])]).astype(np.uint64)
+    roff = calls.offsets(reads)
     jobs = [tuple(j) for j in jobs]
     words = [len(reads[d]) + 1 if d < len(reads) else 0 for d, _, _ in jobs]
-    jarr = np.array(jobs, dtype=_lib.CONS_JOB_DTYPE) if jobs else np.zeros(0, dtype=_lib.CONS_JOB_DTYPE)
+    jarr = calls.job_array(jobs, _lib.CONS_JOB_DTYPE)
     if votes:
         n_a, n_b = sum(w * 26 for w in words), len(jobs)
         b = np.full(max(n_b, 1), 0xDEADBEEF, dtype=np.uint32)
-        fn = lib.smx_cons_votes
+        fn = "smx_cons_votes"
     else:
         n_a, n_b = sum(w * n for w, (_, _, n) in zip(words, jobs)), sum(n for _, _, n in jobs)
         b = np.full(max(n_b, 1), -7, dtype=np.int32)
-        fn = lib.smx_cons_pileup
+        fn = "smx_cons_pileup"
     a = np.full(max(n_a, 1), 0xDEADBEEF, dtype=np.uint32)
-    ms = _lib.C.c_float(-1.0)
-    rc = fn(b"".join(reads), _lib.ptr(roff), len(reads), _lib.ptr(np.array(ks, dtype=np.int32)), _lib.ptr(jarr), len(jobs),
-            _lib.ptr(a), _lib.ptr(b), _lib.C.byref(ms))
-    return rc, a[:n_a], b[:n_b], ms.value
+    ms = []
+    rc = calls.invoke(fn, b"".join(reads), _lib.ptr(roff), len(reads), _lib.ptr(np.array(ks, dtype=np.int32)), _lib.ptr(jarr),
+                      len(jobs), _lib.ptr(a), _lib.ptr(b), kernel_ms=ms, check=False)
+    return rc, a[:n_a], b[:n_b], ms[0]
 
 
 def member_set(rng, q, kd, alphabet):

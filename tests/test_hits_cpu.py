@@ -78,10 +78,10 @@ def test_bad_calls_are_refused_before_the_device_is_asked():
     """Every refusal is host code alone: on a machine without a GPU the same call with good arguments is the one that
     fails, with SMX_ERR_DEVICE."""
     import torch
-    from specimux_amd import _lib
+    from specimux_amd import _lib, calls
     lib = _lib.load()
     seqs = [b"ACGTACGT", b"ACGAACGT", b"", b"ACGT", b"ACGTT"]
-    off = np.concatenate([[0], np.cumsum([len(s) for s in seqs])]).astype(np.uint64)
+    off = calls.offsets(seqs)
     ks = np.array([2] * len(seqs), dtype=np.int32)
 
     def call(jobs, hits, K=5, cov=500):
@@ -103,7 +103,7 @@ def test_bad_calls_are_refused_before_the_device_is_asked():
 
 
 def test_a_job_of_more_than_2_24_targets_is_unsupported():
-    from specimux_amd import _lib
+    from specimux_amd import _lib, calls
     lib = _lib.load()
     n = 2**24 + 2                                  # one query, 2^24 + 1 targets, one byte each
     off = np.arange(n + 1, dtype=np.uint64)

@@ -9,7 +9,7 @@ import numpy as np
 import pytest
 
 from oracle.edlib_semantics import HW, align_c
-from specimux_amd import _lib, identify
+from specimux_amd import _lib, calls, identify
 
 pytestmark = pytest.mark.gpu
 
@@ -257,13 +257,13 @@ def test_a_small_call_after_a_large_one(case, contention):
 def test_refusals_launch_nothing():
     lib = _lib.load()
     seqs = [b"ACGTACGT", b"ACGAACGT", b"", b"ACGT", b"ACGTT"]
-    off = np.concatenate([[0], np.cumsum([len(s) for s in seqs])]).astype(np.uint64)
+    off = calls.offsets(seqs)
     ks = np.array([2] * len(seqs), dtype=np.int32)
 
     def call(jobs, K=5, cov=500):
         jarr = np.array(jobs, dtype=_lib.HITS_JOB_DTYPE)
         a = np.full(256, 0x5A, dtype=np.uint64)
-        ms = _lib.C.c_float(-1.0)
+        ms = _lib.C.c_float(-1.0)                  # its own kernel_ms, and so a direct call: a refusal must leave it alone
         rc = lib.smx_best_hits(b"".join(seqs), _lib.ptr(off), len(seqs), _lib.ptr(ks), _lib.ptr(jarr), len(jobs), K, cov,
                                _lib.ptr(a), _lib.C.byref(ms))
         return rc, lib.smx_last_error().decode(), a, ms.value

@@ -67,10 +67,10 @@ def test_bad_jobs_are_refused_before_the_device_is_asked():
     without a GPU the same call with good jobs is the one that fails, with SMX_ERR_DEVICE."""
     import numpy as np
     import torch
-    from specimux_amd import _lib
+    from specimux_amd import _lib, calls
     lib = _lib.load()
     seqs = [b"ACGTACGT", b"ACGAACGT", b"", b"ACGT", b"ACGTT"]
-    off = np.concatenate([[0], np.cumsum([len(s) for s in seqs])]).astype(np.uint64)
+    off = calls.offsets(seqs)
     ks = np.array([2] * len(seqs), dtype=np.int32)
     group = np.arange(len(seqs), dtype=np.uint32)
 

@@ -8,7 +8,7 @@ import numpy as np
 import pytest
 
 from oracle.edlib_semantics import NW, align_c
-from specimux_amd import _lib, crosstalk
+from specimux_amd import _lib, calls, crosstalk
 
 pytestmark = pytest.mark.gpu
 
@@ -197,7 +197,7 @@ def test_keys_equal_the_host_reduction(case, monkeypatch, min_chunks):
 def test_argument_errors_carry_a_message():
     lib = _lib.load()
     seqs = [b"ACGTACGT", b"ACGAACGT", b"", b"ACGT", b"ACGTT"]
-    off = np.concatenate([[0], np.cumsum([len(s) for s in seqs])]).astype(np.uint64)
+    off = calls.offsets(seqs)
     ks = np.array([2] * len(seqs), dtype=np.int32)
     group = np.arange(len(seqs), dtype=np.uint32)
 

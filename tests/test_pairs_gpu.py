@@ -7,7 +7,7 @@ import pytest
 
 from clusters_utils import mutate, rand_seq
 from oracle.edlib_semantics import NW, align_c
-from specimux_amd import _lib
+from specimux_amd import _lib, calls
 
 pytestmark = pytest.mark.gpu
 
@@ -28,22 +28,20 @@ def pair_limit(ki, kj):
 def pairs_raw(reads, ks, jobs, neighbours=False, sentinel=None):
     """One smx_pairs_distances / smx_pairs_neighbours call on str reads; jobs are (r0, n).  The output is filled with a
     sentinel first.  -> (status, output array, kernel ms)."""
-    lib = _lib.load()
     rs = [r.encode("latin-1") for r in reads]
-    roff = np.concatenate([[0], np.cumsum([len(r) for r in rs])]).astype(np.uint64)
-    jarr = np.array(jobs, dtype=_lib.PAIRS_JOB_DTYPE) if jobs else np.zeros(0, dtype=_lib.PAIRS_JOB_DTYPE)
+    roff, jarr = calls.offsets(rs), calls.job_array(jobs, _lib.PAIRS_JOB_DTYPE)
     if neighbours:
         n_out = sum(n * ((n + 31) // 32) for _, n in jobs)
         out = np.full(max(n_out, 1), 0xDEADBEEF if sentinel is None else sentinel, dtype=np.uint32)
-        fn = lib.smx_pairs_neighbours
+        fn = "smx_pairs_neighbours"
     else:
         n_out = sum(n * (n - 1) // 2 for _, n in jobs)
         out = np.full(max(n_out, 1), -7 if sentinel is None else sentinel, dtype=np.int32)
-        fn = lib.smx_pairs_distances
-    ms = _lib.C.c_float(-1.0)
-    rc = fn(b"".join(rs), _lib.ptr(roff), len(rs), _lib.ptr(np.array(ks, dtype=np.int32)), _lib.ptr(jarr), len(jobs),
-            _lib.ptr(out), _lib.C.byref(ms))
-    return rc, out[:n_out], ms.value
+        fn = "smx_pairs_distances"
+    ms = []
+    rc = calls.invoke(fn, b"".join(rs), _lib.ptr(roff), len(rs), _lib.ptr(np.array(ks, dtype=np.int32)), _lib.ptr(jarr), len(jobs),
+                      _lib.ptr(out), kernel_ms=ms, check=False)
+    return rc, out[:n_out], ms[0]
 
 
 def job_pairs(jobs):

@@ -8,7 +8,7 @@ import numpy as np
 import pytest
 
 from clusters_utils import rand_seq
-from specimux_amd import _lib, consensus
+from specimux_amd import _lib, calls, consensus
 from specimux_amd.variants import JobPhase, Site
 from variants_utils import phase_reference
 
@@ -20,9 +20,7 @@ SENTINEL = 0xDEADBEEF
 def phase_raw(reads, ks, jobs, min_permille, min_reads, max_sites):
     """One smx_cons_phase call with every output filled with a sentinel first.  -> (status, [JobPhase], site slots past
     the kept ones, kernel ms)."""
-    lib = _lib.load()
-    roff = np.concatenate([[0], np.cumsum([len(r) for r in reads])]).astype(np.uint64)
-    jarr = np.array(jobs, dtype=_lib.CONS_JOB_DTYPE) if jobs else np.zeros(0, dtype=_lib.CONS_JOB_DTYPE)
+    roff, jarr = calls.offsets(reads), calls.job_array(jobs, _lib.CONS_JOB_DTYPE)
     vwords = [(len(reads[d]) + 1) * 26 for d, _, _ in jobs]
     pwords = [(n + 63) // 64 for _, _, n in jobs]
     votes = np.full(max(sum(vwords), 1), SENTINEL, dtype=np.uint32)
@@ -33,12 +31,13 @@ def phase_raw(reads, ks, jobs, min_permille, min_reads, max_sites):
     n_qualified = np.full(max(len(jobs), 1), SENTINEL, dtype=np.uint32)
     planes = np.full(max(sum(pwords) * 2 * max_sites, 1), 0xDEADBEEFDEADBEEF, dtype=np.uint64)
     link = np.full(max(len(jobs) * max_sites * max_sites * 4, 1), SENTINEL, dtype=np.uint32)
-    ms = _lib.C.c_float(-1.0)
-    rc = lib.smx_cons_phase(b"".join(reads), _lib.ptr(roff), len(reads), _lib.ptr(np.array(ks, dtype=np.int32)), _lib.ptr(jarr),
-                            len(jobs), min_permille, min_reads, max_sites, _lib.ptr(votes), _lib.ptr(aligned), _lib.ptr(sites),
-                            _lib.ptr(n_sites), _lib.ptr(n_qualified), _lib.ptr(planes), _lib.ptr(link), _lib.C.byref(ms))
+    ms = []
+    rc = calls.invoke("smx_cons_phase", b"".join(reads), _lib.ptr(roff), len(reads), _lib.ptr(np.array(ks, dtype=np.int32)),
+                      _lib.ptr(jarr), len(jobs), min_permille, min_reads, max_sites, _lib.ptr(votes), _lib.ptr(aligned),
+                      _lib.ptr(sites), _lib.ptr(n_sites), _lib.ptr(n_qualified), _lib.ptr(planes), _lib.ptr(link), kernel_ms=ms,
+                      check=False)
     if rc != _lib.OK:
-        return rc, [], None, ms.value
+        return rc, [], None, ms[0]
     out, spare, vat, pat = [], [], 0, 0
     for j, (vw, pw) in enumerate(zip(vwords, pwords)):
         slots = sites[j * max_sites:(j + 1) * max_sites]
@@ -49,7 +48,7 @@ def phase_raw(reads, ks, jobs, min_permille, min_reads, max_sites):
                             link[j * max_sites ** 2 * 4:(j + 1) * max_sites ** 2 * 4].reshape(max_sites, max_sites, 4)))
         vat, pat = vat + vw, pat + max_sites * 2 * pw
     assert vat == votes.size or not jobs
-    return rc, out, spare, ms.value
+    return rc, out, spare, ms[0]
 
 
 def assert_equal(got, spare, want):

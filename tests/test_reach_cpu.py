@@ -101,10 +101,10 @@ def test_bad_calls_are_refused_before_the_device_is_asked():
     """Every refusal is host code alone: on a machine without a GPU the same call with good arguments is the one that
     fails, with SMX_ERR_DEVICE."""
     import torch
-    from specimux_amd import _lib
+    from specimux_amd import _lib, calls
     lib = _lib.load()
     seqs = [b"ACGTACGT", b"ACGAACGT", b"", b"ACGT", b"ACGTT"]
-    off = np.concatenate([[0], np.cumsum([len(s) for s in seqs])]).astype(np.uint64)
+    off = calls.offsets(seqs)
     w = np.array([1] * len(seqs), dtype=np.uint32)
 
     def call(jobs, keys, E=5, off=off):

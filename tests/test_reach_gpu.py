@@ -11,7 +11,7 @@ import numpy as np
 import pytest
 
 import bimera_utils as U
-from specimux_amd import _lib, bimera, identify
+from specimux_amd import _lib, bimera, calls, identify
 
 pytestmark = pytest.mark.gpu
 
@@ -122,13 +122,13 @@ def test_a_small_call_after_a_large_one(case):
 def test_refusals_launch_nothing():
     lib = _lib.load()
     seqs = [b"ACGTACGT", b"ACGAACGT", b"", b"ACGT", b"ACGTT"]
-    off = np.concatenate([[0], np.cumsum([len(s) for s in seqs])]).astype(np.uint64)
+    off = calls.offsets(seqs)
     w = np.ones(len(seqs), dtype=np.uint32)
 
     def call(jobs, E=5, matrix=False):
         jarr = np.array(jobs, dtype=_lib.REACH_JOB_DTYPE)
         a = np.full(1024, 0x5A, dtype=np.uint64)
-        ms = _lib.C.c_float(-1.0)
+        ms = _lib.C.c_float(-1.0)                  # its own kernel_ms, and so a direct call: a refusal must leave it alone
         fn = lib.smx_prefix_reach_matrix if matrix else lib.smx_prefix_reach
         rc = fn(b"".join(seqs), _lib.ptr(off), len(seqs), _lib.ptr(w), _lib.ptr(w), _lib.ptr(jarr), len(jobs), E, _lib.ptr(a),
                 _lib.C.byref(ms))

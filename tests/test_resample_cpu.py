@@ -153,10 +153,10 @@ def test_bad_resample_arguments_are_refused_before_the_device_is_asked():
     no job: on a machine without a GPU the same call with good arguments is the one that fails, with SMX_ERR_DEVICE.  The
     checks of the jobs come with the plan, as for smx_cons_votes."""
     import torch
-    from specimux_amd import _lib
+    from specimux_amd import _lib, calls
     lib = _lib.load()
     reads = [b"ACGTACGT", b"ACGAACGT", b"", b"ACGT", b"ACGTT"]
-    roff = np.concatenate([[0], np.cumsum([len(r) for r in reads])]).astype(np.uint64)
+    roff = calls.offsets(reads)
     ks = np.array([2] * len(reads), dtype=np.int32)
 
     def call(jobs, n_levels, with_masks=True):

@@ -11,7 +11,7 @@ import pytest
 
 from clusters_utils import rand_seq
 from cons_utils import votes_reference
-from specimux_amd import _lib, consensus
+from specimux_amd import _lib, calls, consensus
 from support_utils import resample_reference
 
 pytestmark = pytest.mark.gpu
@@ -24,9 +24,7 @@ ONES = 2**64 - 1
 def resample_raw(reads, ks, jobs, masks):
     """One smx_cons_resample call with every output filled with a sentinel first.  -> (status, [(table, aligned, agree,
     sub_aligned)] per job, kernel ms)."""
-    lib = _lib.load()
-    roff = np.concatenate([[0], np.cumsum([len(r) for r in reads])]).astype(np.uint64)
-    jarr = np.array(jobs, dtype=_lib.CONS_JOB_DTYPE) if jobs else np.zeros(0, dtype=_lib.CONS_JOB_DTYPE)
+    roff, jarr = calls.offsets(reads), calls.job_array(jobs, _lib.CONS_JOB_DTYPE)
     masks = np.ascontiguousarray(masks, dtype=np.uint64)
     n_levels = masks.shape[0]
     words = [len(reads[d]) + 1 for d, _, _ in jobs]
@@ -34,12 +32,12 @@ def resample_raw(reads, ks, jobs, masks):
     aligned = np.full(max(len(jobs), 1), SENTINEL, dtype=np.uint32)
     agree = np.full(max(sum(words) * n_levels, 1), SENTINEL64, dtype=np.uint64)
     sub = np.full(max(len(jobs) * n_levels * 64, 1), SENTINEL, dtype=np.uint32)
-    ms = _lib.C.c_float(-1.0)
-    rc = lib.smx_cons_resample(b"".join(reads), _lib.ptr(roff), len(reads), _lib.ptr(np.array(ks, dtype=np.int32)),
-                               _lib.ptr(jarr), len(jobs), _lib.ptr(masks) if masks.size else None, n_levels, _lib.ptr(votes),
-                               _lib.ptr(aligned), _lib.ptr(agree), _lib.ptr(sub), _lib.C.byref(ms))
+    ms = []
+    rc = calls.invoke("smx_cons_resample", b"".join(reads), _lib.ptr(roff), len(reads), _lib.ptr(np.array(ks, dtype=np.int32)),
+                      _lib.ptr(jarr), len(jobs), _lib.ptr(masks) if masks.size else None, n_levels, _lib.ptr(votes),
+                      _lib.ptr(aligned), _lib.ptr(agree), _lib.ptr(sub), kernel_ms=ms, check=False)
     if rc != _lib.OK:
-        return rc, [], ms.value
+        return rc, [], ms[0]
     out, at = [], 0
     for j, w in enumerate(words):
         out.append((votes[at * 26:(at + w) * 26].reshape(-1, 26), int(aligned[j]),
@@ -47,7 +45,7 @@ def resample_raw(reads, ks, jobs, masks):
                     sub[j * n_levels * 64:(j + 1) * n_levels * 64].reshape(n_levels, 64)))
         at += w
     assert at * n_levels == agree.size or not jobs
-    return rc, out, ms.value
+    return rc, out, ms[0]
 
 
 def assert_equal(got, want):

@@ -10,7 +10,7 @@ import pytest
 
 from conftest import GOLDEN
 from oracle.edlib_semantics import HW, align_c
-from specimux_amd import _lib, specimine, synth
+from specimux_amd import _lib, calls, specimine, synth
 
 pytestmark = pytest.mark.gpu
 
@@ -32,8 +32,7 @@ def kernel_dists(pairs):
         ks.append(k)
         targets.extend(pairs[i][1].encode("latin-1") for i in idx)
         order.extend(idx)
-    qoff = np.concatenate([[0], np.cumsum([len(q) for q in queries])]).astype(np.uint64)
-    toff = np.concatenate([[0], np.cumsum([len(t) for t in targets])]).astype(np.uint64)
+    qoff, toff = calls.offsets(queries), calls.offsets(targets)
     jarr = np.array(jobs, dtype=_lib.MINE_JOB_DTYPE)
     dist = np.full(len(pairs), -7, dtype=np.int32)
     _lib.check(lib.smx_mine_distances(b"".join(queries), _lib.ptr(qoff), len(queries), _lib.ptr(np.array(ks, np.int32)),
@@ -151,8 +150,7 @@ def mine_raw(queries, ks, targets, jobs, best=False, sentinel=None):
     lib = _lib.load()
     qs = [q.encode("latin-1") if isinstance(q, str) else q for q in queries]
     ts = [t.encode("latin-1") if isinstance(t, str) else t for t in targets]
-    qoff = np.concatenate([[0], np.cumsum([len(q) for q in qs])]).astype(np.uint64)
-    toff = np.concatenate([[0], np.cumsum([len(t) for t in ts])]).astype(np.uint64)
+    qoff, toff = calls.offsets(qs), calls.offsets(ts)
     jarr = np.array(jobs, dtype=_lib.MINE_JOB_DTYPE)
     if best:
         n_out = sum(j[3] for j in jobs)

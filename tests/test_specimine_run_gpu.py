@@ -10,7 +10,7 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN, REPO
-from specimux_amd import _lib, specimine, synth
+from specimux_amd import _lib, calls, specimine, synth
 
 pytestmark = pytest.mark.gpu
 
@@ -39,8 +39,7 @@ def best_both(queries, ks, targets, jobs):
     lib = _lib.load()
     qb = [q.encode("latin-1") for q in queries]
     tb = [t.encode("latin-1") for t in targets]
-    qoff = np.concatenate([[0], np.cumsum([len(q) for q in qb])]).astype(np.uint64)
-    toff = np.concatenate([[0], np.cumsum([len(t) for t in tb])]).astype(np.uint64)
+    qoff, toff = calls.offsets(qb), calls.offsets(tb)
     jarr = np.array(jobs, dtype=_lib.MINE_JOB_DTYPE)
     karr = np.array(ks, dtype=np.int32)
     n_out = int(jarr["nt"].sum()) if len(jobs) else 0

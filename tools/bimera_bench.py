@@ -27,8 +27,8 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
 sys.path.insert(0, os.path.join(REPO, "tools"))
 
-from specimux_amd import _lib, bimera  # noqa: E402
-from cluster_bench import BASES, mutate, spread  # noqa: E402
+from specimux_amd import _lib, bimera, calls  # noqa: E402
+from cluster_bench import BASES, device_ms, mutate, spread  # noqa: E402
 
 
 def rand(rng, n):
@@ -55,10 +55,9 @@ def make_pool(rng, seqs, n, lo=600, hi=700, related_share=0.01):
 
 def reach_call(seqs, sizes, pool, E):
     """-> call(r) -> kernel ms with the pool rotated r times; stats() of the last output"""
-    lib = _lib.load()
     N, P = len(seqs), len(pool)
     job = (0, N, N, P) if P else (0, N, 0, N)
-    jarr = np.array([job], dtype=_lib.REACH_JOB_DTYPE)
+    jarr = calls.job_array([job], _lib.REACH_JOB_DTYPE)
     keys = np.zeros(N * 2 * (E + 1) * bimera.SLOTS, dtype=np.uint64)
     weight = np.array(list(sizes) + [bimera.ALWAYS] * P, dtype=np.uint32)
     need = np.array([bimera.need_of(s, 2000) for s in sizes] + [0] * P, dtype=np.uint32)
@@ -68,12 +67,8 @@ def reach_call(seqs, sizes, pool, E):
     def call(r):
         at = (r * (P // 7 + 1)) % max(P, 1)
         all_seqs = list(seqs) + pool[at:] + pool[:at]
-        off = np.zeros(len(all_seqs) + 1, dtype=np.uint64)
-        off[1:] = np.cumsum([len(s) for s in all_seqs], dtype=np.uint64)
-        t = _lib.C.c_float(0.0)
-        _lib.check(lib.smx_prefix_reach(b"".join(all_seqs), _lib.ptr(off), len(all_seqs), _lib.ptr(weight), _lib.ptr(need),
-                                        _lib.ptr(jarr), 1, E, _lib.ptr(keys), _lib.C.byref(t)))
-        return t.value
+        return device_ms("smx_prefix_reach", b"".join(all_seqs), _lib.ptr(calls.offsets(all_seqs)), len(all_seqs), _lib.ptr(weight),
+                         _lib.ptr(need), _lib.ptr(jarr), 1, E, _lib.ptr(keys))
 
     def stats():
         pairs = keys.reshape(-1, bimera.SLOTS) != np.uint64(bimera.NONE)

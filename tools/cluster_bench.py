@@ -24,7 +24,7 @@ import numpy as np
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
 
-from specimux_amd import _lib, clusters, specimine  # noqa: E402
+from specimux_amd import _lib, calls, clusters, specimine  # noqa: E402
 
 BASES = np.frombuffer(b"ACGT", dtype=np.uint8)
 
@@ -66,60 +66,58 @@ def spread(ms):
             "kernel_ms_max": round(max(ms), 3)}
 
 
+def device_ms(name, *args):
+    """One libsmx call through calls.invoke -> the device time it reports."""
+    ms = []
+    calls.invoke(name, *args, kernel_ms=ms)
+    return ms[0]
+
+
 def pairs_call(specimens, neighbours):
     """-> (call() -> kernel ms, within() -> pairs within their limit in the last output)"""
-    lib = _lib.load()
     reads = [r for rs, _ in specimens for r in rs]
-    roff = np.zeros(len(reads) + 1, dtype=np.uint64)
-    roff[1:] = np.cumsum([len(r) for r in reads], dtype=np.uint64)
-    karr = np.array([k for _, ks in specimens for k in ks], dtype=np.int32)
-    jobs = np.zeros(len(specimens), dtype=_lib.PAIRS_JOB_DTYPE)
-    at = 0
-    for j, (rs, _) in enumerate(specimens):
-        jobs[j] = (at, len(rs))
+    roff = calls.offsets(reads)
+    karr = calls.limits([k for _, ks in specimens for k in ks])
+    jobs, at = [], 0
+    for rs, _ in specimens:
+        jobs.append((at, len(rs)))
         at += len(rs)
+    jobs = calls.job_array(jobs, _lib.PAIRS_JOB_DTYPE)
     n_out = sum(len(rs) * ((len(rs) + 31) // 32) if neighbours else len(rs) * (len(rs) - 1) // 2 for rs, _ in specimens)
     out = np.zeros(max(n_out, 1), dtype=np.uint32 if neighbours else np.int32)
-    fn = lib.smx_pairs_neighbours if neighbours else lib.smx_pairs_distances
+    name = "smx_pairs_neighbours" if neighbours else "smx_pairs_distances"
     blob = b"".join(reads)
 
     def call():
-        t = _lib.C.c_float(0.0)
-        _lib.check(fn(blob, _lib.ptr(roff), len(reads), _lib.ptr(karr), _lib.ptr(jobs), len(specimens), _lib.ptr(out),
-                      _lib.C.byref(t)))
-        return t.value
+        return device_ms(name, blob, _lib.ptr(roff), len(reads), _lib.ptr(karr), _lib.ptr(jobs), len(specimens), _lib.ptr(out))
 
     return call, lambda: int(np.unpackbits(out.view(np.uint8)).sum()) // 2 if neighbours else int((out >= 0).sum())
 
 
 def mine_call(specimens):
-    lib = _lib.load()
     reads = [r for rs, _ in specimens for r in rs]
-    off = np.zeros(len(reads) + 1, dtype=np.uint64)
-    off[1:] = np.cumsum([len(r) for r in reads], dtype=np.uint64)
-    karr = np.array([k for _, ks in specimens for k in ks], dtype=np.int32)
+    off = calls.offsets(reads)
+    karr = calls.limits([k for _, ks in specimens for k in ks])
     jobs, at = [], 0
     for rs, _ in specimens:
         jobs.append((at, len(rs), at, len(rs), 0.0))
         at += len(rs)
-    jarr = np.array(jobs, dtype=_lib.MINE_JOB_DTYPE)
+    jarr = calls.job_array(jobs, _lib.MINE_JOB_DTYPE)
     out = np.zeros(sum(len(rs) ** 2 for rs, _ in specimens), dtype=np.int32)
     blob = b"".join(reads)
 
     def call():
-        t = _lib.C.c_float(0.0)
-        _lib.check(lib.smx_mine_distances(blob, _lib.ptr(off), len(reads), _lib.ptr(karr), blob, _lib.ptr(off), len(reads),
-                                          _lib.ptr(jarr), len(jobs), _lib.ptr(out), _lib.C.byref(t)))
-        return t.value
+        return device_ms("smx_mine_distances", blob, _lib.ptr(off), len(reads), _lib.ptr(karr), blob, _lib.ptr(off), len(reads),
+                         _lib.ptr(jarr), len(jobs), _lib.ptr(out))
 
     return call, lambda: int((out >= 0).sum())
 
 
-def timed(calls, repeats):
+def timed(fns, repeats):
     """Each call once as a warm-up, then `repeats` rounds that alternate between them.  -> kernel ms per call."""
-    ms = [[] for _ in calls]
+    ms = [[] for _ in fns]
     for r in range(repeats + 1):
-        for i, call in enumerate(calls):
+        for i, call in enumerate(fns):
             t = call()
             if r:
                 ms[i].append(t)

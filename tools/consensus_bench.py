@@ -21,8 +21,8 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
-from cluster_bench import BASES, mutate, pairs_call, spread, timed  # noqa: E402
-from specimux_amd import _lib, specimine  # noqa: E402
+from cluster_bench import BASES, device_ms, mutate, pairs_call, spread, timed  # noqa: E402
+from specimux_amd import _lib, calls, specimine  # noqa: E402
 
 
 def history_bytes(m, n, k):
@@ -60,19 +60,16 @@ def main():
         reads = [mutate(rng, template, a.error).tobytes() for _ in range(a.reads)]
         specimens.append((reads, [specimine.max_distance(len(r), a.min_identity) for r in reads]))
     reads = [r for rs, _ in specimens for r in rs]
-    roff = np.zeros(len(reads) + 1, dtype=np.uint64)
-    roff[1:] = np.cumsum([len(r) for r in reads], dtype=np.uint64)
-    karr = np.array([k for _, ks in specimens for k in ks], dtype=np.int32)
-    jobs = np.array([(c * a.reads, c * a.reads, a.reads) for c in range(a.clusters)], dtype=_lib.CONS_JOB_DTYPE)
+    roff = calls.offsets(reads)
+    karr = calls.limits([k for _, ks in specimens for k in ks])
+    jobs = calls.job_array([(c * a.reads, c * a.reads, a.reads) for c in range(a.clusters)], _lib.CONS_JOB_DTYPE)
     votes = np.zeros(sum((len(rs[0]) + 1) * _lib.CONS_VOTE_WORDS for rs, _ in specimens), dtype=np.uint32)
     aligned = np.zeros(a.clusters, dtype=np.uint32)
     blob = b"".join(reads)
 
     def cons_call():
-        t = _lib.C.c_float(0.0)
-        _lib.check(lib.smx_cons_votes(blob, _lib.ptr(roff), len(reads), _lib.ptr(karr), _lib.ptr(jobs), a.clusters,
-                                      _lib.ptr(votes), _lib.ptr(aligned), _lib.C.byref(t)))
-        return t.value
+        return device_ms("smx_cons_votes", blob, _lib.ptr(roff), len(reads), _lib.ptr(karr), _lib.ptr(jobs), a.clusters,
+                         _lib.ptr(votes), _lib.ptr(aligned))
 
     nb_call, nb_count = pairs_call(specimens, True)
     c_ms, n_ms = timed([cons_call, nb_call], a.repeats)

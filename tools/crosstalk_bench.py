@@ -21,27 +21,21 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
 sys.path.insert(0, os.path.join(REPO, "tools"))
 
-from specimux_amd import _lib, specimine  # noqa: E402
-from cluster_bench import BASES, mutate, pairs_call, spread, timed  # noqa: E402
+from specimux_amd import _lib, calls, specimine  # noqa: E402
+from cluster_bench import BASES, device_ms, mutate, pairs_call, spread, timed  # noqa: E402
 
 
 def nearest_call(seqs, ks, groups, jobs):
     """-> (call() -> kernel ms, found() -> reads with an own key, reads with an other key in the last output)"""
-    lib = _lib.load()
-    off = np.zeros(len(seqs) + 1, dtype=np.uint64)
-    off[1:] = np.cumsum([len(s) for s in seqs], dtype=np.uint64)
-    karr = np.array(ks, dtype=np.int32)
+    off, karr, jarr = calls.offsets(seqs), calls.limits(ks), calls.job_array(jobs, _lib.NEAREST_JOB_DTYPE)
     garr = np.array(groups, dtype=np.uint32)
-    jarr = np.array(jobs, dtype=_lib.NEAREST_JOB_DTYPE)
     n = sum(j[3] for j in jobs)
     own, other = np.zeros(n, dtype=np.uint64), np.zeros(n, dtype=np.uint64)
     blob = b"".join(seqs)
 
     def call():
-        t = _lib.C.c_float(0.0)
-        _lib.check(lib.smx_nearest(blob, _lib.ptr(off), len(seqs), _lib.ptr(karr), _lib.ptr(garr), _lib.ptr(jarr), len(jobs),
-                                   _lib.ptr(own), _lib.ptr(other), _lib.C.byref(t)))
-        return t.value
+        return device_ms("smx_nearest", blob, _lib.ptr(off), len(seqs), _lib.ptr(karr), _lib.ptr(garr), _lib.ptr(jarr), len(jobs),
+                         _lib.ptr(own), _lib.ptr(other))
 
     none = np.uint64(2**64 - 1)
     return call, lambda: (int((own != none).sum()), int((other != none).sum()))

@@ -29,8 +29,8 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
 sys.path.insert(0, os.path.join(REPO, "tools"))
 
-from specimux_amd import _lib, identify, specimine  # noqa: E402
-from cluster_bench import BASES, mutate, spread  # noqa: E402
+from specimux_amd import _lib, calls, identify, specimine  # noqa: E402
+from cluster_bench import BASES, device_ms, mutate, spread  # noqa: E402
 
 
 def rand(rng, n):
@@ -68,20 +68,15 @@ def rotated(refs, r):
 
 def hits_call(queries, refs, ks_q, ks_r, K, cov):
     """-> call(r) -> kernel ms on the database rotated r times; stats() of the last output"""
-    lib = _lib.load()
-    jarr = np.array([(0, len(queries), len(queries), len(refs))], dtype=_lib.HITS_JOB_DTYPE)
+    jarr = calls.job_array([(0, len(queries), len(queries), len(refs))], _lib.HITS_JOB_DTYPE)
     keys = np.zeros(len(queries) * K, dtype=np.uint64)
 
     def call(r):
         order = rotated(list(range(len(refs))), r)
         seqs = list(queries) + [refs[i] for i in order]
-        off = np.zeros(len(seqs) + 1, dtype=np.uint64)
-        off[1:] = np.cumsum([len(s) for s in seqs], dtype=np.uint64)
-        karr = np.array(list(ks_q) + [ks_r[i] for i in order], dtype=np.int32)
-        t = _lib.C.c_float(0.0)
-        _lib.check(lib.smx_best_hits(b"".join(seqs), _lib.ptr(off), len(seqs), _lib.ptr(karr), _lib.ptr(jarr), 1, K, cov,
-                                     _lib.ptr(keys), _lib.C.byref(t)))
-        return t.value
+        karr = calls.limits(list(ks_q) + [ks_r[i] for i in order])
+        return device_ms("smx_best_hits", b"".join(seqs), _lib.ptr(calls.offsets(seqs)), len(seqs), _lib.ptr(karr), _lib.ptr(jarr), 1,
+                         K, cov, _lib.ptr(keys))
 
     def stats():
         rows = keys.reshape(-1, K) != np.uint64(identify.NONE)
@@ -91,22 +86,15 @@ def hits_call(queries, refs, ks_q, ks_r, K, cov):
 
 def mine_call(queries, refs, ks_q, min_identity):
     """smx_mine_best_identity over the same pairs: every query against every ref (the refs are the targets)."""
-    lib = _lib.load()
-    qoff = np.zeros(len(queries) + 1, dtype=np.uint64)
-    qoff[1:] = np.cumsum([len(s) for s in queries], dtype=np.uint64)
-    karr = np.array(ks_q, dtype=np.int32)
-    jarr = np.array([(0, len(queries), 0, len(refs), min_identity)], dtype=_lib.MINE_JOB_DTYPE)
+    qoff, karr = calls.offsets(queries), calls.limits(ks_q)
+    jarr = calls.job_array([(0, len(queries), 0, len(refs), min_identity)], _lib.MINE_JOB_DTYPE)
     best = np.zeros(len(refs), dtype=np.float64)
     qblob = b"".join(queries)
 
     def call(r):
         rs = rotated(refs, r)
-        toff = np.zeros(len(rs) + 1, dtype=np.uint64)
-        toff[1:] = np.cumsum([len(s) for s in rs], dtype=np.uint64)
-        t = _lib.C.c_float(0.0)
-        _lib.check(lib.smx_mine_best_identity(qblob, _lib.ptr(qoff), len(queries), _lib.ptr(karr), b"".join(rs), _lib.ptr(toff),
-                                              len(rs), _lib.ptr(jarr), 1, _lib.ptr(best), _lib.C.byref(t)))
-        return t.value
+        return device_ms("smx_mine_best_identity", qblob, _lib.ptr(qoff), len(queries), _lib.ptr(karr), b"".join(rs),
+                         _lib.ptr(calls.offsets(rs)), len(rs), _lib.ptr(jarr), 1, _lib.ptr(best))
     return call, lambda: {"targets_with_identity": int((best > 0).sum())}
 
 

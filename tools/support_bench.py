@@ -27,8 +27,8 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
-from cluster_bench import BASES, mutate, spread, timed, write_tree  # noqa: E402
-from specimux_amd import _lib, specimine, support  # noqa: E402
+from cluster_bench import BASES, device_ms, mutate, spread, timed, write_tree  # noqa: E402
+from specimux_amd import _lib, calls, specimine, support  # noqa: E402
 
 
 def main():
@@ -61,19 +61,14 @@ def main():
     for c in range(a.clusters):
         for l, (tag, d, _) in enumerate(support.level_depths(a.reads, depths)):
             masks[l, c * a.reads:(c + 1) * a.reads] = support.subset_masks(1, f"S{c:03d}_c1", tag, a.reads, d)
-    roff = np.zeros(len(reads) + 1, dtype=np.uint64)
-    roff[1:] = np.cumsum([len(r) for r in reads], dtype=np.uint64)
-    karr = np.array(ks, dtype=np.int32)
-    jarr = np.array(jobs, dtype=_lib.CONS_JOB_DTYPE)
+    roff, karr, jarr = calls.offsets(reads), calls.limits(ks), calls.job_array(jobs, _lib.CONS_JOB_DTYPE)
     votes = np.zeros(sum((len(reads[d]) + 1) * _lib.CONS_VOTE_WORDS for d, _, _ in jobs), dtype=np.uint32)
     aligned = np.zeros(a.clusters, dtype=np.uint32)
     blob = b"".join(reads)
 
     def votes_call():
-        t = _lib.C.c_float(0.0)
-        _lib.check(lib.smx_cons_votes(blob, _lib.ptr(roff), len(reads), _lib.ptr(karr), _lib.ptr(jarr), a.clusters,
-                                      _lib.ptr(votes), _lib.ptr(aligned), _lib.C.byref(t)))
-        return t.value
+        return device_ms("smx_cons_votes", blob, _lib.ptr(roff), len(reads), _lib.ptr(karr), _lib.ptr(jarr), a.clusters,
+                         _lib.ptr(votes), _lib.ptr(aligned))
 
     last = []
 
