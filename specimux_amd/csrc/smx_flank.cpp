@@ -2,6 +2,7 @@
 // into, and the stand-alone assignment of keys to candidate barcodes.  Kernels: smx_flank.hip, logic: smx_flank_core.h.
 #include "smx_host.h"
 #include "smx_flank_core.h"
+#include "smx_flank_plan.h"
 
 extern "C" int smx_launch_flank_count(const smx::FlankPanel *P, void *stream, const uint8_t *d_windows, int wstride,
                                       const int32_t *d_lens, const smx_hit *d_hits, uint32_t n_reads, uint64_t *d_keys,
@@ -103,33 +104,13 @@ int smx_flank_assign(const uint64_t *keys, uint32_t n_keys, const char *cands, c
                      const uint8_t *cand_primer, uint32_t n_cands, int32_t k, int32_t *best, int32_t *first, int32_t *ntied,
                      float *kernel_ms) {
     if (kernel_ms) *kernel_ms = 0.f;
-    if ((n_keys && (!keys || !best || !first || !ntied)) || !cand_off || (n_cands && (!cands || !cand_primer)))
-        return fail(SMX_ERR_ARG, "null argument");
-    if (k < 0) return fail(SMX_ERR_ARG, "negative distance threshold %d", k);
-    for (uint32_t i = 0; i < n_keys; i++)
-        if (keys[i] == SMX_STATS_EMPTY || smx::flank_key_len(keys[i]) > SMX_FLANK_MAX_W)
-            return fail(SMX_ERR_ARG, "key %u (%016llx) is no flank key", i, (unsigned long long)keys[i]);
-    // the candidates grouped by primer, each group in the caller's order
-    std::vector<int> pstart(65, 0), clen(n_cands), cidx(n_cands);
-    std::vector<uint32_t> cmw((size_t)n_cands * 4);
-    for (uint32_t c = 0; c < n_cands; c++) {
-        const uint32_t m = cand_off[c + 1] - cand_off[c];
-        if (cand_off[c + 1] < cand_off[c] || m < 1 || m > SMX_FLANK_MAX_W)
-            return fail(SMX_ERR_ARG, "candidate %u has %u letters (1..%d)", c, m, SMX_FLANK_MAX_W);
-        if (cand_primer[c] >= 64) return fail(SMX_ERR_ARG, "candidate %u names primer %u (0..63)", c, cand_primer[c]);
-        pstart[cand_primer[c] + 1]++;
-    }
-    for (int p = 0; p < 64; p++) pstart[p + 1] += pstart[p];
-    std::vector<int> at(pstart.begin(), pstart.end() - 1);
-    for (uint32_t c = 0; c < n_cands; c++) {
-        const int m = (int)(cand_off[c + 1] - cand_off[c]), s = at[cand_primer[c]]++;
-        unsigned long long peq[16];
-        std::string bad;
-        if (!build_peq(cands + cand_off[c], m, peq, &bad)) return fail(SMX_ERR_ARG, "candidate %u: %s", c, bad.c_str());
-        for (int b = 0; b < 4; b++) cmw[(size_t)s * 4 + b] = (uint32_t)peq[b];   // codes 0..3 = A C G T
-        clen[s] = m;
-        cidx[s] = (int)c;
-    }
+    smx::FlankAssignPlan plan;   // argument checks and the candidates grouped by primer (smx_flank_plan.h)
+    std::string why;
+    const int rc = smx::flank_assign_plan(keys, n_keys, cands, cand_off, cand_primer, n_cands, k, best && first && ntied, build_peq,
+                                          &plan, &why);
+    if (rc != SMX_OK) return fail(rc, "%s", why.c_str());
+    const std::vector<int> &pstart = plan.pstart, &clen = plan.clen, &cidx = plan.cidx;
+    const std::vector<uint32_t> &cmw = plan.cmw;
     if (n_keys == 0) return SMX_OK;
     SMX_TRY(require_device());
     DevMem<uint64_t> d_keys;

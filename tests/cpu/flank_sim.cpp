@@ -7,6 +7,8 @@
 //   flank_sim exhaustive       every {A,C} candidate of 1-5 letters x every {A,C,G} flank of 0-7 letters x every k
 //   flank_sim random SEED      13-letter (and 1..26-letter) candidates, planted copies at distance exactly k and k + 1,
 //                              IUPAC candidates; writes oracle_sample.txt (candidate hex, flank hex, distance)
+//   flank_sim plan             the host plan of smx_flank_assign (smx_flank_plan.h: argument checks, candidates regrouped
+//                              by primer) against a plain stable sort by primer, and every refusal (flank_plan_host.h)
 // Prints "name value" counters and, last, "N mismatches".
 #include <cstdio>
 #include <cstdlib>
@@ -17,6 +19,7 @@
 #include <vector>
 
 #include "smx_flank_core.h"
+#include "flank_plan_host.h"
 
 using namespace smx;
 
@@ -301,12 +304,22 @@ static int run_random(unsigned long seed) {
     return 0;
 }
 
+// ---- mode plan
+static int run_plan() {
+    FlankPlanCounts C;
+    flank_plan_cases(&C);
+    flank_plan_print(C);
+    mismatches += C.mismatches;
+    return 0;
+}
+
 int main(int argc, char **argv) {
     int rc = 2;
     if (argc >= 2 && !strcmp(argv[1], "flank")) rc = run_flank();
     else if (argc >= 2 && !strcmp(argv[1], "exhaustive")) rc = run_exhaustive();
     else if (argc >= 3 && !strcmp(argv[1], "random")) rc = run_random(strtoul(argv[2], nullptr, 10));
-    else fprintf(stderr, "usage: flank_sim flank | exhaustive | random SEED\n");
+    else if (argc >= 2 && !strcmp(argv[1], "plan")) rc = run_plan();
+    else fprintf(stderr, "usage: flank_sim flank | exhaustive | random SEED | plan\n");
     if (rc) return rc;
     printf("%ld mismatches\n", mismatches);
     return mismatches ? 1 : 0;

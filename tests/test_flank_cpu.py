@@ -2,7 +2,8 @@
 flank_of_hit, flank_shw and flank_take the gfx950 kernels of smx_flank.hip run, over smx_stats_core.h's table) against plain
 string code: the end string built with an ordinary reverse complement and sliced, a full DP matrix for the prefix distance.
 A sample of the simulation's DP distances is checked against the suite's oracle, and the counters it prints are bounded
-from below so that its coverage cannot shrink unnoticed.  No GPU needed."""
+from below so that its coverage cannot shrink unnoticed.  The host plan of smx_flank_assign (smx_flank_plan.h) runs in
+the same simulation against a plain stable sort by primer.  No GPU needed."""
 import os
 import subprocess
 
@@ -88,6 +89,17 @@ def test_shw_structured_random(sim, tmp_path, seed):
             assert got["editDistance"] == int(want), (cand, flank, want, got["editDistance"])
             n += 1
     assert n == c["oracle_sample"] >= 300
+
+
+def test_assign_plan_against_a_stable_sort_by_primer(sim, tmp_path):
+    """The host plan of smx_flank_assign (smx_flank_plan.h): the candidates regrouped by primer, each group in the caller's
+    order, equal a plain stable sort by primer; every refusal is refused with its message."""
+    c = run(sim, tmp_path, "plan")
+    assert c["plan_cases"] == 8 and c["plan_refusals"] == 16
+    assert c["plan_interleaved"] >= 4            # caller's lists whose primers descend somewhere: the grouping permutes
+    assert c["plan_moved"] >= 500                # candidates whose grouped slot is not their caller's index
+    assert c["plan_empty_primers"] >= 5 and c["plan_primer63"] >= 500
+    assert c["plan_no_candidates"] == 2 and c["plan_largest_group"] == 600 and c["plan_candidates"] >= 1500
 
 
 def test_assign_checks_its_arguments_on_the_host():

@@ -217,6 +217,8 @@ def test_forced_paths_land_in_their_counters(lib, cases):
 
 @pytest.mark.parametrize("name", ["c1_nopf", "c3_nopf", "near_nopf"])
 def test_assign_agrees_with_the_demux_kernel(lib, cases, name):
+    """A cross-check between two kernels of this project, on hits with one primer location.  The assign kernel's reference
+    is the plain twin of tests/test_flank_assign_gpu.py."""
     from specimux_amd import barcodes
     from specimux_amd.models import reverse_complement
     _both, cp, reads, _pan = cases[name]
