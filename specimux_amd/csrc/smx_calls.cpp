@@ -1,5 +1,11 @@
 // smx_calls.cpp -- the one-shot calls of libsmx.so over host buffers: alignments (smx_align, smx_align_batch), specimine
 // (smx_mine.hip), clusters (smx_pairs.hip), consensus (smx_cons.hip), crosstalk (smx_nearest.hip), identify (smx_hits.hip), bimera (smx_reach.hip) and the inner scan (smx_inner.hip).  Each keeps one grow-only device workspace; its calls are serialised.
+// Every *_call below runs in one order: null checks, the plan (a bad call is refused here, without a
+// device), the workspace's lock, require_device, *kernel_ms = 0, the early returns of a call without work, the uploads,
+// the launches (timed_launches), the copy-out.  Consensus alone zeroes *kernel_ms and answers a call without jobs
+// before it asks for the device (the tests pin it), so there a good call without a device fails with *kernel_ms
+// zeroed.  What a call uploads beyond its sequences and what it copies out is spelled out in the call; the rest is
+// the frame right below.
 #include "smx_host.h"
 #include "smx_align_lane.h"   // align_collect
 #include "smx_cons_plan.h"
@@ -104,22 +110,58 @@ int smx_align_batch(const char *queries, const uint32_t *qoff, uint32_t n_querie
     return SMX_OK;
 }
 
+// ---- the frame of the chunked calls
+namespace {
+// a plan's refusal (smx_*_plan.h: a status and why) as the call's failure
+int refused(int rc, const std::string &why) { return rc == SMX_OK ? SMX_OK : fail(rc, "%s", why.c_str()); }
+
+// The padded sequences of a call on the device: the bytes, where each begins and how long it is.
+struct DevSeqs {
+    DevBuf bytes, doff, len;
+    int upload(const std::vector<unsigned char> &pad, const std::vector<uint64_t> &off, const std::vector<int32_t> &lens) {
+        HIP_TRY(bytes.upload(pad));
+        HIP_TRY(doff.upload(off));
+        HIP_TRY(len.upload(lens));
+        return SMX_OK;
+    }
+    int upload(const char *seqs, const uint64_t *off, uint32_t n) {   // the caller's sequences, padded here (smx_chunk_plan.h)
+        std::vector<uint64_t> d;
+        std::vector<int32_t> l;
+        std::vector<unsigned char> pad;
+        std::string why;
+        SMX_TRY(refused(smx::chunk_padded_sequences(seqs, off, n, &d, &l, &pad, &why), why));
+        return upload(pad, d, l);
+    }
+};
+
+// the generic class's per-lane state, one slice per workgroup: only a call with records of that class needs it
+int ensure_scratch(DevBuf *scratch, const smx::ChunkLaunches &L) {
+    if (L.n[0]) HIP_TRY(scratch->ensure((size_t)L.scratch_words * 8));
+    return SMX_OK;
+}
+
+// The launches of a call, timed if the caller asks for it: enqueue() puts them on the null stream and returns the
+// first nonzero launch status.  what: "mining kernel launch", for the message.  Returns once the device is idle.
+// The events are the section's own: the inner scan, which has a section per launch group, creates a pair per group.
+template <typename F> int timed_launches(float *kernel_ms, const char *what, F &&enqueue) {
+    KernelTimer timer;
+    if (kernel_ms) HIP_TRY(timer.start());
+    if (const int e = enqueue()) return fail(SMX_ERR_DEVICE, "%s failed: %s", what, hipGetErrorString((hipError_t)e));
+    if (kernel_ms) HIP_TRY(timer.stop(kernel_ms));
+    HIP_TRY(hipDeviceSynchronize());
+    return SMX_OK;
+}
+}  // namespace
+
 // ---- specimine: batched long-read HW distances (smx_mine.hip); grow-only device workspace, calls serialised
 namespace {
 struct {
     std::mutex mutex;
-    DevBuf queries, qoff, targets, tdoff, tlen, pairs, chunk_start;
+    DevBuf queries, qoff, pairs, chunk_start;
+    DevSeqs targets;
     DevBuf scratch;     // per-lane state of the generic class, one slice per workgroup
     DevBuf jobs_out;    // the jobs, then the output
 } g_mine;
-
-// the padded copy of the targets (smx_chunk_plan.h), failing the call's way
-int mine_targets(const char *targets, const uint64_t *toff, uint32_t n_targets, std::vector<uint64_t> *tdoff,
-                 std::vector<int32_t> *tlen, std::vector<unsigned char> *tpad) {
-    std::string why;
-    const int rc = smx::mine_targets(targets, toff, n_targets, tdoff, tlen, tpad, &why);
-    return rc == SMX_OK ? SMX_OK : fail(rc, "%s", why.c_str());
-}
 
 // One smx_mine_* call.  distances: job j's nq x nt distances at out[sum over earlier jobs of nq * nt] (int32); else
 // the best identities at out[sum over earlier jobs of nt] (double).  Device and host memory hold the queries, the
@@ -129,45 +171,37 @@ int mine_call(bool distances, const char *queries, const uint64_t *qoff, uint32_
               void *out, float *kernel_ms) {
     if (!out && n_jobs) return fail(SMX_ERR_ARG, "null argument");
     if (!queries || !qoff || !k || !targets || !toff || (n_jobs && !jobs)) return fail(SMX_ERR_ARG, "null argument");
-    std::lock_guard<std::mutex> guard(g_mine.mutex);
-    SMX_TRY(require_device());
     // the checks, the padded targets, the jobs, the (job, query) records by class and the grids: smx_mine_plan.h
     smx::MinePlan P;
     std::string why;
-    const int rc = smx::mine_plan(queries, qoff, n_queries, k, targets, toff, n_targets, jobs, n_jobs, smx::CHUNK_SCRATCH_BYTES,
-                                  &P, &why);
-    if (rc != SMX_OK) return fail(rc, "%s", why.c_str());
+    SMX_TRY(refused(smx::mine_plan(queries, qoff, n_queries, k, targets, toff, n_targets, jobs, n_jobs, smx::CHUNK_SCRATCH_BYTES,
+                                   &P, &why), why));
+    std::lock_guard<std::mutex> guard(g_mine.mutex);
+    SMX_TRY(require_device());
+    if (kernel_ms) *kernel_ms = 0.0f;
     const uint64_t n_out = distances ? P.n_dist : P.n_best;
-    if (n_out == 0) {
-        if (kernel_ms) *kernel_ms = 0.0f;
-        return SMX_OK;
-    }
+    if (n_out == 0) return SMX_OK;
     const size_t out_bytes = n_out * (distances ? sizeof(int32_t) : sizeof(double));
     auto &W = g_mine;
     const size_t jobs_bytes = n_jobs * sizeof(smx::MineJobDev);
     HIP_TRY(W.queries.upload(queries, (size_t)qoff[n_queries]));
     HIP_TRY(W.qoff.upload(qoff, ((size_t)n_queries + 1) * 8));
-    HIP_TRY(W.targets.upload(P.tpad));
-    HIP_TRY(W.tdoff.upload(P.tdoff));
-    HIP_TRY(W.tlen.upload(P.tlen));
+    SMX_TRY(W.targets.upload(P.tpad, P.tdoff, P.tlen));
     HIP_TRY(W.pairs.upload(P.pairs));
     HIP_TRY(W.chunk_start.upload(P.chunk_start));
-    if (P.n_pairs[0]) HIP_TRY(W.scratch.ensure((size_t)P.scratch_words * 8));
+    SMX_TRY(ensure_scratch(&W.scratch, P));
     HIP_TRY(W.jobs_out.upload(P.jobs.data(), jobs_bytes, out_bytes));
     void *d_out = W.jobs_out.as<char>() + jobs_bytes;
     if (!distances) HIP_TRY(hipMemset(d_out, 0, out_bytes));       // +0.0: "no pair counts"
-    KernelTimer timer;
-    if (kernel_ms) HIP_TRY(timer.start());
-    const int e = smx::chunk_for_each_class(P.n_pairs, [&](int c, int wr, uint32_t n, size_t pat, size_t cat) {
-        return smx_launch_mine(nullptr, wr, distances, W.queries.as<unsigned char>(), W.qoff.as<uint64_t>(),
-                               W.targets.as<unsigned char>(), W.tdoff.as<uint64_t>(), W.tlen.as<int32_t>(),
-                               W.pairs.as<smx::MinePair>() + pat, W.chunk_start.as<uint64_t>() + cat, n, W.jobs_out.p,
-                               (int)P.grid[c], P.per_block[c], P.lds_max[c], d_out, W.scratch.as<unsigned long long>(),
-                               P.words_max0);
-    });
-    if (e != 0) return fail(SMX_ERR_DEVICE, "mining kernel launch failed: %s", hipGetErrorString((hipError_t)e));
-    if (kernel_ms) HIP_TRY(timer.stop(kernel_ms));
-    HIP_TRY(hipDeviceSynchronize());
+    SMX_TRY(timed_launches(kernel_ms, "mining kernel launch", [&] {
+        return smx::chunk_for_each_class(P, [&](const smx::ChunkLaunch &L) {
+            return smx_launch_mine(nullptr, L.wr, distances, W.queries.as<unsigned char>(), W.qoff.as<uint64_t>(),
+                                   W.targets.bytes.as<unsigned char>(), W.targets.doff.as<uint64_t>(), W.targets.len.as<int32_t>(),
+                                   W.pairs.as<smx::MinePair>() + L.rec_at, W.chunk_start.as<uint64_t>() + L.start_at, L.n,
+                                   W.jobs_out.p, L.grid, L.per_block, L.lds, d_out, W.scratch.as<unsigned long long>(),
+                                   P.words_max0);
+        });
+    }));
     HIP_TRY(hipMemcpy(out, d_out, out_bytes, hipMemcpyDeviceToHost));
     return SMX_OK;
 }
@@ -190,7 +224,8 @@ int smx_mine_best_identity(const char *queries, const uint64_t *qoff, uint32_t n
 namespace {
 struct {
     std::mutex mutex;
-    DevBuf reads, doff, len, k, rows, chunk_start;
+    DevSeqs reads;
+    DevBuf k, rows, chunk_start;
     DevBuf scratch;     // per-lane state of the generic class, one slice per workgroup
     DevBuf jobs_out;    // the jobs, then the output
 } g_pairs;
@@ -200,13 +235,12 @@ struct {
 int pairs_call(bool distances, const char *reads, const uint64_t *roff, uint32_t n_reads, const int32_t *k,
                const smx_pairs_job *jobs, uint32_t n_jobs, uint32_t *out, float *kernel_ms) {
     if (!reads || !roff || !k || (n_jobs && (!jobs || !out))) return fail(SMX_ERR_ARG, "null argument");
-    std::lock_guard<std::mutex> guard(g_pairs.mutex);
-    SMX_TRY(require_device());
     // the checks, the padded reads, the jobs, the rows by class and the grids: smx_pairs_plan.h
     smx::PairsPlan P;
     std::string why;
-    const int rc = smx::pairs_plan(distances, reads, roff, n_reads, jobs, n_jobs, smx::CHUNK_SCRATCH_BYTES, &P, &why);
-    if (rc != SMX_OK) return fail(rc, "%s", why.c_str());
+    SMX_TRY(refused(smx::pairs_plan(distances, reads, roff, n_reads, jobs, n_jobs, smx::CHUNK_SCRATCH_BYTES, &P, &why), why));
+    std::lock_guard<std::mutex> guard(g_pairs.mutex);
+    SMX_TRY(require_device());
     if (kernel_ms) *kernel_ms = 0.0f;
     if (P.n_out == 0) return SMX_OK;
     const size_t out_bytes = P.n_out * 4;
@@ -216,27 +250,22 @@ int pairs_call(bool distances, const char *reads, const uint64_t *roff, uint32_t
     }
     auto &W = g_pairs;
     const size_t jobs_bytes = (n_jobs * sizeof(smx::PairsJobDev) + 15) & ~(size_t)15;
-    HIP_TRY(W.reads.upload(P.pad));
-    HIP_TRY(W.doff.upload(P.doff));
-    HIP_TRY(W.len.upload(P.len));
+    SMX_TRY(W.reads.upload(P.pad, P.doff, P.len));
     HIP_TRY(W.k.upload(k, (size_t)n_reads * 4));
     HIP_TRY(W.rows.upload(P.rows));
     HIP_TRY(W.chunk_start.upload(P.chunk_start));
-    if (P.n_rows[0]) HIP_TRY(W.scratch.ensure((size_t)P.scratch_words * 8));
+    SMX_TRY(ensure_scratch(&W.scratch, P));
     HIP_TRY(W.jobs_out.upload(P.jobs.data(), n_jobs * sizeof(smx::PairsJobDev), jobs_bytes - n_jobs * sizeof(smx::PairsJobDev) + out_bytes));
     void *d_out = W.jobs_out.as<char>() + jobs_bytes;
     if (!distances) HIP_TRY(hipMemset(d_out, 0, out_bytes));
-    KernelTimer timer;
-    if (kernel_ms) HIP_TRY(timer.start());
-    const int e = smx::chunk_for_each_class(P.n_rows, [&](int c, int wr, uint32_t n, size_t rat, size_t cat) {
-        return smx_launch_pairs(nullptr, wr, distances, W.reads.as<unsigned char>(), W.doff.as<uint64_t>(),
-                                W.len.as<int32_t>(), W.k.as<int32_t>(), W.rows.as<smx::PairsRow>() + rat,
-                                W.chunk_start.as<uint64_t>() + cat, n, W.jobs_out.p, (int)P.grid[c], P.per_block[c],
-                                P.lds_max[c], d_out, W.scratch.as<unsigned long long>(), P.words_max0);
-    });
-    if (e != 0) return fail(SMX_ERR_DEVICE, "pairs kernel launch failed: %s", hipGetErrorString((hipError_t)e));
-    if (kernel_ms) HIP_TRY(timer.stop(kernel_ms));
-    HIP_TRY(hipDeviceSynchronize());
+    SMX_TRY(timed_launches(kernel_ms, "pairs kernel launch", [&] {
+        return smx::chunk_for_each_class(P, [&](const smx::ChunkLaunch &L) {
+            return smx_launch_pairs(nullptr, L.wr, distances, W.reads.bytes.as<unsigned char>(), W.reads.doff.as<uint64_t>(),
+                                    W.reads.len.as<int32_t>(), W.k.as<int32_t>(), W.rows.as<smx::PairsRow>() + L.rec_at,
+                                    W.chunk_start.as<uint64_t>() + L.start_at, L.n, W.jobs_out.p, L.grid, L.per_block, L.lds,
+                                    d_out, W.scratch.as<unsigned long long>(), P.words_max0);
+        });
+    }));
     HIP_TRY(hipMemcpy(out, d_out, out_bytes, hipMemcpyDeviceToHost));
     if (!distances) smx::pairs_mirror(P, out);    // bit i of row j for every bit j > i of row i
     return SMX_OK;
@@ -258,7 +287,8 @@ int smx_pairs_neighbours(const char *reads, const uint64_t *roff, uint32_t n_rea
 namespace {
 struct {
     std::mutex mutex;
-    DevBuf seqs, doff, len, k, group, refs, runs, chunk_start, jobs;
+    DevSeqs seqs;
+    DevBuf k, group, refs, runs, chunk_start, jobs;
     DevBuf scratch;     // per-lane state of the generic class, one slice per workgroup
     DevBuf out;         // best_own then best_other, or the distances
 } g_nearest;
@@ -270,11 +300,9 @@ int nearest_call(bool distances, const char *seqs, const uint64_t *off, uint32_t
                  int32_t *dist, float *kernel_ms) {
     if (!seqs || !off || !k || !group || (n_jobs && (!jobs || (distances ? !dist : !own || !other))))
         return fail(SMX_ERR_ARG, "null argument");
-    // every check of the arguments comes before the device is touched
     smx::NearestPlan P;
     std::string why;
-    const int rc = smx::nearest_plan(seqs, off, n_seqs, jobs, n_jobs, &P, &why);
-    if (rc != SMX_OK) return fail(rc, "%s", why.c_str());
+    SMX_TRY(refused(smx::nearest_plan(seqs, off, n_seqs, jobs, n_jobs, &P, &why), why));
     std::lock_guard<std::mutex> guard(g_nearest.mutex);
     SMX_TRY(require_device());
     // G: the chunks a call should keep the device busy with, 32 per CU, or the test hook's figure
@@ -295,39 +323,30 @@ int nearest_call(bool distances, const char *seqs, const uint64_t *off, uint32_t
         if (!distances) { memset(own, 0xff, (size_t)P.n_best * 8); memset(other, 0xff, (size_t)P.n_best * 8); }
         return SMX_OK;
     }
-    std::vector<uint64_t> doff;
-    std::vector<int32_t> len;
-    std::vector<unsigned char> pad;
-    SMX_TRY(mine_targets(seqs, off, n_seqs, &doff, &len, &pad));
     auto &W = g_nearest;
-    HIP_TRY(W.seqs.upload(pad));
-    HIP_TRY(W.doff.upload(doff));
-    HIP_TRY(W.len.upload(len));
+    SMX_TRY(W.seqs.upload(seqs, off, n_seqs));
     HIP_TRY(W.k.upload(k, (size_t)n_seqs * 4));
     HIP_TRY(W.group.upload(group, (size_t)n_seqs * 4));
     HIP_TRY(W.refs.upload(P.refs));
     HIP_TRY(W.runs.upload(P.runs));
     HIP_TRY(W.chunk_start.upload(P.chunk_start));
     HIP_TRY(W.jobs.upload(P.jobs));
-    if (P.n_runs[0]) HIP_TRY(W.scratch.ensure((size_t)P.scratch_words * 8));
+    SMX_TRY(ensure_scratch(&W.scratch, P));
     HIP_TRY(W.out.ensure(out_bytes));
     // nearest: "no ref" until a lane says otherwise.  distances: every pair is written (nt > 0 and nq > 0 make runs)
     if (!distances) HIP_TRY(hipMemset(W.out.p, 0xff, out_bytes));
     unsigned long long *d_own = W.out.as<unsigned long long>(), *d_other = d_own + (distances ? 0 : P.n_best);
-    KernelTimer timer;
-    if (kernel_ms) HIP_TRY(timer.start());
     size_t ref_at[6] = {0, 0, 0, 0, 0, 0};             // every class's own ref list, one after the other
     for (int c = 1; c < 6; c++) ref_at[c] = ref_at[c - 1] + P.n_refs[c - 1];
-    const int e = smx::chunk_for_each_class(P.n_runs, [&](int c, int wr, uint32_t n, size_t rat, size_t cat) {
-        return smx_launch_nearest(nullptr, wr, distances, W.seqs.as<unsigned char>(), W.doff.as<uint64_t>(),
-                                  W.len.as<int32_t>(), W.k.as<int32_t>(), W.group.as<uint32_t>(), W.refs.as<uint32_t>() + ref_at[c],
-                                  W.runs.as<smx::NearestRun>() + rat, W.chunk_start.as<uint64_t>() + cat, n, W.jobs.p,
-                                  (int)P.grid[c], P.per_block[c], P.lds_max[c], d_own, d_other, W.out.as<int32_t>(),
-                                  W.scratch.as<unsigned long long>(), P.words_max0);
-    });
-    if (e != 0) return fail(SMX_ERR_DEVICE, "nearest kernel launch failed: %s", hipGetErrorString((hipError_t)e));
-    if (kernel_ms) HIP_TRY(timer.stop(kernel_ms));
-    HIP_TRY(hipDeviceSynchronize());
+    SMX_TRY(timed_launches(kernel_ms, "nearest kernel launch", [&] {
+        return smx::chunk_for_each_class(P, [&](const smx::ChunkLaunch &L) {
+            return smx_launch_nearest(nullptr, L.wr, distances, W.seqs.bytes.as<unsigned char>(), W.seqs.doff.as<uint64_t>(),
+                                      W.seqs.len.as<int32_t>(), W.k.as<int32_t>(), W.group.as<uint32_t>(),
+                                      W.refs.as<uint32_t>() + ref_at[L.c], W.runs.as<smx::NearestRun>() + L.rec_at,
+                                      W.chunk_start.as<uint64_t>() + L.start_at, L.n, W.jobs.p, L.grid, L.per_block, L.lds, d_own,
+                                      d_other, W.out.as<int32_t>(), W.scratch.as<unsigned long long>(), P.words_max0);
+        });
+    }));
     if (distances) {
         HIP_TRY(hipMemcpy(dist, W.out.p, out_bytes, hipMemcpyDeviceToHost));
     } else {
@@ -353,7 +372,8 @@ int smx_nearest_distances(const char *seqs, const uint64_t *off, uint32_t n_seqs
 namespace {
 struct {
     std::mutex mutex;
-    DevBuf seqs, doff, len, k, ord, recs, chunk_start, jobs;
+    DevSeqs seqs;
+    DevBuf k, ord, recs, chunk_start, jobs;
     DevBuf scratch;     // per-lane state of the generic class, one slice per workgroup
     DevBuf out;         // the keys, or the distances
 } g_hits;
@@ -363,11 +383,9 @@ int hits_call(bool distances, const char *seqs, const uint64_t *off, uint32_t n_
               const smx_hits_job *jobs, uint32_t n_jobs, uint32_t K, uint32_t min_cov_permille, uint64_t *keys, int32_t *dist,
               float *kernel_ms) {
     if (!seqs || !off || !k || (n_jobs && (!jobs || (distances ? !dist : !keys)))) return fail(SMX_ERR_ARG, "null argument");
-    // every check of the arguments comes before the device is touched
     smx::HitsPlan P;
     std::string why;
-    const int rc = smx::hits_plan(seqs, off, n_seqs, jobs, n_jobs, K, min_cov_permille, &P, &why);
-    if (rc != SMX_OK) return fail(rc, "%s", why.c_str());
+    SMX_TRY(refused(smx::hits_plan(seqs, off, n_seqs, jobs, n_jobs, K, min_cov_permille, &P, &why), why));
     std::lock_guard<std::mutex> guard(g_hits.mutex);
     SMX_TRY(require_device());
     if (kernel_ms) *kernel_ms = 0.0f;
@@ -379,34 +397,25 @@ int hits_call(bool distances, const char *seqs, const uint64_t *off, uint32_t n_
         memset(distances ? (void *)dist : (void *)keys, 0xff, out_bytes);
         return SMX_OK;
     }
-    std::vector<uint64_t> doff;
-    std::vector<int32_t> len;
-    std::vector<unsigned char> pad;
-    SMX_TRY(mine_targets(seqs, off, n_seqs, &doff, &len, &pad));
     auto &W = g_hits;
-    HIP_TRY(W.seqs.upload(pad));
-    HIP_TRY(W.doff.upload(doff));
-    HIP_TRY(W.len.upload(len));
+    SMX_TRY(W.seqs.upload(seqs, off, n_seqs));
     HIP_TRY(W.k.upload(k, (size_t)n_seqs * 4));
     HIP_TRY(W.ord.upload(P.ord));
     HIP_TRY(W.recs.upload(P.recs));
     HIP_TRY(W.chunk_start.upload(P.chunk_start));
     HIP_TRY(W.jobs.upload(P.jobs));
-    if (P.n_recs[0]) HIP_TRY(W.scratch.ensure((size_t)P.scratch_words * 8));
+    SMX_TRY(ensure_scratch(&W.scratch, P));
     HIP_TRY(W.out.ensure(out_bytes));
     HIP_TRY(hipMemset(W.out.p, 0xff, out_bytes));
-    KernelTimer timer;
-    if (kernel_ms) HIP_TRY(timer.start());
-    const int e = smx::chunk_for_each_class(P.n_recs, [&](int c, int wr, uint32_t n, size_t rat, size_t cat) {
-        return smx_launch_hits(nullptr, wr, distances, W.seqs.as<unsigned char>(), W.doff.as<uint64_t>(),
-                               W.len.as<int32_t>(), W.k.as<int32_t>(), W.ord.as<uint32_t>(), W.recs.as<smx::HitsRec>() + rat,
-                               W.chunk_start.as<uint64_t>() + cat, n, W.jobs.p, (int)P.grid[c], P.per_block[c], P.lds_max[c],
-                               (int)K, W.out.as<unsigned long long>(), W.out.as<int32_t>(), W.scratch.as<unsigned long long>(),
-                               P.words_max0);
-    });
-    if (e != 0) return fail(SMX_ERR_DEVICE, "hits kernel launch failed: %s", hipGetErrorString((hipError_t)e));
-    if (kernel_ms) HIP_TRY(timer.stop(kernel_ms));
-    HIP_TRY(hipDeviceSynchronize());
+    SMX_TRY(timed_launches(kernel_ms, "hits kernel launch", [&] {
+        return smx::chunk_for_each_class(P, [&](const smx::ChunkLaunch &L) {
+            return smx_launch_hits(nullptr, L.wr, distances, W.seqs.bytes.as<unsigned char>(), W.seqs.doff.as<uint64_t>(),
+                                   W.seqs.len.as<int32_t>(), W.k.as<int32_t>(), W.ord.as<uint32_t>(),
+                                   W.recs.as<smx::HitsRec>() + L.rec_at, W.chunk_start.as<uint64_t>() + L.start_at, L.n, W.jobs.p,
+                                   L.grid, L.per_block, L.lds, (int)K, W.out.as<unsigned long long>(), W.out.as<int32_t>(),
+                                   W.scratch.as<unsigned long long>(), P.words_max0);
+        });
+    }));
     HIP_TRY(hipMemcpy(distances ? (void *)dist : (void *)keys, W.out.p, out_bytes, hipMemcpyDeviceToHost));
     return SMX_OK;
 }
@@ -428,7 +437,8 @@ int smx_best_hits_distances(const char *seqs, const uint64_t *off, uint32_t n_se
 namespace {
 struct {
     std::mutex mutex;
-    DevBuf seqs, doff, len, weight, need, recs, chunk_start, jobs;
+    DevSeqs seqs;       // forwards, then reversed (reach_sequences); len per sequence
+    DevBuf weight, need, recs, chunk_start, jobs;
     DevBuf out;         // the keys, or the matrix
 } g_reach;
 
@@ -438,11 +448,9 @@ int reach_call(bool matrix, const char *seqs, const uint64_t *off, uint32_t n_se
                const uint32_t *need, const smx_reach_job *jobs, uint32_t n_jobs, uint32_t E, uint64_t *keys, uint32_t *reach,
                float *kernel_ms) {
     if (!seqs || !off || !weight || !need || (n_jobs && (!jobs || (matrix ? !reach : !keys)))) return fail(SMX_ERR_ARG, "null argument");
-    // every check of the arguments comes before the device is touched
     smx::ReachPlan P;
     std::string why;
-    int rc = smx::reach_plan(off, n_seqs, jobs, n_jobs, E, &P, &why);
-    if (rc != SMX_OK) return fail(rc, "%s", why.c_str());
+    SMX_TRY(refused(smx::reach_plan(off, n_seqs, jobs, n_jobs, E, &P, &why), why));
     std::lock_guard<std::mutex> guard(g_reach.mutex);
     SMX_TRY(require_device());
     if (kernel_ms) *kernel_ms = 0.0f;
@@ -456,12 +464,9 @@ int reach_call(bool matrix, const char *seqs, const uint64_t *off, uint32_t n_se
     }
     std::vector<uint64_t> doff;
     std::vector<unsigned char> pad;
-    rc = smx::reach_sequences(seqs, off, n_seqs, &doff, &pad, &why);
-    if (rc != SMX_OK) return fail(rc, "%s", why.c_str());
+    SMX_TRY(refused(smx::reach_sequences(seqs, off, n_seqs, &doff, &pad, &why), why));
     auto &W = g_reach;
-    HIP_TRY(W.seqs.upload(pad));
-    HIP_TRY(W.doff.upload(doff));
-    HIP_TRY(W.len.upload(P.len));
+    SMX_TRY(W.seqs.upload(pad, doff, P.len));
     HIP_TRY(W.weight.upload(weight, (size_t)n_seqs * 4));
     HIP_TRY(W.need.upload(need, (size_t)n_seqs * 4));
     HIP_TRY(W.recs.upload(P.recs));
@@ -469,15 +474,12 @@ int reach_call(bool matrix, const char *seqs, const uint64_t *off, uint32_t n_se
     HIP_TRY(W.jobs.upload(P.jobs));
     HIP_TRY(W.out.ensure(out_bytes));
     HIP_TRY(hipMemset(W.out.p, 0xff, out_bytes));
-    KernelTimer timer;
-    if (kernel_ms) HIP_TRY(timer.start());
-    const int e = smx_launch_reach(nullptr, matrix, W.seqs.as<unsigned char>(), W.doff.as<uint64_t>(), W.len.as<int32_t>(),
-                                   W.weight.as<uint32_t>(), W.need.as<uint32_t>(), W.recs.p, W.chunk_start.as<uint64_t>(),
-                                   (uint32_t)P.recs.size(), W.jobs.p, (int)P.grid, P.per_block, (int)E, n_seqs,
-                                   W.out.as<unsigned long long>(), W.out.as<uint32_t>());
-    if (e != 0) return fail(SMX_ERR_DEVICE, "reach kernel launch failed: %s", hipGetErrorString((hipError_t)e));
-    if (kernel_ms) HIP_TRY(timer.stop(kernel_ms));
-    HIP_TRY(hipDeviceSynchronize());
+    SMX_TRY(timed_launches(kernel_ms, "reach kernel launch", [&] {
+        return smx_launch_reach(nullptr, matrix, W.seqs.bytes.as<unsigned char>(), W.seqs.doff.as<uint64_t>(),
+                                W.seqs.len.as<int32_t>(), W.weight.as<uint32_t>(), W.need.as<uint32_t>(), W.recs.p,
+                                W.chunk_start.as<uint64_t>(), (uint32_t)P.recs.size(), W.jobs.p, (int)P.grid, P.per_block, (int)E,
+                                n_seqs, W.out.as<unsigned long long>(), W.out.as<uint32_t>());
+    }));
     HIP_TRY(hipMemcpy(matrix ? (void *)reach : (void *)keys, W.out.p, out_bytes, hipMemcpyDeviceToHost));
     return SMX_OK;
 }
@@ -499,7 +501,8 @@ int smx_prefix_reach_matrix(const char *seqs, const uint64_t *off, uint32_t n_se
 namespace {
 struct {
     std::mutex mutex;
-    DevBuf reads, doff, len, k, jobs, align, chunk_start;
+    DevSeqs reads;
+    DevBuf k, jobs, align, chunk_start;
     DevBuf scratch;             // per-lane state of the generic class, one slice per workgroup
     DevBuf hist_pm, hist_s;     // the alignment history, one slice per workgroup
     DevBuf rows, dist, votes, aligned;
@@ -534,7 +537,6 @@ int cons_call(const char *reads, const uint64_t *roff, uint32_t n_reads, const i
     if (phase && n_jobs && (!phase->sites || !phase->n_sites || !phase->n_qualified || !phase->planes || !phase->link))
         return fail(SMX_ERR_ARG, "null argument");
     if (resample && n_jobs && (!resample->agree || !resample->sub_aligned)) return fail(SMX_ERR_ARG, "null argument");
-    // every check of the arguments comes before the device is touched
     uint64_t hist_budget = smx::CONS_HIST_BYTES;
     if (const char *env = getenv("SMX_CONS_HIST_BYTES")) hist_budget = strtoull(env, nullptr, 10);   // test hook: few workgroups in flight
     smx::ConsPlan P;
@@ -542,36 +544,23 @@ int cons_call(const char *reads, const uint64_t *roff, uint32_t n_reads, const i
     int rc = smx::cons_plan(reads, roff, n_reads, k, jobs, n_jobs, hist_budget, &P, &why);
     if (rc == SMX_OK && phase) rc = smx::cons_plan_phase(phase->min_permille, phase->max_sites, &P, &why);
     if (rc == SMX_OK && resample) rc = smx::cons_plan_resample(resample->masks != nullptr, resample->n_levels, &P, &why);
-    if (rc != SMX_OK) return fail(rc, "%s", why.c_str());
+    SMX_TRY(refused(rc, why));
     if (kernel_ms) *kernel_ms = 0.0f;
-    if (n_jobs == 0) return SMX_OK;
+    if (n_jobs == 0) return SMX_OK;     // a call without jobs is answered without a device (the tests pin it): the one step out of order
     std::lock_guard<std::mutex> guard(g_cons.mutex);
     SMX_TRY(require_device());
-    std::vector<uint64_t> doff;
-    std::vector<int32_t> len;
-    std::vector<unsigned char> pad;
-    SMX_TRY(mine_targets(reads, roff, n_reads, &doff, &len, &pad));
     auto &W = g_cons;
-    HIP_TRY(W.reads.upload(pad));
-    HIP_TRY(W.doff.upload(doff));
-    HIP_TRY(W.len.upload(len));
+    SMX_TRY(W.reads.upload(reads, roff, n_reads));
     HIP_TRY(W.k.upload(k, (size_t)n_reads * 4));
     HIP_TRY(W.jobs.upload(P.jobs));
     HIP_TRY(W.align.upload(P.align));
     HIP_TRY(W.chunk_start.upload(P.chunk_start));
     HIP_TRY(W.rows.ensure((size_t)P.rows_words * 4));
     HIP_TRY(W.dist.ensure((size_t)P.n_dist * 4));
-    // runs of chunks per workgroup only where the history bounds the grid: a chunk is 128 alignments with traceback,
-    // and a call has few of them by the standards of the device
-    smx::ChunkGrid G[6];
-    uint64_t grid_max = 0;
-    for (int c = 0; c < 6; c++) {
-        G[c] = smx::chunk_grid(P.chunks[c], 1, P.grid_cap);
-        grid_max = std::max(grid_max, G[c].grid);
-    }
+    const uint64_t grid_max = P.grid_max();   // a history slice per workgroup of the largest launch
     HIP_TRY(W.hist_pm.ensure((size_t)(grid_max * P.hist_slice * MINE_THREADS * sizeof(smx::cons_pm))));
     HIP_TRY(W.hist_s.ensure((size_t)(grid_max * P.hist_slice * MINE_THREADS * sizeof(int))));
-    if (P.n_align[0]) HIP_TRY(W.scratch.ensure((size_t)smx::chunk_scratch_words(G[0].grid, P.words_max0) * 8));
+    SMX_TRY(ensure_scratch(&W.scratch, P));
     if (!pileup) {
         HIP_TRY(W.votes.ensure((size_t)P.votes_words * 4));
         HIP_TRY(W.aligned.ensure((size_t)n_jobs * 4));
@@ -591,32 +580,31 @@ int cons_call(const char *reads, const uint64_t *roff, uint32_t n_reads, const i
         HIP_TRY(W.agree.ensure((size_t)P.agree_off.back() * 8));
         HIP_TRY(W.sub_aligned.ensure((size_t)P.sub_words * 4));
     }
-    KernelTimer timer;
-    if (kernel_ms) HIP_TRY(timer.start());
-    int e = smx::chunk_for_each_class(P.n_align, [&](int c, int wr, uint32_t n, size_t jat, size_t cat) {
-        return smx_launch_cons_align(nullptr, wr, W.reads.as<unsigned char>(), W.doff.as<uint64_t>(), W.len.as<int32_t>(),
-                                     W.k.as<int32_t>(), W.align.as<smx::ConsJobDev>() + jat, W.chunk_start.as<uint64_t>() + cat,
-                                     n, (int)G[c].grid, G[c].per_block, P.lds_max[c], W.rows.as<uint32_t>(),
-                                     W.dist.as<int32_t>(), W.hist_pm.p, W.hist_s.as<int>(), P.hist_slice,
-                                     W.scratch.as<unsigned long long>(), P.words_max0);
-    });
-    if (e == 0 && !pileup)
-        e = smx_launch_cons_vote(nullptr, W.len.as<int32_t>(), W.jobs.p, n_jobs, P.max_words, W.rows.as<uint32_t>(),
-                                 W.dist.as<int32_t>(), W.votes.as<uint32_t>(), W.aligned.as<uint32_t>());
-    if (e == 0 && phase)
-        e = smx_launch_cons_phase(nullptr, W.len.as<int32_t>(), W.jobs.p, n_jobs, W.rows.as<uint32_t>(), W.dist.as<int32_t>(),
-                                  W.votes.as<uint32_t>(), W.aligned.as<uint32_t>(), phase->min_permille, phase->min_reads,
-                                  phase->max_sites, P.max_plane_words, W.planes_off.as<uint64_t>(), W.sites.p,
-                                  W.n_sites.as<uint32_t>(), W.n_qualified.as<uint32_t>(), W.planes.as<uint64_t>(),
-                                  W.link.as<uint32_t>());
-    if (e == 0 && resample)
-        e = smx_launch_cons_resample(nullptr, W.reads.as<unsigned char>(), W.doff.as<uint64_t>(), W.len.as<int32_t>(), W.jobs.p,
-                                     n_jobs, resample->n_levels, P.max_words, W.rows.as<uint32_t>(), W.dist.as<int32_t>(),
-                                     W.masks.as<uint64_t>(), W.member_off.as<uint64_t>(), W.agree_off.as<uint64_t>(),
-                                     P.member_off.back(), W.agree.as<uint64_t>(), W.sub_aligned.as<uint32_t>());
-    if (e != 0) return fail(SMX_ERR_DEVICE, "consensus kernel launch failed: %s", hipGetErrorString((hipError_t)e));
-    if (kernel_ms) HIP_TRY(timer.stop(kernel_ms));
-    HIP_TRY(hipDeviceSynchronize());
+    const int32_t *d_len = W.reads.len.as<int32_t>();
+    SMX_TRY(timed_launches(kernel_ms, "consensus kernel launch", [&] {
+        int e = smx::chunk_for_each_class(P, [&](const smx::ChunkLaunch &L) {
+            return smx_launch_cons_align(nullptr, L.wr, W.reads.bytes.as<unsigned char>(), W.reads.doff.as<uint64_t>(), d_len,
+                                         W.k.as<int32_t>(), W.align.as<smx::ConsJobDev>() + L.rec_at,
+                                         W.chunk_start.as<uint64_t>() + L.start_at, L.n, L.grid, L.per_block, L.lds,
+                                         W.rows.as<uint32_t>(), W.dist.as<int32_t>(), W.hist_pm.p, W.hist_s.as<int>(), P.hist_slice,
+                                         W.scratch.as<unsigned long long>(), P.words_max0);
+        });
+        if (e == 0 && !pileup)
+            e = smx_launch_cons_vote(nullptr, d_len, W.jobs.p, n_jobs, P.max_words, W.rows.as<uint32_t>(),
+                                     W.dist.as<int32_t>(), W.votes.as<uint32_t>(), W.aligned.as<uint32_t>());
+        if (e == 0 && phase)
+            e = smx_launch_cons_phase(nullptr, d_len, W.jobs.p, n_jobs, W.rows.as<uint32_t>(), W.dist.as<int32_t>(),
+                                      W.votes.as<uint32_t>(), W.aligned.as<uint32_t>(), phase->min_permille, phase->min_reads,
+                                      phase->max_sites, P.max_plane_words, W.planes_off.as<uint64_t>(), W.sites.p,
+                                      W.n_sites.as<uint32_t>(), W.n_qualified.as<uint32_t>(), W.planes.as<uint64_t>(),
+                                      W.link.as<uint32_t>());
+        if (e == 0 && resample)
+            e = smx_launch_cons_resample(nullptr, W.reads.bytes.as<unsigned char>(), W.reads.doff.as<uint64_t>(), d_len, W.jobs.p,
+                                         n_jobs, resample->n_levels, P.max_words, W.rows.as<uint32_t>(), W.dist.as<int32_t>(),
+                                         W.masks.as<uint64_t>(), W.member_off.as<uint64_t>(), W.agree_off.as<uint64_t>(),
+                                         P.member_off.back(), W.agree.as<uint64_t>(), W.sub_aligned.as<uint32_t>());
+        return e;
+    }));
     if (pileup) {
         if (P.n_dist) HIP_TRY(hipMemcpy(dist, W.dist.p, (size_t)P.n_dist * 4, hipMemcpyDeviceToHost));
         if (P.rows_words) HIP_TRY(hipMemcpy(rows, W.rows.p, (size_t)P.rows_words * 4, hipMemcpyDeviceToHost));
@@ -691,22 +679,19 @@ int inner_call(const char *patterns, const uint32_t *poff, uint32_t Q, const int
     // the pattern checks, lead / PL / RW, the table blob and the launch groups: smx_inner_plan.h
     smx::InnerPlan P;
     std::string why;
-    int rc = smx::inner_plan(patterns, poff, Q, k, margin, H, budget, smx::INNER_DEFAULT_BUDGET,
-                             smx::InnerAlphabet{code_of, build_peq}, &P, &why);
-    if (rc != SMX_OK) return fail(rc, "%s", why.c_str());
+    SMX_TRY(refused(smx::inner_plan(patterns, poff, Q, k, margin, H, budget, smx::INNER_DEFAULT_BUDGET,
+                                    smx::InnerAlphabet{code_of, build_peq}, &P, &why), why));
     std::lock_guard<std::mutex> guard(g_inner.mutex);
     SMX_TRY(require_device());
     if (kernel_ms) *kernel_ms = 0.0f;
     if (n_reads == 0) return SMX_OK;
     auto &W = g_inner;
     HIP_TRY(W.tables.upload(P.blob));
-    KernelTimer timer;
     smx::InnerGroup g;
     std::vector<unsigned char> stage, out;
     // groups of whole reads: everything one launch group keeps on the device fits the budget (one read always goes)
     for (uint32_t r0 = 0; r0 < n_reads; r0 = g.r1) {
-        rc = P.next_group(len, n_reads, r0, &g, &why);
-        if (rc != SMX_OK) return fail(rc, "%s", why.c_str());
+        SMX_TRY(refused(P.next_group(len, n_reads, r0, &g, &why), why));
         const uint32_t nr = g.nr();
         const unsigned char *src;
         if (flat) {
@@ -739,24 +724,20 @@ int inner_call(const char *patterns, const uint32_t *poff, uint32_t Q, const int
         int32_t *d_he = W.out.as<int32_t>();
         int8_t *d_hd = W.out.as<int8_t>() + g.he_bytes;
         uint8_t *d_nh = W.out.as<uint8_t>() + g.he_bytes + g.hd_bytes;
-        if (kernel_ms) HIP_TRY(timer.start());
-        int e = 0;
-        for (const smx::InnerClass &C : P.cls) {
-            if (C.idx.empty() || g.units == 0 || e != 0) continue;
-            A.peq = W.tables.as<char>() + C.peq_at;
-            A.pm = (const int *)(W.tables.as<char>() + C.tab_at);
-            A.pk = A.pm + C.slots();
-            A.jmap = A.pm + 2 * C.slots();
-            e = smx_launch_inner_scan(nullptr, C.w64, C.G, C.npass, &A);
-        }
-        if (e == 0) e = smx_launch_inner_merge(nullptr, &A, nr, d_nh, d_hd, d_he);
-        if (e != 0) return fail(SMX_ERR_DEVICE, "inner scan launch failed: %s", hipGetErrorString((hipError_t)e));
-        if (kernel_ms) {
-            float ms = 0.0f;
-            HIP_TRY(timer.stop(&ms));
-            *kernel_ms += ms;
-        }
-        HIP_TRY(hipDeviceSynchronize());
+        float ms = 0.0f;
+        SMX_TRY(timed_launches(kernel_ms ? &ms : nullptr, "inner scan launch", [&] {
+            int e = 0;
+            for (const smx::InnerClass &C : P.cls) {
+                if (C.idx.empty() || g.units == 0 || e != 0) continue;
+                A.peq = W.tables.as<char>() + C.peq_at;
+                A.pm = (const int *)(W.tables.as<char>() + C.tab_at);
+                A.pk = A.pm + C.slots();
+                A.jmap = A.pm + 2 * C.slots();
+                e = smx_launch_inner_scan(nullptr, C.w64, C.G, C.npass, &A);
+            }
+            return e ? e : smx_launch_inner_merge(nullptr, &A, nr, d_nh, d_hd, d_he);
+        }));
+        if (kernel_ms) *kernel_ms += ms;
         out.resize(g.out_bytes());
         HIP_TRY(hipMemcpy(out.data(), W.out.p, out.size(), hipMemcpyDeviceToHost));
         memcpy(hit_end + (size_t)r0 * Q * H, out.data(), g.he_bytes);

@@ -1,7 +1,8 @@
 // smx_chunk_plan.h -- what the host side of every chunked long-read call shares (specimine, clusters, consensus,
 // crosstalk, identify): the state class of a pattern, the LDS bytes of its Peq table, the grid of a
-// class's chunk list, the scratch of the generic class, the padded copy of the sequences and the walk over the classes
-// of a call.  The bimera call (smx_reach_plan.h) takes the grid and the padded copy from here and has no classes.
+// class's chunk list, the scratch of the generic class, the per-class launch table of a call (ChunkLaunches) with the
+// walk over its launches, the pattern classes of a sequence list and its padded copy.  The bimera call
+// (smx_reach_plan.h) takes the grid and the padded copy from here and has no classes.
 // Host only and free of HIP calls, like the plans that use it (smx_cons_plan.h, smx_nearest_plan.h,
 // smx_hits_plan.h, smx_reach_plan.h), so that the CPU simulations and the sanitizer drivers compile it as it is.
 #ifndef SMX_CHUNK_PLAN_H
@@ -71,15 +72,57 @@ inline uint64_t chunk_scratch_cap(int words_max0, uint64_t budget = CHUNK_SCRATC
 }
 inline uint64_t chunk_scratch_words(uint64_t grid0, int words_max0) { return grid0 * chunk_slice_words(words_max0); }
 
-// The grid of class c of a call: chunk_grid, the generic class's capped by its scratch as well.
-inline ChunkGrid chunk_class_grid(int c, uint64_t chunks, uint64_t floor, int words_max0, uint64_t budget = CHUNK_SCRATCH_BYTES) {
-    return chunk_grid(chunks, floor, c == 0 ? chunk_scratch_cap(words_max0, budget) : CHUNK_GRID_MAX);
-}
+// The launch table of a call: per state class its records (whatever the call's kernel walks: (job, query) pairs, rows,
+// runs, jobs), their chunk prefix and the launch that takes them.  The plan of a call is one (MinePlan, PairsPlan,
+// ConsPlan, NearestPlan and HitsPlan derive from it): it notes every pattern it will launch, appends its records class
+// after class, and seals the table once.
+struct ChunkLaunches {
+    uint32_t n[CHUNK_CLASSES] = {0, 0, 0, 0, 0, 0};              // records per class
+    std::vector<uint64_t> chunk_start;                           // per class with records: their chunk prefix, n + 1 entries
+    uint64_t chunks[CHUNK_CLASSES] = {0, 0, 0, 0, 0, 0};
+    uint64_t grid[CHUNK_CLASSES] = {0, 0, 0, 0, 0, 0};           // 0 for a class without records: nothing reads its per_block
+    uint64_t per_block[CHUNK_CLASSES] = {1, 1, 1, 1, 1, 1};
+    size_t lds_max[CHUNK_CLASSES] = {0, 0, 0, 0, 0, 0};          // the LDS bytes of the class's launch: its largest table
+    int words_max0 = 0;                    // the generic class's longest pattern, in words
+    uint64_t scratch_words = 0;            // u64 words of the generic class's state: grid[0] slices of 3 x words_max0 x lanes
 
-// Per query (specimine) or read (clusters, which allows empty ones): the LDS bytes of its Peq table and its state class.
-// Returns SMX_OK, or the status to fail with and why.
-inline int mine_queries(const char *queries, const uint64_t *qoff, uint32_t n_queries, bool allow_empty, std::vector<size_t> *qlds_out,
-                        std::vector<int> *qclass_out, std::string *why) {
+    // a pattern of class c that will be launched: the LDS bytes of its table (0: not known, a lengths-only plan) and its words
+    void note(int c, size_t lds, size_t W) {
+        lds_max[c] = std::max(lds_max[c], lds);
+        if (c == 0) words_max0 = std::max(words_max0, (int)W);
+    }
+    // a record of n_chunks chunks behind the records of class c; the classes are filled in ascending order
+    void append(int c, uint64_t n_chunks) {
+        if (!n[c]) chunk_start.push_back(0);
+        n[c]++;
+        chunks[c] += n_chunks;
+        chunk_start.push_back(chunks[c]);
+    }
+    // The grids: `floor` chunks per workgroup, more only where the grid is capped: by grid_cap and the launch, and in
+    // the generic class by the scratch slices of the workgroups in flight, which fit scratch_budget.
+    void seal(uint64_t floor, uint64_t scratch_budget = CHUNK_SCRATCH_BYTES, uint64_t grid_cap = CHUNK_GRID_MAX) {
+        for (int c = 0; c < CHUNK_CLASSES; c++) {
+            if (!n[c]) continue;
+            const uint64_t cap = c ? grid_cap : std::min(grid_cap, chunk_scratch_cap(words_max0, scratch_budget));
+            const ChunkGrid G = chunk_grid(chunks[c], floor, cap);
+            per_block[c] = G.per_block;
+            grid[c] = G.grid;
+        }
+        scratch_words = chunk_scratch_words(grid[0], words_max0);
+    }
+    // forget the records and their grids and keep the noted patterns: a plan that is given its records more than once
+    void clear_records() {
+        chunk_start.clear();
+        for (int c = 0; c < CHUNK_CLASSES; c++) { n[c] = 0; chunks[c] = 0; grid[c] = 0; per_block[c] = 1; }
+        scratch_words = 0;
+    }
+    uint64_t grid_max() const { return *std::max_element(grid, grid + CHUNK_CLASSES); }
+};
+
+// The pattern classes of a sequence list (specimine's queries; clusters' reads, which may be empty): per sequence the LDS
+// bytes of its Peq table and its state class.  Returns SMX_OK, or the status to fail with and why.
+inline int chunk_pattern_classes(const char *queries, const uint64_t *qoff, uint32_t n_queries, bool allow_empty,
+                                 std::vector<size_t> *qlds_out, std::vector<int> *qclass_out, std::string *why) {
     std::vector<size_t> &qlds = *qlds_out;
     std::vector<int> &qclass = *qclass_out;
     qlds.assign(n_queries, 0);
@@ -105,10 +148,11 @@ inline int mine_queries(const char *queries, const uint64_t *qoff, uint32_t n_qu
     return SMX_OK;
 }
 
-// The sequences as the kernels read them: 16-byte aligned copies, 16 bytes of slack at the end (a lane loads 16 bytes at
-// a time).  Returns SMX_OK, or the status to fail with and why.
-inline int mine_targets(const char *seqs, const uint64_t *off, uint32_t n_seqs, std::vector<uint64_t> *doff_out,
-                        std::vector<int32_t> *len_out, std::vector<unsigned char> *pad, std::string *why) {
+// The padded copy of a sequence list (reads, refs, drafts, databases alike), as the kernels read it: 16-byte aligned
+// copies, 16 bytes of slack at the end (a lane loads 16 bytes at a time).  Returns SMX_OK, or the status to fail with
+// and why.
+inline int chunk_padded_sequences(const char *seqs, const uint64_t *off, uint32_t n_seqs, std::vector<uint64_t> *doff_out,
+                                  std::vector<int32_t> *len_out, std::vector<unsigned char> *pad, std::string *why) {
     std::vector<uint64_t> &doff = *doff_out;
     std::vector<int32_t> &len = *len_out;
     doff.assign(n_seqs, 0);
@@ -130,15 +174,25 @@ inline int mine_targets(const char *seqs, const uint64_t *off, uint32_t n_seqs, 
 }
 
 // The launches of a call, class after class: the records of the classes lie one after the other, and so do their chunk
-// prefixes of n + 1 entries each.  launch(class, wr, n, record offset, chunk_start offset) runs for every class with
-// records; the walk ends at the first nonzero return, which it returns.
-template <typename F> inline int chunk_for_each_class(const uint32_t (&n)[CHUNK_CLASSES], F &&launch) {
-    size_t rat = 0, cat = 0;
+// prefixes of n + 1 entries each.  launch(ChunkLaunch) runs for every class with records; the walk ends at the first
+// nonzero return, which it returns.
+struct ChunkLaunch {
+    int c, wr;                 // the class and the wr of its launch
+    uint32_t n;                // its records,
+    size_t rec_at, start_at;   // where they and their chunk prefix begin in the call's lists
+    int grid;
+    uint64_t per_block;
+    size_t lds;
+};
+
+template <typename F> inline int chunk_for_each_class(const ChunkLaunches &L, F &&launch) {
+    size_t rec_at = 0, start_at = 0;
     for (int c = 0; c < CHUNK_CLASSES; c++) {
-        if (!n[c]) continue;
-        if (const int e = launch(c, CHUNK_CLASS_WORDS[c], n[c], rat, cat)) return e;
-        rat += n[c];
-        cat += (size_t)n[c] + 1;
+        if (!L.n[c]) continue;
+        const ChunkLaunch K{c, CHUNK_CLASS_WORDS[c], L.n[c], rec_at, start_at, (int)L.grid[c], L.per_block[c], L.lds_max[c]};
+        if (const int e = launch(K)) return e;
+        rec_at += L.n[c];
+        start_at += (size_t)L.n[c] + 1;
     }
     return 0;
 }

@@ -16,14 +16,9 @@ namespace smx {
 constexpr uint64_t CONS_HIST_BYTES = (uint64_t)2 << 30;      // the history workspace of the workgroups in flight, at most
 constexpr uint64_t CONS_HIST_ENTRY = sizeof(cons_pm) + sizeof(int);   // one block of one column of one lane
 
-struct ConsPlan {
+struct ConsPlan : ChunkLaunches {    // the launch table: the jobs of `align` per class (n), chunk_start, the grids, the scratch
     std::vector<ConsJobDev> jobs;          // the caller's jobs in the caller's order: what the vote kernel walks
     std::vector<ConsJobDev> align;         // the jobs with members, class after class (0 = generic, 1..5 = 1..16 words)
-    std::vector<uint64_t> chunk_start;     // per class with jobs: its jobs' chunk prefix, n + 1 entries
-    uint32_t n_align[6] = {0, 0, 0, 0, 0, 0};
-    uint64_t chunks[6] = {0, 0, 0, 0, 0, 0};
-    size_t lds_max[6] = {0, 0, 0, 0, 0, 0};
-    int words_max0 = 0;                    // the generic class's longest draft, in words
     uint64_t hist_slice = 0;               // history entries per lane of one workgroup
     uint64_t grid_cap = 1;                 // workgroups whose slices fit hist_budget
     uint64_t rows_words = 0, n_dist = 0, votes_words = 0;
@@ -100,8 +95,7 @@ inline int cons_plan(const char *reads, const uint64_t *roff, uint32_t n_reads, 
         P.max_words = std::max(P.max_words, (uint32_t)m + 1);
         if (J.n == 0) continue;
         P.hist_slice = std::max(P.hist_slice, (uint64_t)B * (uint64_t)cols);
-        P.lds_max[c] = std::max(P.lds_max[c], T.lds);
-        if (c == 0) P.words_max0 = std::max(P.words_max0, (int)T.W);
+        P.note(c, T.lds, T.W);
         by_class[c].push_back(j);
     }
     const uint64_t slice_bytes = P.hist_slice * MINE_THREADS * CONS_HIST_ENTRY;
@@ -112,17 +106,17 @@ inline int cons_plan(const char *reads, const uint64_t *roff, uint32_t n_reads, 
     }
     P.grid_cap = std::max<uint64_t>(1, hist_budget / std::max<uint64_t>(slice_bytes, 1));
     for (int c = 0; c < 6; c++) {
-        if (by_class[c].empty()) continue;
         // in draft order: a workgroup rebuilds the Peq table only when the draft changes
         std::stable_sort(by_class[c].begin(), by_class[c].end(), [&](uint32_t a, uint32_t b) { return jobs[a].draft < jobs[b].draft; });
-        P.n_align[c] = (uint32_t)by_class[c].size();
-        P.chunk_start.push_back(0);
         for (uint32_t j : by_class[c]) {
             P.align.push_back(P.jobs[j]);
-            P.chunks[c] += (P.jobs[j].n + MINE_THREADS - 1) / MINE_THREADS;
-            P.chunk_start.push_back(P.chunks[c]);
+            P.append(c, (P.jobs[j].n + MINE_THREADS - 1) / MINE_THREADS);
         }
     }
+    // runs of chunks per workgroup only where the history bounds the grid: a chunk is 128 alignments with traceback,
+    // and a call has few of them by the standards of the device.  Every class is capped by the history; the generic
+    // class's scratch has no budget of its own here (UINT64_MAX)
+    P.seal(1, UINT64_MAX, P.grid_cap);
     return SMX_OK;
 }
 

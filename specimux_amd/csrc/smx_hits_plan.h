@@ -22,18 +22,12 @@ namespace smx {
 
 constexpr uint64_t HITS_BLOCK_CHUNKS = 8;                       // chunks a workgroup takes in a row: specimine's, DESIGN.md §10
 
-struct HitsPlan {
+struct HitsPlan : ChunkLaunches {    // the launch table: the records per class (n), chunk_start, the grids, the scratch
     std::vector<HitsJobDev> jobs;          // the caller's jobs in the caller's order
     std::vector<int32_t> len;              // per sequence
     std::vector<uint32_t> ord;             // job after job its tord, then its qord: sequence indices
     std::vector<HitsRec> recs;             // class after class (0 = generic, 1..5 = 1..16 words), by pattern within a class
-    uint32_t n_recs[6] = {0, 0, 0, 0, 0, 0};
-    std::vector<uint64_t> chunk_start;     // per class with records: its records' chunk prefix, n + 1 entries
-    uint64_t chunks[6] = {0, 0, 0, 0, 0, 0};
-    uint64_t grid[6] = {0, 0, 0, 0, 0, 0}, per_block[6] = {1, 1, 1, 1, 1, 1};
-    size_t lds_max[6] = {0, 0, 0, 0, 0, 0};   // 0 everywhere after a lengths-only call
-    int words_max0 = 0;                    // the generic class's longest pattern, in words
-    uint64_t scratch_words = 0;            // u64 words of the generic class's state: grid[0] slices of 3 x words_max0 x lanes
+    // lds_max is 0 everywhere after a lengths-only call
     uint64_t n_rows = 0, n_dist = 0;       // sum(nq), sum(nq x nt)
     uint64_t n_pairs = 0;                  // sum of the records' n: the pairs the call aligns
 };
@@ -111,15 +105,16 @@ inline int hits_plan(const char *seqs, const uint64_t *off, uint32_t n_seqs, con
         }
         const size_t W = ((size_t)m + 63) / 64;
         const int c = chunk_class(W);
+        size_t lds = 0;
         if (seqs) {                                // the LDS its Peq table needs
             const ChunkTable T = chunk_table(seqs + off[r], (uint64_t)m);
             if (!T.fits()) {
                 *why = T.refusal("pattern " + std::to_string(r) + ": ");
                 return SMX_ERR_UNSUPPORTED;
             }
-            P.lds_max[c] = std::max(P.lds_max[c], T.lds);
+            lds = T.lds;
         }
-        if (c == 0) P.words_max0 = std::max(P.words_max0, (int)W);
+        P.note(c, lds, W);
         cls[r] = (signed char)c;
         *c_out = c;
         return SMX_OK;
@@ -166,21 +161,10 @@ inline int hits_plan(const char *seqs, const uint64_t *off, uint32_t n_seqs, con
     for (int c = 0; c < 6; c++) {
         // one pattern's records next to each other (a target shared by several jobs): its table is built once
         std::stable_sort(by_class[c].begin(), by_class[c].end(), [](const HitsRec &a, const HitsRec &b) { return a.pattern < b.pattern; });
-        P.n_recs[c] = (uint32_t)by_class[c].size();
-        if (by_class[c].empty()) continue;
-        P.chunk_start.push_back(0);
-        for (const HitsRec &R : by_class[c]) {
-            P.chunks[c] += ((uint64_t)R.n + MINE_THREADS - 1) / MINE_THREADS;
-            P.chunk_start.push_back(P.chunks[c]);
-        }
+        for (const HitsRec &R : by_class[c]) P.append(c, ((uint64_t)R.n + MINE_THREADS - 1) / MINE_THREADS);
         P.recs.insert(P.recs.end(), by_class[c].begin(), by_class[c].end());
-        // HITS_BLOCK_CHUNKS chunks per workgroup; more only where the grid is capped: by the launch, and in the generic
-        // class by the scratch slices of the workgroups in flight
-        const ChunkGrid G = chunk_class_grid(c, P.chunks[c], HITS_BLOCK_CHUNKS, P.words_max0);
-        P.per_block[c] = G.per_block;
-        P.grid[c] = G.grid;
     }
-    P.scratch_words = chunk_scratch_words(P.grid[0], P.words_max0);
+    P.seal(HITS_BLOCK_CHUNKS);
     return SMX_OK;
 }
 

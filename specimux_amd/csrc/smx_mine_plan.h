@@ -17,19 +17,12 @@ namespace smx {
 // 1.5x on runs of cheap (decoy) chunks, runs of 8 lose ~11 % to balance on costly chunks
 constexpr uint64_t MINE_BLOCK_CHUNKS = 8;
 
-struct MinePlan {
-    std::vector<uint64_t> tdoff;           // the targets as the kernel reads them (mine_targets)
+struct MinePlan : ChunkLaunches {    // the launch table: the pairs per class (n), chunk_start, the grids, the scratch
+    std::vector<uint64_t> tdoff;           // the targets as the kernel reads them (chunk_padded_sequences)
     std::vector<int32_t> tlen;
     std::vector<unsigned char> tpad;
     std::vector<MineJobDev> jobs;          // the caller's jobs in the caller's order, with their output offsets
     std::vector<MinePair> pairs;           // class after class (0 = generic, 1..5 = 1..16 words), by query within a class
-    uint32_t n_pairs[6] = {0, 0, 0, 0, 0, 0};
-    std::vector<uint64_t> chunk_start;     // per class with records: its records' chunk prefix, n + 1 entries
-    uint64_t chunks[6] = {0, 0, 0, 0, 0, 0};
-    uint64_t grid[6] = {0, 0, 0, 0, 0, 0}, per_block[6] = {1, 1, 1, 1, 1, 1};
-    size_t lds_max[6] = {0, 0, 0, 0, 0, 0};
-    int words_max0 = 0;                    // the generic class's longest query, in words
-    uint64_t scratch_words = 0;            // u64 words of the generic class's state: grid[0] slices of 3 x words_max0 x lanes
     uint64_t n_dist = 0, n_best = 0;       // sum(nq x nt), sum(nt): the output elements of the two modes
 };
 
@@ -42,9 +35,9 @@ inline int mine_plan(const char *queries, const uint64_t *qoff, uint32_t n_queri
     P = MinePlan();
     std::vector<size_t> qlds;
     std::vector<int> qclass;
-    int rc = mine_queries(queries, qoff, n_queries, false, &qlds, &qclass, why);
+    int rc = chunk_pattern_classes(queries, qoff, n_queries, false, &qlds, &qclass, why);
     if (rc != SMX_OK) return rc;
-    rc = mine_targets(targets, toff, n_targets, &P.tdoff, &P.tlen, &P.tpad, why);
+    rc = chunk_padded_sequences(targets, toff, n_targets, &P.tdoff, &P.tlen, &P.tpad, why);
     if (rc != SMX_OK) return rc;
     // jobs -> (job, query) pairs with at least one target, grouped by register class, in query order within a class
     // (a workgroup rebuilds the Peq table only when the query changes)
@@ -63,30 +56,18 @@ inline int mine_plan(const char *queries, const uint64_t *qoff, uint32_t n_queri
         for (uint32_t i = 0; i < J.nq; i++) {
             const uint32_t q = J.q0 + i;
             const int c = qclass[q];
-            P.lds_max[c] = std::max(P.lds_max[c], qlds[q]);
-            if (c == 0) P.words_max0 = std::max(P.words_max0, (int)((qoff[q + 1] - qoff[q] + 63) / 64));
+            P.note(c, qlds[q], (size_t)((qoff[q + 1] - qoff[q] + 63) / 64));
             pairs[c].push_back(MinePair{j, q, k[q], 0});
         }
     }
     for (int c = 0; c < 6; c++) {
         std::stable_sort(pairs[c].begin(), pairs[c].end(), [](const MinePair &a, const MinePair &b) { return a.q < b.q; });
-        P.n_pairs[c] = (uint32_t)pairs[c].size();
-        if (pairs[c].empty()) continue;
-        P.chunk_start.push_back(0);
-        for (const MinePair &R : pairs[c]) {
-            P.chunks[c] += ((uint64_t)P.jobs[R.job].nt + MINE_THREADS - 1) / MINE_THREADS;
-            P.chunk_start.push_back(P.chunks[c]);
-        }
+        for (const MinePair &R : pairs[c]) P.append(c, ((uint64_t)P.jobs[R.job].nt + MINE_THREADS - 1) / MINE_THREADS);
         P.pairs.insert(P.pairs.end(), pairs[c].begin(), pairs[c].end());
     }
     // MINE_BLOCK_CHUNKS chunks per workgroup; more only where the grid is capped: by the launch, and in the generic class by
     // the scratch slices of the workgroups in flight
-    for (int c = 0; c < 6; c++) {
-        const ChunkGrid G = chunk_class_grid(c, P.chunks[c], MINE_BLOCK_CHUNKS, P.words_max0, scratch_budget);
-        P.per_block[c] = G.per_block;
-        P.grid[c] = G.grid;
-    }
-    P.scratch_words = P.n_pairs[0] ? chunk_scratch_words(P.grid[0], P.words_max0) : 0;
+    P.seal(MINE_BLOCK_CHUNKS, scratch_budget);
     return SMX_OK;
 }
 

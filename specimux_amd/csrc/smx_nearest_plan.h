@@ -15,19 +15,12 @@ namespace smx {
 
 constexpr uint64_t NEAREST_CHUNKS_PER_CU = 32;                    // G = this x the CU count: measured, DESIGN.md §16
 
-struct NearestPlan {
+struct NearestPlan : ChunkLaunches {    // the launch table: the runs per class (n), chunk_start, the grids, the scratch
     std::vector<NearestJobDev> jobs;       // the caller's jobs in the caller's order
     std::vector<int32_t> len;              // per sequence
     std::vector<uint32_t> refs;            // the sequences some job takes as refs, class after class (0 = generic,
     uint32_t n_refs[6] = {0, 0, 0, 0, 0, 0};   // 1..5 = 1..16 words), in index order within a class
     std::vector<NearestRun> runs;          // class after class; first / n index the class's own ref list
-    uint32_t n_runs[6] = {0, 0, 0, 0, 0, 0};
-    std::vector<uint64_t> chunk_start;     // per class with runs: its runs' chunk prefix, n + 1 entries
-    uint64_t chunks[6] = {0, 0, 0, 0, 0, 0};
-    uint64_t grid[6] = {0, 0, 0, 0, 0, 0}, per_block[6] = {1, 1, 1, 1, 1, 1};
-    size_t lds_max[6] = {0, 0, 0, 0, 0, 0};
-    int words_max0 = 0;                    // the generic class's longest ref, in words
-    uint64_t scratch_words = 0;            // u64 words of the generic class's state: grid[0] slices of 3 x words_max0 x lanes
     uint64_t run_len = 1;                  // the run length chosen: a (job, class) of n refs has ceil(n / run_len) runs
     uint64_t n_best = 0, n_dist = 0;       // sum(nt), sum(nq x nt)
     struct Slice { uint32_t job, lo, n; }; // a job's refs of one class: refs [lo, lo + n) of the class's list
@@ -88,8 +81,7 @@ inline int nearest_plan(const char *seqs, const uint64_t *off, uint32_t n_seqs, 
             return SMX_ERR_UNSUPPORTED;
         }
         const int c = T.cls;
-        P.lds_max[c] = std::max(P.lds_max[c], T.lds);
-        if (c == 0) P.words_max0 = std::max(P.words_max0, (int)T.W);
+        P.note(c, T.lds, T.W);
         by_class[c].push_back(r);
     }
     // per (job, class) the job's refs are a slice of the class list
@@ -116,8 +108,7 @@ inline int nearest_plan(const char *seqs, const uint64_t *off, uint32_t n_seqs, 
 inline void nearest_plan_runs(NearestPlan *plan, uint64_t min_chunks) {
     NearestPlan &P = *plan;
     P.runs.clear();                                // a plan may be given its runs more than once (the tests do)
-    P.chunk_start.clear();
-    for (int c = 0; c < 6; c++) { P.n_runs[c] = 0; P.chunks[c] = 0; P.grid[c] = 0; P.per_block[c] = 1; }
+    P.clear_records();                    // the refs nearest_plan noted stay
     uint64_t longest = 1;
     for (int c = 0; c < 6; c++)
         for (const NearestPlan::Slice &S : P.slices[c]) longest = std::max<uint64_t>(longest, S.n);
@@ -136,8 +127,6 @@ inline void nearest_plan_runs(NearestPlan *plan, uint64_t min_chunks) {
     }
     P.run_len = lo_len;
     for (int c = 0; c < 6; c++) {
-        if (P.slices[c].empty()) continue;
-        P.chunk_start.push_back(0);
         for (const NearestPlan::Slice &S : P.slices[c]) {
             const uint64_t per_run = ((uint64_t)P.jobs[S.job].nt + MINE_THREADS - 1) / MINE_THREADS;
             const uint32_t n_runs = (uint32_t)((S.n + P.run_len - 1) / P.run_len);
@@ -147,18 +136,11 @@ inline void nearest_plan_runs(NearestPlan *plan, uint64_t min_chunks) {
                 const uint32_t n = base + (r < rem ? 1 : 0);
                 P.runs.push_back(NearestRun{S.job, at, n});
                 at += n;
-                P.chunks[c] += per_run;
-                P.chunk_start.push_back(P.chunks[c]);
+                P.append(c, per_run);
             }
-            P.n_runs[c] += n_runs;
         }
-        // one chunk per workgroup; several only where the grid is capped: by the launch, and in the generic class by
-        // the scratch slices of the workgroups in flight
-        const ChunkGrid G = chunk_class_grid(c, P.chunks[c], 1, P.words_max0);
-        P.per_block[c] = G.per_block;
-        P.grid[c] = G.grid;
     }
-    P.scratch_words = chunk_scratch_words(P.grid[0], P.words_max0);
+    P.seal(1);                            // one chunk per workgroup; several only where the grid is capped
 }
 
 }  // namespace smx

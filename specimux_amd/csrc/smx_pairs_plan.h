@@ -15,20 +15,13 @@ namespace smx {
 
 constexpr uint64_t PAIRS_BLOCK_CHUNKS = 8;     // chunks a workgroup takes in a row: specimine's, DESIGN.md §10
 
-struct PairsPlan {
+struct PairsPlan : ChunkLaunches {    // the launch table: the rows per class (n), chunk_start, the grids, the scratch
     bool distances = true;                 // the mode the output was planned for
-    std::vector<uint64_t> doff;            // the reads as the kernel reads them (mine_targets)
+    std::vector<uint64_t> doff;            // the reads as the kernel reads them (chunk_padded_sequences)
     std::vector<int32_t> len;
     std::vector<unsigned char> pad;
     std::vector<PairsJobDev> jobs;         // the caller's jobs in the caller's order, with their output offsets
     std::vector<PairsRow> rows;            // class after class (0 = generic, 1..5 = 1..16 words), in read order within a class
-    uint32_t n_rows[6] = {0, 0, 0, 0, 0, 0};
-    std::vector<uint64_t> chunk_start;     // per class with rows: its rows' chunk prefix, n + 1 entries
-    uint64_t chunks[6] = {0, 0, 0, 0, 0, 0};
-    uint64_t grid[6] = {0, 0, 0, 0, 0, 0}, per_block[6] = {1, 1, 1, 1, 1, 1};
-    size_t lds_max[6] = {0, 0, 0, 0, 0, 0};
-    int words_max0 = 0;                    // the generic class's longest row read, in words
-    uint64_t scratch_words = 0;            // u64 words of the generic class's state: grid[0] slices of 3 x words_max0 x lanes
     // 32-bit words of the output: per job n (n - 1) / 2 distances, or n x ceil(n / 32) adjacency words (a job of one
     // read has a zero word, and no row)
     uint64_t n_out = 0;
@@ -43,9 +36,9 @@ inline int pairs_plan(bool distances, const char *reads, const uint64_t *roff, u
     P.distances = distances;
     std::vector<size_t> qlds;
     std::vector<int> qclass;
-    int rc = mine_queries(reads, roff, n_reads, true, &qlds, &qclass, why);
+    int rc = chunk_pattern_classes(reads, roff, n_reads, true, &qlds, &qclass, why);
     if (rc != SMX_OK) return rc;
-    rc = mine_targets(reads, roff, n_reads, &P.doff, &P.len, &P.pad, why);
+    rc = chunk_padded_sequences(reads, roff, n_reads, &P.doff, &P.len, &P.pad, why);
     if (rc != SMX_OK) return rc;
     // the jobs' ranges may not overlap: every read is a row of at most one matrix
     std::vector<uint32_t> order;
@@ -72,29 +65,19 @@ inline int pairs_plan(bool distances, const char *reads, const uint64_t *roff, u
         for (uint32_t i = 0; i + 1 < n; i++) {
             const uint32_t r = jobs[j].r0 + i;
             const int c = qclass[r];
-            P.lds_max[c] = std::max(P.lds_max[c], qlds[r]);
-            if (c == 0) P.words_max0 = std::max(P.words_max0, (P.len[r] + 63) / 64);
+            P.note(c, qlds[r], (size_t)(P.len[r] + 63) / 64);
             rows[c].push_back(PairsRow{j, r});
         }
     }
     for (int c = 0; c < 6; c++) {
-        P.n_rows[c] = (uint32_t)rows[c].size();
-        if (rows[c].empty()) continue;
-        P.chunk_start.push_back(0);
         for (const PairsRow &R : rows[c]) {
             // the row's first chunk is the one that holds j = i + 1; chunks are aligned in j
             const uint32_t n = P.jobs[R.job].n, i = R.read - P.jobs[R.job].r0;
-            P.chunks[c] += ((uint64_t)n + MINE_THREADS - 1) / MINE_THREADS - (i + 1) / MINE_THREADS;
-            P.chunk_start.push_back(P.chunks[c]);
+            P.append(c, ((uint64_t)n + MINE_THREADS - 1) / MINE_THREADS - (i + 1) / MINE_THREADS);
         }
         P.rows.insert(P.rows.end(), rows[c].begin(), rows[c].end());
     }
-    for (int c = 0; c < 6; c++) {
-        const ChunkGrid G = chunk_class_grid(c, P.chunks[c], PAIRS_BLOCK_CHUNKS, P.words_max0, scratch_budget);
-        P.per_block[c] = G.per_block;
-        P.grid[c] = G.grid;
-    }
-    P.scratch_words = P.n_rows[0] ? chunk_scratch_words(P.grid[0], P.words_max0) : 0;
+    P.seal(PAIRS_BLOCK_CHUNKS, scratch_budget);
     return SMX_OK;
 }
 

@@ -98,7 +98,7 @@ inline int reach_plan(const uint64_t *off, uint32_t n_seqs, const smx_reach_job 
 }
 
 // The sequences as the kernel reads them: sequence s forwards at index s and reversed at index n_seqs + s of one padded
-// copy (mine_targets: 16-byte aligned, 16 bytes of slack at the end), so that the right side is the left side's code
+// copy (chunk_padded_sequences: 16-byte aligned, 16 bytes of slack at the end), so that the right side is the left side's code
 // over other bytes.  doff receives 2 n_seqs offsets.
 inline int reach_sequences(const char *seqs, const uint64_t *off, uint32_t n_seqs, std::vector<uint64_t> *doff,
                            std::vector<unsigned char> *pad, std::string *why) {
@@ -117,7 +117,7 @@ inline int reach_sequences(const char *seqs, const uint64_t *off, uint32_t n_seq
     }
     off2[(size_t)n_seqs * 2] = total * 2;
     std::vector<int32_t> len2;
-    return mine_targets(both.data(), off2.data(), n_seqs * 2, doff, &len2, pad, why);
+    return chunk_padded_sequences(both.data(), off2.data(), n_seqs * 2, doff, &len2, pad, why);
 }
 
 }  // namespace smx

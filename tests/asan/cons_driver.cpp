@@ -10,6 +10,7 @@
 #include <string>
 #include <vector>
 
+#include "../cpu/chunk_walk_host.h"   // chunk_with_wr
 #include "smx_cons_plan.h"
 
 using namespace smx;
@@ -125,7 +126,7 @@ int main() {
     size_t n_chunks = 0, at = 0;
     for (int c = 0; c < 6; c++) {
         n_chunks += P.chunks[c];
-        if (P.n_align[c]) at += P.n_align[c] + 1;
+        if (P.n[c]) at += P.n[c] + 1;
     }
     if (at != P.chunk_start.size() || P.align.size() + 1 != jobs.size()) die("the class lists do not add up");
     long long aligned = 0, checksum = 0;
@@ -140,15 +141,8 @@ int main() {
             const int k = (R.k[J.draft] < 0 || R.k[r] < 0) ? -1 : std::max(R.k[J.draft], R.k[r]);
             const ConsHist H{hpm.data() + lane, hs.data() + lane, (int)J.B};
             uint32_t *row = rows.data() + J.rows_off + (size_t)i * (Q.m + 1);
-            int d;
-            switch (CHUNK_CLASS_WORDS[chunk_class((size_t)Q.W)]) {
-                case 1: d = pair_in_class<1>(H, Q, k, t, n, row, sP, sM, sS, lane); break;
-                case 2: d = pair_in_class<2>(H, Q, k, t, n, row, sP, sM, sS, lane); break;
-                case 4: d = pair_in_class<4>(H, Q, k, t, n, row, sP, sM, sS, lane); break;
-                case 8: d = pair_in_class<8>(H, Q, k, t, n, row, sP, sM, sS, lane); break;
-                case 16: d = pair_in_class<16>(H, Q, k, t, n, row, sP, sM, sS, lane); break;
-                default: d = pair_in_class<0>(H, Q, k, t, n, row, sP, sM, sS, lane); break;
-            }
+            const int d = chunk_with_wr(CHUNK_CLASS_WORDS[chunk_class((size_t)Q.W)],
+                                        [&](auto WR) { return pair_in_class<WR>(H, Q, k, t, n, row, sP, sM, sS, lane); });
             dist[J.dist_off + i] = d;
             if (d < 0) continue;
             aligned++;

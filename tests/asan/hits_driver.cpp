@@ -112,8 +112,8 @@ int main() {
             if (plan(jobs, (uint32_t)K, cov) != SMX_OK) die(why.c_str());
             size_t at = 0, n_recs = 0;
             for (int c = 0; c < 6; c++) {
-                n_recs += P.n_recs[c];
-                if (P.n_recs[c]) at += P.n_recs[c] + 1;
+                n_recs += P.n[c];
+                if (P.n[c]) at += P.n[c] + 1;
             }
             if (at != P.chunk_start.size() || n_recs != P.recs.size()) die("the class lists do not add up");
             // buffers of exactly the planned sizes

@@ -107,8 +107,8 @@ int main() {
         nearest_plan_runs(&P, G);
         size_t at = 0, n_runs = 0;
         for (int c = 0; c < 6; c++) {
-            n_runs += P.n_runs[c];
-            if (P.n_runs[c]) at += P.n_runs[c] + 1;
+            n_runs += P.n[c];
+            if (P.n[c]) at += P.n[c] + 1;
         }
         if (at != P.chunk_start.size() || n_runs != P.runs.size()) die("the class lists do not add up");
         // buffers of exactly the planned sizes

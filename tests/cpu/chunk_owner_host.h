@@ -1,7 +1,8 @@
-// chunk_owner (specimux_amd/csrc/smx_mine_lds.h) over 64 emulated lanes: the same chunk_owner_step / _probe / _advance /
-// _left (smx_mine_core.h) the device function runs, with the wave's ballot built lane by lane.  The host twins of the
-// chunked kernels (mine_host.h, pairs_host.h) find a workgroup's first record with it and check it against
-// std::upper_bound; a probe outside the prefix's n + 1 entries is then an overflow of the buffer the caller handed in.
+// chunk_owner (specimux_amd/csrc/smx_mine_lds.h) over 64 emulated lanes: the same chunk_owner_step / _probe / _advance
+// / _left (smx_mine_core.h) the device function runs, with the wave's ballot built lane by lane. The host twins of the
+// chunked kernels (through chunk_walk_host.h; reach_host.h directly) find a workgroup's first record with it and check
+// it against std::upper_bound; a probe outside the prefix's n + 1 entries is then an overflow of the buffer the caller
+// handed in.
 #ifndef SMX_TESTS_CHUNK_OWNER_HOST_H
 #define SMX_TESTS_CHUNK_OWNER_HOST_H
 #include <algorithm>

@@ -20,7 +20,7 @@
 #include <string>
 #include <vector>
 
-#include "smx_chunk_plan.h"   // chunk_class: the state class a call gives a draft
+#include "chunk_walk_host.h"   // chunk_with_wr; smx_chunk_plan.h: chunk_class, the state class a call gives a draft
 #include "smx_cons_core.h"
 
 using namespace smx;
@@ -118,13 +118,11 @@ struct Sim {
             for (size_t i = old; i < need; i++) { hPM[i] = cons_pm{rng(), rng()}; hS[i] = (int)(rng() >> 40); }
         }
         const ConsHist H{hPM.data() + lane, hS.data() + lane, B};
-        switch (wr) {
-            case 1: { RegState<1> st; return cons_pair<1>(st, H, Q.peq.data(), Q.rowmap, Q.m, Q.W, Q.Wp, k, t, n, row); }
-            case 2: { RegState<2> st; return cons_pair<2>(st, H, Q.peq.data(), Q.rowmap, Q.m, Q.W, Q.Wp, k, t, n, row); }
-            case 4: { RegState<4> st; return cons_pair<4>(st, H, Q.peq.data(), Q.rowmap, Q.m, Q.W, Q.Wp, k, t, n, row); }
-            case 8: { RegState<8> st; return cons_pair<8>(st, H, Q.peq.data(), Q.rowmap, Q.m, Q.W, Q.Wp, k, t, n, row); }
-            case 16: { RegState<16> st; return cons_pair<16>(st, H, Q.peq.data(), Q.rowmap, Q.m, Q.W, Q.Wp, k, t, n, row); }
-            default: {
+        return chunk_with_wr(wr, [&](auto WR) {
+            if constexpr (WR > 0) {
+                RegState<WR> st;
+                return cons_pair<WR>(st, H, Q.peq.data(), Q.rowmap, Q.m, Q.W, Q.Wp, k, t, n, row);
+            } else {
                 const size_t sneed = (size_t)std::max(Q.W, 1) * MINE_THREADS;
                 if (sP.size() < sneed) {
                     const size_t old = sP.size();
@@ -134,7 +132,7 @@ struct Sim {
                 GlobalState st{sP.data() + lane, sM.data() + lane, sS.data() + lane};
                 return cons_pair<0>(st, H, Q.peq.data(), Q.rowmap, Q.m, Q.W, Q.Wp, k, t, n, row);
             }
-        }
+        });
     }
 
     // what a row must satisfy by itself: replayed on the draft it rebuilds the read (no insertion longer than the

@@ -16,7 +16,7 @@
 #include <string>
 #include <vector>
 
-#include "smx_chunk_plan.h"   // chunk_class: the state class a call gives a query
+#include "chunk_walk_host.h"   // chunk_with_wr; smx_chunk_plan.h: chunk_class, the state class a call gives a query
 #include "smx_mine_core.h"
 
 using namespace smx;
@@ -81,13 +81,11 @@ struct Sim {
     explicit Sim(uint64_t seed) : rng(seed) {}
 
     int run_pair(int wr, const Query &Q, const unsigned char *t, int n, int k) {
-        switch (wr) {
-            case 1: { RegState<1> st; return mine_pair<1>(st, Q.peq.data(), Q.rowmap, Q.m, Q.W, Q.Wp, k, t, n); }
-            case 2: { RegState<2> st; return mine_pair<2>(st, Q.peq.data(), Q.rowmap, Q.m, Q.W, Q.Wp, k, t, n); }
-            case 4: { RegState<4> st; return mine_pair<4>(st, Q.peq.data(), Q.rowmap, Q.m, Q.W, Q.Wp, k, t, n); }
-            case 8: { RegState<8> st; return mine_pair<8>(st, Q.peq.data(), Q.rowmap, Q.m, Q.W, Q.Wp, k, t, n); }
-            case 16: { RegState<16> st; return mine_pair<16>(st, Q.peq.data(), Q.rowmap, Q.m, Q.W, Q.Wp, k, t, n); }
-            default: {
+        return chunk_with_wr(wr, [&](auto WR) {
+            if constexpr (WR > 0) {
+                RegState<WR> st;
+                return mine_pair<WR>(st, Q.peq.data(), Q.rowmap, Q.m, Q.W, Q.Wp, k, t, n);
+            } else {
                 const size_t need = (size_t)Q.W * MINE_THREADS;
                 if (sP.size() < need) {   // grow with junk: the kernel's scratch is never initialised either
                     const size_t old = sP.size();
@@ -98,7 +96,7 @@ struct Sim {
                 GlobalState st{sP.data() + lane, sM.data() + lane, sS.data() + lane};
                 return mine_pair<0>(st, Q.peq.data(), Q.rowmap, Q.m, Q.W, Q.Wp, k, t, n);
             }
-        }
+        });
     }
 
     // one (query, target) with every k of ks against the unlimited DP distance d

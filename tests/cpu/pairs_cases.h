@@ -167,7 +167,7 @@ inline void pairs_case_run(const PairsCase &C, int budget_kind, const std::map<s
 inline void pairs_case_print(const PairsCaseTotals &T) {
     printf("plans %lld\ncapped_plans %lld\npairs %lld\nchunks %lld\nbuilds %lld\nblocks %lld\nrows %lld\nrows_late %lld\nword_stores %lld\n"
            "words_guarded %lld\nblocks_inside %lld\nowner_rounds_max %lld\ncompared %lld\nwithin %lld\nbeyond %lld\nneighbours %lld\n",
-           T.plans, T.capped_plans, T.H.pairs, T.H.chunks, T.H.builds, T.H.blocks, T.H.rows, T.H.rows_late, T.HA.word_stores,
+           T.plans, T.capped_plans, T.H.pairs, T.H.chunks, T.H.builds, T.H.blocks, T.H.records, T.H.rows_late, T.HA.word_stores,
            T.HA.words_guarded, T.H.blocks_inside, T.H.owner_rounds_max, T.compared, T.within, T.beyond, T.neighbours);
     for (int c = 0; c < 6; c++) printf("class_pairs_%d %lld\n", c, T.H.class_pairs[c]);
     printf("%lld mismatches\n", T.mismatches);

@@ -10,6 +10,7 @@
 #include <cstring>
 #include <vector>
 
+#include "chunk_owner_host.h"
 #include "smx_reach_plan.h"
 
 namespace smx {
@@ -83,8 +84,7 @@ inline void reach_host_run(const ReachPlan &P, const ReachHostSeqs &S, uint32_t 
     const uint64_t per_block = P.per_block, n_chunks = chunk_start[n_recs];
     for (uint64_t block = 0; block < P.grid; block++) {
         const uint64_t lo = block * per_block, hi = lo + per_block < n_chunks ? lo + per_block : n_chunks;
-        // the record that owns lo, as chunk_owner finds it: the last p with chunk_start[p] <= lo
-        uint32_t p = (uint32_t)(std::upper_bound(chunk_start, chunk_start + n_recs, lo) - chunk_start) - 1;
+        uint32_t p = chunk_owner_host(chunk_start, n_recs, lo);    // the 64-lane search, checked against std::upper_bound
         for (uint64_t v = lo; v < hi; v++) {
             while (chunk_start[p + 1] <= v) p++;
             const ReachRec R = P.recs[p];

@@ -48,3 +48,41 @@ def test_the_shapes_reach_every_class_and_the_chunk_walk(counts):
 def test_owner_search_takes_up_to_four_rounds(counts):
     # prefixes of 1 .. 300 001 records: the 64-lane search against std::upper_bound, a fourth round from 262 145 records on
     assert counts["owner_sweep_rounds"] == 4 and counts["owner_sweep_searches"] > 5000
+
+
+def test_bad_calls_are_refused_before_the_device_is_asked():
+    """Every refusal of a specimine call is host code alone (smx_mine_plan.h), for both entry points: on a machine
+    without a GPU the same call with good jobs is the one that fails, with SMX_ERR_DEVICE.  A refused call leaves
+    kernel_ms alone."""
+    import numpy as np
+    import torch
+    from specimux_amd import _lib, calls
+    lib = _lib.load()
+    good_q, good_t = [b"ACGTACGT", b"ACGAACG"], [b"TTACGTACGTTT", b"ACGAACGT", b"GGGG"]
+    wide = bytes(range(256)) * 19 + bytes(64)          # 4928 bytes, 77 words x 256 distinct bytes: more than the LDS holds
+
+    def call(best, queries, targets, jobs, toff=None):
+        qoff, toff = calls.offsets(queries), calls.offsets(targets) if toff is None else np.array(toff, dtype=np.uint64)
+        ks = np.full(len(queries), 3, dtype=np.int32)
+        jarr = np.array(jobs, dtype=_lib.MINE_JOB_DTYPE)
+        out = np.zeros(64, dtype=np.float64 if best else np.int32)
+        ms = _lib.C.c_float(-1.0)
+        fn = lib.smx_mine_best_identity if best else lib.smx_mine_distances
+        rc = fn(b"".join(queries), _lib.ptr(qoff), len(queries), _lib.ptr(ks), b"".join(targets), _lib.ptr(toff), len(targets),
+                _lib.ptr(jarr), len(jobs), _lib.ptr(out), _lib.C.byref(ms))
+        return rc, lib.smx_last_error().decode(), ms.value
+    for best in (False, True):
+        for queries, jobs, toff, code, word in (
+                ([b"ACGT", b""], [(0, 1, 0, 3, 0.5)], None, _lib.ERR_ARG, "query 1 is empty"),
+                (good_q, [(1, 2, 0, 3, 0.5)], None, _lib.ERR_ARG, "out of bounds"),
+                (good_q, [(0, 2, 2, 2, 0.5)], None, _lib.ERR_ARG, "out of bounds"),
+                (good_q, [(0, 2, 0, 3, 0.5)], [0, 12, 8, 24], _lib.ERR_ARG, "target 1: bad offsets"),
+                ([b"ACGT", wide], [(0, 1, 0, 3, 0.5)], None, _lib.ERR_UNSUPPORTED, "do not fit the LDS")):
+            rc, msg, ms = call(best, queries, good_t, jobs, toff)
+            assert rc == code and word in msg and ms == -1.0, (best, jobs, rc, msg, ms)
+        # a job without targets and one without queries next to a full one: good
+        rc, msg, ms = call(best, good_q, good_t, [(0, 2, 0, 3, 0.5), (0, 1, 3, 0, 0.5), (2, 0, 0, 2, 0.5)])
+        if torch.cuda.is_available():
+            assert rc == _lib.OK and ms >= 0.0, (rc, msg, ms)
+        else:
+            assert rc == _lib.ERR_DEVICE and ms == -1.0, (rc, msg, ms)
