@@ -282,6 +282,65 @@ def test_lane_abi(lib, tmp_path, synth_files):
         stats.close()
 
 
+def test_lane_fallback_list_longer_than_what_travels_with_the_batch(lib, synth_files):
+    """A lane sends the first 4 096 fallback indices with every batch and smx_lane_fallback fetches the rest: a lane of 8 192
+    reads and one batch with more than 4 096 reads whose primary record trimmed to nothing (the c2 file's, tiled, between
+    1 500 other rows of the file), then a small batch on the same lane, which must report its own short list."""
+    import stats_utils as U
+    from specimux_amd import _lib, trace_stats
+    from specimux_amd.demultiplex import compiled_panel, concat_records
+    from specimux_amd.io_utils import SeqRecord
+    from specimux_amd.native_io import Lane
+    pf, sf, fq = synth_files["c2"]
+    both = Both(pf, sf)
+    cp = compiled_panel(both.specimens, both.parameters, both.args, both.prefilter)
+    view = U.panel_view(both.opanel)
+    NP = len(view.primers)
+    assert view.primer_names == cp.primer_names and view.pairs == [tuple(p) for p in cp.pairs] and cp.hits_per_read == 2 * NP
+    reads, _ = O.read_sequences(fq)
+    bases, offsets, _seqs = concat_records([SeqRecord(s, rid, rid, q) for rid, s, q in reads])
+    windows, lens = cp.pack_windows(bases, offsets)
+    file_ops = cp.run(windows, lens)[0]
+    empty = np.flatnonzero(file_ops["flags"] & _lib.OPF_TRIM_EMPTY)
+    others = np.flatnonzero((file_ops["flags"] & _lib.OPF_TRIM_EMPTY) == 0)[:1500]
+    assert len(empty) >= 1 and len(others) == 1500
+    rows = np.concatenate([np.resize(empty, 4500), others])
+    rows = rows[np.random.default_rng(5).permutation(len(rows))]            # interleaved
+    small = np.concatenate([others[:97], empty[:1], others[97:99], empty[-1:]])
+
+    def reference_of(batch):
+        ops, _extra, _counts, hits, _bdist = cp.run(windows[batch], lens[batch], want_hits="lean")
+        return U.rows_reference(NP, view.pdir, view.pairs, True, hits, ops)
+
+    stats = trace_stats.DeviceStats(cp, 1 << 12)
+    lane = Lane(cp, 8192)
+    counts = np.zeros(cp.counts_len, dtype=np.uint64)
+    try:
+        lane.attach_stats(stats)
+        table = {}
+        for batch in (rows, small):
+            n = len(batch)
+            lane.windows[:n] = windows[batch]
+            lane.lens[:n] = lens[batch]
+            lane.submit(n)
+            ops, _extra = lane.wait(counts)
+            flagged = np.flatnonzero(ops["flags"] & _lib.OPF_TRIM_EMPTY).tolist()
+            if batch is rows:
+                assert 4096 < len(flagged) <= n == 6000
+            else:
+                assert flagged == [97, 100] and n == 101
+            assert sorted(lane.fallback().tolist()) == flagged
+            want, listed = reference_of(batch)
+            assert listed == flagged
+            for key, c in want.items():
+                table[key] = table.get(key, 0) + c
+            keys, cnts = stats.read()
+            assert dict(zip(keys.tolist(), cnts.tolist())) == table
+    finally:
+        lane.close()
+        stats.close()
+
+
 # ------------------------------------------------------------------ 7: a table that fills up is loud
 def test_full_table_is_loud_and_the_tree_stays(lib, tmp_path, synth_files):
     from specimux_amd import cli

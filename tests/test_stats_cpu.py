@@ -9,6 +9,7 @@ import sys
 
 import pytest
 
+import stats_utils as U
 from oracle import specimux_oracle as O
 from parity_utils import make_args, reads_from_set
 from stats_utils import CASES, REPO, STATS_GOLDEN, oracle_table, panel_view, parse_sim, queries_of, sim_input, unpack_trace
@@ -271,3 +272,132 @@ def test_resolved_record_behind_a_dereplicated_one(sim, tmp_path):
     assert counters["multi_record"] == 2 and counters["candidates"] == 4
     assert [r[5] for r in rows if r[3] == "SPECIMEN_RESOLVED"] == ["unknown", "unknown"]
     assert {row[7:9] for (row, _f) in exp.counts} == {("unknown", "unknown")}
+
+
+# ------------------------------------------------------------------ synthetic hit tables: the reference against the twin
+# The cases of tests/test_stats_kernel_gpu.py (stats_utils.case_*), run through the simulation: its table must equal
+# stats_utils.rows_reference, its fallback list the reference's, for one workgroup and for seven.  `local_spill` proves
+# here, where it can be counted, that the inputs built to pass the workgroup's table by do so.
+@pytest.fixture(scope="module")
+def sim_small(tmp_path_factory):
+    exe = os.fspath(tmp_path_factory.mktemp("stats_small") / "stats_sim_small")
+    subprocess.check_call(["g++", "-O2", "-std=c++17", "-DSTATS_LCAP=64", "-DSTATS_LPROBE=2", "-I",
+                           os.path.join(REPO, "specimux_amd", "csrc"), "-I", os.path.join(REPO, "include"), "-o", exe,
+                           os.path.join(REPO, "tests", "cpu", "stats_sim.cpp")])
+    return exe
+
+
+@pytest.fixture(scope="module")
+def facts(tmp_path_factory):
+    """{c2, c3, c9: (NP, pdir, pairs, number of barcodes)} from the oracle's panel; c9 = stats_utils.panel_nine_pairs."""
+    from specimux_amd import synth
+    out = {}
+    for name, pan in (("c2", synth.panel_c2()), ("c3", synth.panel_c3()), ("c9", U.panel_nine_pairs())):
+        pf, sf = pan.write(os.fspath(tmp_path_factory.mktemp("facts_" + name)))
+        view = panel_view(O.load_panel(pf, sf))
+        out[name] = (len(view.primers), view.pdir, view.pairs, len(view.barcodes))
+    assert out["c2"][0] == 2 and out["c3"][0] == out["c9"][0] == 8 and len(out["c3"][2]) == 4 and len(out["c9"][2]) == 9
+    return out
+
+
+def run_twin(exe, tmp_path, fact, preorient, hits, ops, capacity, grid):
+    NP, pdir, pairs, _nb = fact
+    path = tmp_path / "synthetic.bin"
+    path.write_bytes(U.sim_bytes(NP, pdir, pairs, preorient, hits, ops))
+    return subprocess.run([exe, os.fspath(path), str(capacity), str(grid)], capture_output=True, text=True)
+
+
+def twin_equals_reference(exe, tmp_path, fact, preorient, hits, ops, capacity=1 << 14, grids=(1, 7), want=None):
+    """-> (the simulation's counters per grid, the reference's table and fallback list)"""
+    NP, pdir, pairs, _nb = fact
+    table, fallback = want or U.rows_reference(NP, pdir, pairs, preorient, hits, ops)
+    out = []
+    for grid in grids:
+        res = run_twin(exe, tmp_path, fact, preorient, hits, ops, capacity, grid)
+        assert res.returncode == 0, res.stdout[:300] + res.stderr[:300]
+        counters, got_fallback, got = parse_sim(res.stdout)
+        assert got == dict(table), (grid, len(got), len(table), [(hex(k), got.get(k), table.get(k)) for k in set(got) ^ set(table)][:5])
+        assert sorted(got_fallback) == fallback and counters["reads"] == len(ops)
+        out.append(counters)
+    return out, table, fallback
+
+
+@pytest.fixture(scope="module")
+def truth_table():
+    return U.case_truth_table()
+
+
+@pytest.fixture(scope="module")
+def random_case(facts):
+    NP, pdir, pairs, nb = facts["c9"]
+    hits, ops = U.case_random(NP, nb - 1)
+    return hits, ops, {pre: U.rows_per_read(NP, pdir, pairs, pre, hits, ops) for pre in (True, False)}
+
+
+@pytest.mark.parametrize("preorient", [True, False])
+def test_twin_truth_table(sim, tmp_path, facts, truth_table, preorient):
+    hits, ops = truth_table
+    _c, table, fallback = twin_equals_reference(sim, tmp_path, facts["c2"], preorient, hits, ops)
+    U.assert_truth_table_coverage(table, fallback, ops, preorient)
+
+
+@pytest.mark.parametrize("preorient", [True, False])
+def test_twin_random_hits(sim, sim_small, tmp_path, facts, random_case, preorient):
+    hits, ops, _rows = random_case
+    counters, table, _fb = twin_equals_reference(sim, tmp_path, facts["c9"], preorient, hits, ops)
+    assert len(table) >= U.LCAP + 1                          # more keys than one workgroup's table has slots
+    assert all(c["local_spill"] > 0 for c in counters)
+    small, _t, _f = twin_equals_reference(sim_small, tmp_path, facts["c9"], preorient, hits, ops)
+    assert all(c["local_spill"] > 10000 for c in small)
+
+
+@pytest.mark.parametrize("uses", ["1+j%6", "8x256", "48x256"])
+def test_twin_local_bypass_and_wrap(sim, sim_small, tmp_path, facts, uses):
+    NP, _pdir, pairs, _nb = facts["c3"]
+    hits, ops, _keys = U.case_bypass(NP, pairs[0], 1, U.BYPASS_USES[uses], 71)
+    for exe in (sim, sim_small):
+        counters, table, _fb = twin_equals_reference(exe, tmp_path, facts["c3"], True, hits, ops, capacity=64)
+        assert len(table) == 40 and sum(table.values()) == len(ops)
+        # a workgroup that sees them all holds at most a probe run of these keys: the other 24 (38 in the small build) pass
+        # it by every time
+        floor = sum(sorted(table.values())[:40 - (U.LPROBE if exe == sim else 2)])
+        assert counters[0]["local_spill"] >= floor >= 24 and counters[1]["local_spill"] >= 24
+
+
+def test_twin_global_table_exactly_full_and_one_too_many(sim, sim_small, tmp_path, facts):
+    NP, _pdir, pairs, _nb = facts["c3"]
+    hits, ops = U.case_full_table(NP, pairs[0], 1, 8)
+    for exe in (sim, sim_small):
+        counters, table, _fb = twin_equals_reference(exe, tmp_path, facts["c3"], True, hits, ops, capacity=8)
+        assert sorted(table.values()) == [5] * 8
+        # eight keys never exhaust the stock table's 16 probes: only the 2-probe build drives these past the local table
+        assert all((c["local_spill"] > 0) == (exe == sim_small) for c in counters)
+    hits, ops = U.case_full_table(NP, pairs[0], 1, 9)
+    for exe in (sim, sim_small):
+        for grid in (1, 7):
+            res = run_twin(exe, tmp_path, facts["c3"], True, hits, ops, 8, grid)
+            assert res.returncode == 4 and res.stdout.startswith("SMX_ERR_OVERFLOW") and "key " not in res.stdout
+            assert "(8 slots) is full: 5 increments found no slot" in res.stdout
+
+
+def test_twin_grid_stride_with_a_remainder(sim, tmp_path, facts, random_case):
+    NP, pdir, pairs, _nb = facts["c9"]
+    hits_b, ops_b, rows_b = random_case
+    G = 3
+    hits, ops, use, pool = U.case_stride(hits_b, ops_b, rows_b[True], G)
+    want = U.reference_of_templates(rows_b[True], pool, use)
+    assert len(ops) == 2 * G * 256 + 77 and want == U.rows_reference(NP, pdir, pairs, True, hits, ops)
+    twin_equals_reference(sim, tmp_path, facts["c9"], True, hits, ops, grids=(G,), want=want)
+
+
+def test_twin_fallback_list(sim, tmp_path, facts):
+    hits, ops = U.case_fallback()
+    _c, table, fallback = twin_equals_reference(sim, tmp_path, facts["c2"], True, hits, ops)
+    assert 600 <= len(fallback) <= 800
+
+
+def test_twin_field_edges(sim, tmp_path, facts):
+    NP, _pdir, pairs, _nb = facts["c3"]
+    hits, ops = U.case_field_edges(NP, pairs)
+    _c, table, _fb = twin_equals_reference(sim, tmp_path, facts["c3"], True, hits, ops)
+    U.assert_field_edges(table, len(pairs))
