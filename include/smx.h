@@ -30,7 +30,8 @@
  *           sequence of the run and a right piece of another.
  *   smx_cons_*        <- nothing: the reference hands the consensus of a specimen to an external tool (DESIGN.md
  *           section 15), and never asks whether a cluster holds two sequences (smx_cons_phase, section 18) or how far
- *           a called sequence can be trusted (smx_cons_resample, section 20).
+ *           a called sequence can be trusted (smx_cons_resample, section 20), or how noisy the reads themselves are
+ *           (smx_cons_profile, section 21).
  *   smx_inner_scan    <- nothing: the reference never looks between the two end windows.
  *   smx_counts_*      <- the parent summing (batch_total, batch_matched) (orchestration.py:203-207).
  *
@@ -490,6 +491,40 @@ int smx_cons_phase(const char *reads, const uint64_t *roff, uint32_t n_reads, co
 int smx_cons_resample(const char *reads, const uint64_t *roff, uint32_t n_reads, const int32_t *k,
                       const smx_cons_job *jobs, uint32_t n_jobs, const uint64_t *masks, uint32_t n_levels,
                       uint32_t *votes, uint32_t *aligned, uint64_t *agree, uint32_t *sub_aligned, float *kernel_ms);
+
+/*
+ * errors: after the alignment and the vote of smx_cons_votes, in the same call and over the rows that are still on the
+ * device, every member's row reduced against its job's draft and the read's quality bytes to the error profile of the
+ * reads -- nothing in the reference does this.
+ *   reads .. n_jobs    as for smx_cons_votes; votes / aligned receive exactly what smx_cons_votes returns for them
+ *   quals              the FASTQ quality bytes as they stand in the file, in the layout of reads (the same roff).  The
+ *                      draft's own quality bytes are never read
+ * SMX_ERR_ARG, before the device is asked for: a null quals, per_member or tables while some job has members.
+ * With dc the code of the draft's byte at column p < m (0-3, 4 = any other byte) and, of the member's row word p, sym = bits
+ * 0-2 and L = bits 3-10, a column is a match (sym <= 3, dc <= 3, sym == dc), a sub (sym <= 3, dc <= 3, sym != dc), a del
+ * (sym == 5) or other (sym == 4 or dc == 4); L > 0 at p <= m is one insertion event of L bases.  The column's base is read
+ * byte rp(p) = sum over q < p of ((sym_q <= 4) + L_q) + L_p, the bases inserted before it are the L_p bytes before that:
+ * exact unless some L is 255, the clipped value; such a member is `clipped`.
+ * per_member: job after job, member after member, SMX_PROFILE_MEMBER_WORDS words: match, sub, del, other, ins_events,
+ * ins_bases (the sum of L as stored), clipped (0 / 1), 0.  A member above its limit has eight zeros.
+ * tables: job after job SMX_PROFILE_JOB_WORDS words, summed over the members within their limit:
+ *   q[64][3]      per Phred bin (byte b: b < 33 ? 0 : min(b - 33, 63)) the read bases in a match column, in a sub or other
+ *                 column, and the inserted bases (all L of them, each under its own byte's bin).  Unclipped members only
+ *   subst[4][5]   dc (0-3) x the member's symbol: 0-3 = A C G T, 4 = deletion
+ *   ins[6]        the kept inserted codes 0-4 (the first SMX_CONS_MAX_INS of an insertion), then the bases beyond those
+ *   hp[8][7]      per run of the draft -- a maximal stretch [s, s + r) of one code b <= 3 -- and member: length class
+ *                 min(r, 8) - 1 x (delta + 3), delta = clamp(obs - r, -3, +3), obs = the run's columns where sym == b plus
+ *                 the kept inserted codes equal to b before the columns s .. s + r
+ * Integer adds only: every word is the same from run to run.  A job of n = 0, or without a member within its limit, has
+ * zero tables.
+ */
+#define SMX_PROFILE_MEMBER_WORDS 8
+#define SMX_PROFILE_Q_BINS 64
+#define SMX_PROFILE_JOB_WORDS (SMX_PROFILE_Q_BINS * 3 + 4 * 5 + 6 + 8 * 7)
+
+int smx_cons_profile(const char *reads, const uint64_t *roff, uint32_t n_reads, const int32_t *k,
+                     const smx_cons_job *jobs, uint32_t n_jobs, const unsigned char *quals, uint32_t *votes,
+                     uint32_t *aligned, uint32_t *per_member, uint32_t *tables, float *kernel_ms);
 
 /*
  * crosstalk: NW (global) edit distances of every read of a run to every consensus (ref) of the run, reduced on the device

@@ -31,6 +31,7 @@ CONS_JOB_DTYPE = np.dtype([("draft", "<u4"), ("r0", "<u4"), ("n", "<u4")])
 CONS_MAX_INS, CONS_VOTE_WORDS = 4, 26
 CONS_MAX_SITES = 64
 CONS_REPLICATES, CONS_MAX_LEVELS = 64, 16
+PROFILE_MEMBER_WORDS, PROFILE_Q_BINS, PROFILE_JOB_WORDS = 8, 64, 274
 CONS_SITE_DTYPE = np.dtype([("pos", "<u4"), ("kind", "u1"), ("major", "u1"), ("minor", "u1"), ("pad", "u1"),
                             ("n_major", "<u4"), ("n_minor", "<u4")])
 assert PAIRS_JOB_DTYPE.itemsize == 8 and CONS_JOB_DTYPE.itemsize == 12 and CONS_SITE_DTYPE.itemsize == 16
@@ -127,6 +128,7 @@ SYMBOLS = [
                                  _P, _P, _P, _P, _P, _P, _P, C.POINTER(C.c_float)]),
     ("smx_cons_resample", C.c_int, [C.c_char_p, _P, C.c_uint32, _P, _P, C.c_uint32, _P, C.c_uint32, _P, _P, _P, _P,
                                     C.POINTER(C.c_float)]),
+    ("smx_cons_profile", C.c_int, [C.c_char_p, _P, C.c_uint32, _P, _P, C.c_uint32, _P, _P, _P, _P, _P, C.POINTER(C.c_float)]),
     ("smx_inner_scan", C.c_int, [C.c_char_p, _P, C.c_uint32, _P, _P, _P, C.c_uint32, C.c_int32, C.c_uint32, C.c_uint64,
                                  _P, _P, _P, C.POINTER(C.c_float)]),
     ("smx_inner_scan_batch", C.c_int, [_P, C.c_char_p, _P, C.c_uint32, _P, C.c_int32, C.c_uint32, C.c_uint64, _P, _P, _P,

@@ -190,6 +190,24 @@ def cons_resample(reads: Sequence[bytes], ks: Sequence[int], jobs: Sequence[Tupl
                     split(sub, [(n_levels, _lib.CONS_REPLICATES)] * nj)))
 
 
+def cons_profile(reads: Sequence[bytes], quals: Sequence[bytes], ks: Sequence[int], jobs: Sequence[Tuple[int, int, int]],
+                 kernel_ms: Optional[list] = None):
+    """One smx_cons_profile call.  quals: per read its FASTQ quality bytes, as long as the read (a draft's are never read).
+    Per job what cons_votes returns for it (table, aligned), its members' counts [n, 8] uint32 (match, sub, del, other,
+    ins_events, ins_bases, clipped, 0) and its SMX_PROFILE_JOB_WORDS table words (q[64][3], subst[4][5], ins[6], hp[8][7])."""
+    if len(quals) != len(reads) or any(len(q) != len(r) for q, r in zip(quals, reads)):
+        raise ValueError("quals must hold one string per read, of the read's length")
+    nj = len(jobs)
+    shapes, table, aligned = _vote_outputs(reads, jobs)
+    members = _filled(sum(n for _, _, n in jobs) * _lib.PROFILE_MEMBER_WORDS, WORD_SENTINEL, np.uint32)
+    tables = _filled(nj * _lib.PROFILE_JOB_WORDS, WORD_SENTINEL, np.uint32)
+    _cons("smx_cons_profile", reads, ks, jobs, b"".join(quals), _lib.ptr(table), _lib.ptr(aligned), _lib.ptr(members),
+          _lib.ptr(tables), kernel_ms=kernel_ms)
+    return list(zip(split(table, shapes), [int(a) for a in aligned[:nj]],
+                    split(members, [(n, _lib.PROFILE_MEMBER_WORDS) for _, _, n in jobs]),
+                    split(tables, [(_lib.PROFILE_JOB_WORDS,)] * nj)))
+
+
 # ------------------------------------------------------------------------------------------------ crosstalk
 def _nearest(name, seqs, ks, groups, jobs, *outs, kernel_ms):
     return invoke(name, b"".join(seqs), _lib.ptr(offsets(seqs)), len(seqs), _lib.ptr(limits(ks)),

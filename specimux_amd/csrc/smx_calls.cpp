@@ -508,6 +508,7 @@ struct {
     DevBuf rows, dist, votes, aligned;
     DevBuf planes_off, sites, n_sites, n_qualified, planes, link;   // smx_cons_phase (smx_phase.hip)
     DevBuf masks, member_off, agree_off, agree, sub_aligned;        // smx_cons_resample (smx_resample.hip)
+    DevBuf quals, qoff, per_member, tables;                         // smx_cons_profile (smx_profile.hip)
 } g_cons;
 
 struct ConsPhase {      // what smx_cons_phase adds to a votes call
@@ -525,12 +526,17 @@ struct ConsResample {   // what smx_cons_resample adds to a votes call
     uint32_t *sub_aligned;
 };
 
+struct ConsProfile {    // what smx_cons_profile adds to a votes call
+    const unsigned char *quals;
+    uint32_t *per_member, *tables;
+};
+
 // One smx_cons_* call.  rows / dist (pileup) or votes / aligned (votes) receive the result, the others are null; with
 // `phase` a votes call goes on to the variant kernels over the rows and votes it left on the device, with `resample` to
-// the resampling kernel over the rows and distances.
+// the resampling kernel over the rows and distances, with `profile` to the error-profile kernel over the same.
 int cons_call(const char *reads, const uint64_t *roff, uint32_t n_reads, const int32_t *k, const smx_cons_job *jobs,
               uint32_t n_jobs, uint32_t *rows, int32_t *dist, uint32_t *votes, uint32_t *aligned, float *kernel_ms,
-              const ConsPhase *phase = nullptr, const ConsResample *resample = nullptr) {
+              const ConsPhase *phase = nullptr, const ConsResample *resample = nullptr, const ConsProfile *profile = nullptr) {
     const bool pileup = rows || dist;
     if (!reads || !roff || !k || (n_jobs && (!jobs || (pileup ? !rows || !dist : !votes || !aligned))))
         return fail(SMX_ERR_ARG, "null argument");
@@ -544,6 +550,8 @@ int cons_call(const char *reads, const uint64_t *roff, uint32_t n_reads, const i
     int rc = smx::cons_plan(reads, roff, n_reads, k, jobs, n_jobs, hist_budget, &P, &why);
     if (rc == SMX_OK && phase) rc = smx::cons_plan_phase(phase->min_permille, phase->max_sites, &P, &why);
     if (rc == SMX_OK && resample) rc = smx::cons_plan_resample(resample->masks != nullptr, resample->n_levels, &P, &why);
+    if (rc == SMX_OK && profile)
+        rc = smx::cons_plan_profile(profile->quals != nullptr, profile->per_member != nullptr, profile->tables != nullptr, &P, &why);
     SMX_TRY(refused(rc, why));
     if (kernel_ms) *kernel_ms = 0.0f;
     if (n_jobs == 0) return SMX_OK;     // a call without jobs is answered without a device (the tests pin it): the one step out of order
@@ -580,6 +588,13 @@ int cons_call(const char *reads, const uint64_t *roff, uint32_t n_reads, const i
         HIP_TRY(W.agree.ensure((size_t)P.agree_off.back() * 8));
         HIP_TRY(W.sub_aligned.ensure((size_t)P.sub_words * 4));
     }
+    if (profile) {      // the quality bytes beside the reads, in the caller's layout
+        HIP_TRY(W.quals.upload(profile->quals, P.n_dist ? (size_t)roff[n_reads] : 0));   // without members: may be null, never read
+        HIP_TRY(W.qoff.upload(roff, ((size_t)n_reads + 1) * 8));
+        HIP_TRY(W.per_member.ensure((size_t)P.member_words * 4));
+        HIP_TRY(W.tables.ensure((size_t)P.table_words * 4));
+        HIP_TRY(hipMemset(W.tables.p, 0, (size_t)P.table_words * 4));   // the kernel adds into them
+    }
     const int32_t *d_len = W.reads.len.as<int32_t>();
     SMX_TRY(timed_launches(kernel_ms, "consensus kernel launch", [&] {
         int e = smx::chunk_for_each_class(P, [&](const smx::ChunkLaunch &L) {
@@ -603,6 +618,11 @@ int cons_call(const char *reads, const uint64_t *roff, uint32_t n_reads, const i
                                          n_jobs, resample->n_levels, P.max_words, W.rows.as<uint32_t>(), W.dist.as<int32_t>(),
                                          W.masks.as<uint64_t>(), W.member_off.as<uint64_t>(), W.agree_off.as<uint64_t>(),
                                          P.member_off.back(), W.agree.as<uint64_t>(), W.sub_aligned.as<uint32_t>());
+        if (e == 0 && profile)
+            e = smx_launch_cons_profile(nullptr, W.reads.bytes.as<unsigned char>(), W.reads.doff.as<uint64_t>(), d_len, W.jobs.p,
+                                        n_jobs, P.profile_max_members, W.rows.as<uint32_t>(), W.dist.as<int32_t>(),
+                                        W.quals.as<unsigned char>(), W.qoff.as<uint64_t>(), W.per_member.as<uint32_t>(),
+                                        W.tables.as<uint32_t>());
         return e;
     }));
     if (pileup) {
@@ -627,6 +647,10 @@ int cons_call(const char *reads, const uint64_t *roff, uint32_t n_reads, const i
     if (resample) {
         HIP_TRY(hipMemcpy(resample->agree, W.agree.p, (size_t)P.agree_off.back() * 8, hipMemcpyDeviceToHost));
         HIP_TRY(hipMemcpy(resample->sub_aligned, W.sub_aligned.p, (size_t)P.sub_words * 4, hipMemcpyDeviceToHost));
+    }
+    if (profile) {
+        if (P.member_words) HIP_TRY(hipMemcpy(profile->per_member, W.per_member.p, (size_t)P.member_words * 4, hipMemcpyDeviceToHost));
+        if (profile->tables) HIP_TRY(hipMemcpy(profile->tables, W.tables.p, (size_t)P.table_words * 4, hipMemcpyDeviceToHost));
     }
     return SMX_OK;
 }
@@ -659,6 +683,14 @@ int smx_cons_resample(const char *reads, const uint64_t *roff, uint32_t n_reads,
     if (n_jobs && (!votes || !aligned)) return fail(SMX_ERR_ARG, "null argument");
     const ConsResample resample{masks, n_levels, agree, sub_aligned};
     return cons_call(reads, roff, n_reads, k, jobs, n_jobs, nullptr, nullptr, votes, aligned, kernel_ms, nullptr, &resample);
+}
+
+int smx_cons_profile(const char *reads, const uint64_t *roff, uint32_t n_reads, const int32_t *k, const smx_cons_job *jobs,
+                     uint32_t n_jobs, const unsigned char *quals, uint32_t *votes, uint32_t *aligned, uint32_t *per_member,
+                     uint32_t *tables, float *kernel_ms) {
+    if (n_jobs && (!votes || !aligned)) return fail(SMX_ERR_ARG, "null argument");
+    const ConsProfile profile{quals, per_member, tables};
+    return cons_call(reads, roff, n_reads, k, jobs, n_jobs, nullptr, nullptr, votes, aligned, kernel_ms, nullptr, nullptr, &profile);
 }
 
 // ---- inner scan: every pattern against the whole read, hits on the internal columns (smx_inner.hip)

@@ -1,7 +1,7 @@
 // smx_cons_plan.h -- the host-side plan of one smx_cons_* call (smx_calls.cpp): argument checks, the jobs with their
 // offsets, the alignment's job list by register class with its chunk prefix, and the size of the history workspace.
 // Host only and free of HIP calls, so that the sanitizer drivers (tests/asan/cons_driver.cpp, phase_driver.cpp,
-// resample_driver.cpp) and the CPU simulations run it as it is.
+// resample_driver.cpp, profile_driver.cpp) and the CPU simulations run it as it is.
 #ifndef SMX_CONS_PLAN_H
 #define SMX_CONS_PLAN_H
 #include <algorithm>
@@ -34,6 +34,9 @@ struct ConsPlan : ChunkLaunches {    // the launch table: the jobs of `align` pe
     // agree_off[j + 1]), level after level m + 1 each; sub_aligned holds SMX_CONS_REPLICATES counts per (job, level)
     std::vector<uint64_t> member_off, agree_off;   // n_jobs + 1 entries each
     uint64_t mask_words = 0, sub_words = 0;
+    // the tables of an smx_cons_profile call (cons_plan_profile)
+    uint64_t member_words = 0, table_words = 0;
+    uint32_t profile_max_members = 0;      // the largest job's n: the launch's second grid dimension
 };
 
 // Returns SMX_OK, or the status to fail with and why.  hist_budget: CONS_HIST_BYTES, or a test's smaller figure.
@@ -169,6 +172,30 @@ inline int cons_plan_resample(bool have_masks, uint32_t n_levels, ConsPlan *plan
     }
     P.mask_words = (uint64_t)n_levels * P.member_off.back();
     P.sub_words = (uint64_t)P.jobs.size() * n_levels * SMX_CONS_REPLICATES;
+    return SMX_OK;
+}
+
+// The tables of a planned call with the error profile (smx_cons_profile): the argument checks, the sizes of the member
+// words and job tables, and the launch.  Job j's members own the words [dist_off * SMX_PROFILE_MEMBER_WORDS, ...) of
+// per_member, the order of member_off above, and the job the words [j * SMX_PROFILE_JOB_WORDS, ...) of tables.
+// have_quals .. have_tables: the caller's pointers are not null.
+inline int cons_plan_profile(bool have_quals, bool have_per_member, bool have_tables, ConsPlan *plan, std::string *why) {
+    ConsPlan &P = *plan;
+    if (P.n_dist != 0 && !(have_quals && have_per_member && have_tables)) {
+        *why = std::string(!have_quals ? "quals" : !have_per_member ? "per_member" : "tables") + " is null and the jobs have " +
+               std::to_string(P.n_dist) + " members";
+        return SMX_ERR_ARG;
+    }
+    P.profile_max_members = 0;
+    for (const ConsJobDev &J : P.jobs) P.profile_max_members = std::max(P.profile_max_members, J.n);
+    // the launch: a workgroup row per job, SMX_PROFILE_BLOCK_MEMBERS members per workgroup
+    if ((uint64_t)P.jobs.size() > (uint64_t)INT32_MAX || P.profile_max_members > SMX_PROFILE_BLOCK_MEMBERS * 65535u) {
+        *why = "profile: " + std::to_string(P.jobs.size()) + " jobs or a job of " + std::to_string(P.profile_max_members) +
+               " members is more than one launch holds: split the call";
+        return SMX_ERR_UNSUPPORTED;
+    }
+    P.member_words = P.n_dist * SMX_PROFILE_MEMBER_WORDS;
+    P.table_words = (uint64_t)P.jobs.size() * SMX_PROFILE_JOB_WORDS;
     return SMX_OK;
 }
 

@@ -119,6 +119,9 @@ struct ConsJobDev {
     uint64_t dist_off;    // its n distances
     uint64_t votes_off;   // its (m + 1) x SMX_CONS_VOTE_WORDS vote words
 };
+// errors (smx_profile.hip): a workgroup takes SMX_PROFILE_BLOCK_MEMBERS members of a job, each of its waves
+// SMX_PROFILE_WAVE_MEMBERS of them; the plan (smx_cons_plan.h cons_plan_profile) sizes the grid by the former
+constexpr uint32_t SMX_PROFILE_WAVE_MEMBERS = 4, SMX_PROFILE_BLOCK_MEMBERS = 16;
 
 // inner scan (smx_inner.hip): one chunk of whole reads and one word-width class of patterns.  Device pointers.
 struct InnerArgs {
@@ -196,6 +199,14 @@ int smx_launch_cons_resample(void *stream, const unsigned char *d_bytes, const u
                              const void *d_jobs, uint32_t n_jobs, uint32_t n_levels, uint32_t max_words, const uint32_t *d_rows,
                              const int32_t *d_dist, const uint64_t *d_masks, const uint64_t *d_member_off,
                              const uint64_t *d_agree_off, uint64_t level_stride, uint64_t *d_agree, uint32_t *d_sub_aligned);
+// errors (smx_profile.hip), after smx_launch_cons_align and smx_launch_cons_vote on the same stream: per member its
+// SMX_PROFILE_MEMBER_WORDS counts into d_per_member (job j's members from dist_off on), per job its SMX_PROFILE_JOB_WORDS table
+// words added into d_tables (zeroed by the caller), from d_rows, d_dist, the drafts' bytes and the quality bytes d_quals with
+// their n_reads + 1 offsets d_qoff (the caller's layout, not the padded one).  max_members = the largest job's n
+int smx_launch_cons_profile(void *stream, const unsigned char *d_bytes, const uint64_t *d_off, const int32_t *d_len,
+                            const void *d_jobs, uint32_t n_jobs, uint32_t max_members, const uint32_t *d_rows,
+                            const int32_t *d_dist, const unsigned char *d_quals, const uint64_t *d_qoff,
+                            uint32_t *d_per_member, uint32_t *d_tables);
 // crosstalk (smx_nearest.hip); wr, grid, per_block, d_scratch, d_bytes / d_off / d_len / d_k as for smx_launch_pairs;
 // d_group: the group per sequence.  runs[0..n_runs) (NearestRun over the class's ref list d_refs) with
 // chunk_start[0..n_runs] (nonzero each).  dist = 1: d_dist holds int32 distances, job j's nq x nt at its dist_off;
