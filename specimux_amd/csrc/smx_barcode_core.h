@@ -23,6 +23,17 @@ SMX_HD void bs_sched_barrier() {
 #endif
 }
 
+// Device: the value becomes opaque to the optimiser here (no instruction is emitted).  The automaton's states cross a
+// column boundary through it: without it the OR trees of several columns are reassociated into one, the early columns' Eq
+// words stay live to the end of the scan and spill.
+SMX_HD void bs_pin(unsigned &x) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm("" : "+v"(x));
+#else
+    (void)x;
+#endif
+}
+
 // Bit-sliced SHW scan: ONE lane aligns up to 32 barcodes (one word of the primer's barcode list) against one
 // target at once.  Bit b of every word belongs to barcode b.  Per DP cell (row i = barcode position, column c =
 // target position) the unit-cost recurrence on the vertical / horizontal deltas in {-1,0,+1} is
@@ -90,27 +101,46 @@ SMX_HD void bitsliced_shw(const unsigned *re, const unsigned char *cw, int ncol,
     }
 }
 
-// Banded DP with a fixed band half-width KB >= k (a wider band than k is still exact: it contains the k band); the
-// 2*KB+1 live rows are kept in a circular register window (row r lives in slot r mod WIN, all slot indices static).
-// Every barcode is PADDED to M rows by wildcard rows (Eq = all ones for every text code, also
-// past the end of the window): the loop bounds no longer depend on the barcode length, so the whole scan unrolls into
-// straight-line code -- static row tests, LDS reads at immediate offsets issued ahead of their use, no scalar branches.
-// Exactness: a path that reaches (m, j) continues for free along its diagonal to (M, j + M - m), and every other way
-// into row M costs at least as much, so min over the live columns of row M equals min over the live columns of row m;
-// the lean summary only ever uses that minimum (the lowest non-empty distance level and its bits).  Column c' of row M
-// is live iff c' - (M - m) lies inside the window.  M + KB columns instead of m + k: 19 vs 16 for 13-nt barcodes, at
-// less than half the instructions per column.
+// The padded scan: a bit-sliced diagonal automaton over thresholded states, not a delta-encoded DP.
+// Every barcode is PADDED to M rows by wildcard rows (Eq = all ones for every text code, also past the end of the
+// window): the loop bounds no longer depend on the barcode length, so the whole scan unrolls into straight-line code --
+// static row tests, LDS reads at immediate offsets issued ahead of their use, no scalar branches.  A path that reaches
+// (m, j) continues for free along its diagonal to (M, j + M - m), and every other way into row M costs at least as much,
+// so min over the live columns of row M equals min over the live columns of row m.  Column c' of row M is live iff
+// c' - (M - m) lies inside the window (nlive = ncol + (M - m)).  M + KB columns instead of m + k.
+//
+// States.  The consumers (phase3b_barcodes ORs the levels into dmask, phase3c_summary reads the lowest) need one fact
+// per barcode and level: was D[M][col] == d <= KB at some live column.  That is a thresholded quantity, so the scan
+// keeps the booleans A_d(row, col) <=> D[row][col] <= d for d = 0..KB directly, with neither deltas nor a score counter.
+// D[row][col] >= |row - col|, hence level d has at most 2d + 1 states per column that can be set, on the diagonals
+// delta = row - col in [-d, d]: (KB + 1)^2 words in all, kept per (level, diagonal) in registers at static indices.
+//
+// Recurrence.  Consuming text position c (col = c -> c + 1), Eq = re[(row - 1) * 16 + code], row = c + 1 + delta:
+//     new(d, delta) = (old(d, delta) & Eq)        diagonal step, match
+//                   |  old(d-1, delta)            substitution
+//                   |  old(d-1, delta+1)          text position skipped     (same row, column c)
+//                   |  new(d-1, delta-1)          barcode position skipped  (row - 1, column c + 1: the NEW lower level)
+// Terms whose diagonal lies outside [-(d-1), d-1] are absent; a state with row < 0 or row > M is 0; row 0 is the constant
+// (c + 1 <= d), all ones wherever it is inside the level's diagonals; column 0 starts as A_d(delta, 0) = (0 <= delta).
+// The Eq reads of a column are the rows row - 1 in [c - KB, c + KB] and [0, M), shared by all levels.  Levels are
+// updated in ascending order and the old level d - 1 is held in one level's worth of temporaries while level d is made.
+//
+// Levels.  After column c the last row sits on diagonal delta = M - (c + 1); while |delta| <= KB, for d = |delta|..KB
+//     seen[d] |= live & A_d(M) & ~A_(d-1)(M)      (A_(d-1) absent, i.e. 0, when d - 1 < |delta|;  live = c < nlive)
+// which is exactly the barcodes whose row-M score is d at that column.  All levels d <= KB are exact (kidx is not needed;
+// the caller ignores levels above k).  This is bit for bit what the banded delta DP of bitsliced_shw_pad_tails collects:
+// its banded values satisfy D' >= D and D' == D wherever D <= KB, hence {D' == d} == {D == d} for every d <= KB.
 template <int KB, int M>
 SMX_HD void bitsliced_shw_pad(const unsigned *re, const unsigned char *cw, int ncol, int m,
                               int kidx, unsigned (&seen)[KB + 1]) {
     constexpr int WIN = 2 * KB + 1, NC = M + KB;
     static_assert(KB < M && M <= 16, "band / padding out of range");
-    unsigned Pw[WIN], Mw[WIN];
+    (void)kidx;
+    unsigned A[KB + 1][WIN];   // A[d][KB + delta], |delta| <= d
 #pragma unroll
-    for (int i = 0; i < WIN; i++) { Pw[i] = ~0u; Mw[i] = 0u; }
-    constexpr int b0 = KB;   // D(bottom in-band row of column 0)
-    unsigned s0 = (b0 & 1) ? ~0u : 0u, s1 = (b0 & 2) ? ~0u : 0u, s2 = (b0 & 4) ? ~0u : 0u, s3 = (b0 & 8) ? ~0u : 0u,
-             s4 = 0u;
+    for (int d = 0; d <= KB; d++)
+#pragma unroll
+        for (int w = 0; w < WIN; w++) A[d][w] = w >= KB ? ~0u : 0u;   // column 0: D[delta][0] = delta <= d
 #pragma unroll
     for (int d = 0; d <= KB; d++) seen[d] = 0u;
     constexpr int rs = 16;   // table block layout [row][code]: every Eq read is base + code at an immediate offset
@@ -122,48 +152,62 @@ SMX_HD void bitsliced_shw_pad(const unsigned *re, const unsigned char *cw, int n
         const unsigned raw = (unsigned)cw[c];
         const unsigned code = c < ncol ? raw : 15u;
         const unsigned *rc = re + code;
-        Pw[(c + KB) % WIN] = ~0u; Mw[(c + KB) % WIN] = 0u;   // the row entering the band: initial vertical delta
-        unsigned Ph = ~0u, Mh = 0u, Zb = 0u;
+        unsigned Eq[WIN];   // Eq[KB + delta]: row - 1 = c + delta
 #pragma unroll
         for (int w = 0; w < WIN; w++) {
-            const int row = c - KB + w;
-            const int sl = ((row % WIN) + WIN) % WIN;
-            if (row >= 0 && row < M) {
-                const unsigned Eq = rc[row * rs];
-                const unsigned Z = Eq | Mh | Mw[sl];
-                const unsigned nPh = Mw[sl] | ~(Z | Pw[sl]);
-                const unsigned nMh = Pw[sl] & Z;
-                const unsigned nPv = Mh | ~(Z | Ph);
-                const unsigned nMv = Ph & Z;
-                Pw[sl] = nPv; Mw[sl] = nMv; Ph = nPh; Mh = nMh;
-                Zb = Z;
-            }
+            const int r1 = c - KB + w;
+            Eq[w] = (r1 >= 0 && r1 < M) ? rc[r1 * rs] : 0u;
         }
-        const bool descending = c + KB <= M - 1;
-        if (descending) {   // +1 unless the diagonal is free: an increment ripple alone
-            unsigned cy = ~Zb, t;
-            t = s0 & cy; s0 ^= cy; cy = t;
-            t = s1 & cy; s1 ^= cy; cy = t;
-            t = s2 & cy; s2 ^= cy; cy = t;
-            t = s3 & cy; s3 ^= cy; cy = t;
-            s4 ^= cy;
-        } else bs_updown5(s0, s1, s2, s3, s4, Ph, Mh);   // score += Ph - Mh (disjoint masks) in one ripple
-        if (c >= M - KB - 1) {   // the tracked cell sits on the last row from here on
-            const unsigned live = c < nlive ? ~0u : 0u;
-            const unsigned hi = ~(s4 | s3) & live;
+        unsigned lo[WIN];   // the OLD level d - 1 while level d is updated
 #pragma unroll
-            for (int d = 0; d <= KB; d++)   // levels above k are computed too (no per-level select); the caller ignores them
-                seen[d] |= hi & ((d & 1) ? s0 : ~s0) & ((d & 2) ? s1 : ~s1) & ((d & 4) ? s2 : ~s2);
+        for (int w = 0; w < WIN; w++) lo[w] = 0u;
+#pragma unroll
+        for (int d = 0; d <= KB; d++) {
+            unsigned od[WIN];
+#pragma unroll
+            for (int w = 0; w < WIN; w++) od[w] = A[d][w];
+#pragma unroll
+            for (int w = KB - d; w <= KB + d; w++) {   // ascending diagonals: new(d-1, delta-1) is already in A[d - 1]
+                const int row = c + 1 + (w - KB);
+                unsigned v;
+                if (row < 0 || row > M) v = 0u;
+                else if (row == 0) v = ~0u;
+                else {
+                    const int dl = d - 1, ad = w - KB < 0 ? KB - w : w - KB;   // |delta|
+                    v = od[w] & Eq[w];
+                    if (ad <= dl) v |= lo[w];
+                    unsigned v2 = 0u;
+                    if (w + 1 - KB <= dl && w + 1 - KB >= -dl) v2 |= lo[w + 1];
+                    if (w - 1 - KB <= dl && w - 1 - KB >= -dl) v2 |= A[d - 1][w - 1];
+                    v |= v2;
+                    bs_pin(v);
+                }
+                A[d][w] = v;
+            }
+#pragma unroll
+            for (int w = 0; w < WIN; w++) lo[w] = od[w];
         }
-        bs_sched_barrier();   // keep the live ranges column-sized (otherwise ~130 LDS reads get hoisted and spill)
+        const int dM = M - (c + 1), adM = dM < 0 ? -dM : dM;
+        if (adM <= KB) {   // the last row is inside the widest level's diagonals from here on
+            const unsigned live = c < nlive ? ~0u : 0u;
+#pragma unroll
+            for (int d = 0; d <= KB; d++)
+                if (d >= adM) seen[d] |= live & A[d][KB + dM] & ~(d - 1 >= adM ? A[d - 1][KB + dM] : 0u);
+        }
+        bs_sched_barrier();   // keep the live ranges column-sized: the Eq reads are not hoisted across columns
     }
 }
 
 // ------------------------------------------------------------------------------------------------
-// The same scan for `--trim tails` (models.py:300-319): besides the distance levels it reports, for this location, the
+// The padded scan for `--trim tails` (models.py:300-319): besides the distance levels it reports, for this location, the
 // minimum level of every barcode (ML[d]) and the last live column at which a barcode selected by `want` sits at its own
 // minimum -- the end of the alignment the reference keeps for that barcode (all optimal ends of its best alignment).
 // Row M, column c' corresponds to row m, column c' - (M - m): a minimum of row m travels down its diagonal for free.
+// This one stays on the delta-encoded DP of bitsliced_shw (the recurrence above it), banded with a fixed half-width
+// KB >= k (a wider band than k is still exact: it contains the k band); the 2*KB+1 live rows are kept in a circular
+// register window (row r lives in slot r mod WIN, all slot indices static), the score of the band's bottom cell in the
+// 5-bit counter.  Same padding, same reads and same seen[] as bitsliced_shw_pad (the CPU simulation holds the two
+// recurrences against each other on every level d <= KB).
 template <int KB, int M>
 SMX_HD void bitsliced_shw_pad_tails(const unsigned *re, const unsigned char *cw, int ncol, int m,
                                     int kidx, const unsigned (&want)[KB + 1], unsigned (&seen)[KB + 1],
