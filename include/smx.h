@@ -32,6 +32,7 @@
  *           section 15), and never asks whether a cluster holds two sequences (smx_cons_phase, section 18) or how far
  *           a called sequence can be trusted (smx_cons_resample, section 20), or how noisy the reads themselves are
  *           (smx_cons_profile, section 21).
+ *   smx_nj            <- nothing: the reference builds no tree of a run's sequences.
  *   smx_inner_scan    <- nothing: the reference never looks between the two end windows.
  *   smx_counts_*      <- the parent summing (batch_total, batch_matched) (orchestration.py:203-207).
  *
@@ -637,6 +638,33 @@ int smx_prefix_reach(const char *seqs, const uint64_t *off, uint32_t n_seqs, con
 int smx_prefix_reach_matrix(const char *seqs, const uint64_t *off, uint32_t n_seqs, const uint32_t *weight,
                             const uint32_t *need, const smx_reach_job *jobs, uint32_t n_jobs, uint32_t E, uint32_t *reach,
                             float *kernel_ms);
+
+/*
+ * tree: the neighbour-joining tree of n tips from their integer distances -- the join that specimux-tree builds over
+ * the called sequences of a run; nothing in the reference does this.  The hot path is double
+ * arithmetic, and the algorithm is fixed to the last operation (smx_nj_core.h: the order of every operation, no fused
+ * multiply-add, ties by the smallest slots), so the records are the same bits from run to run and equal to the ones a
+ * host loop over the same functions computes.
+ *   tri                the packed upper triangle, row-major over i < j, n (n - 1) / 2 int32: the layout
+ *                      smx_pairs_distances writes.  Every entry is >= 0 (SMX_ERR_ARG)
+ *   n                  0..SMX_NJ_MAX_N tips (SMX_ERR_UNSUPPORTED above: the device keeps n x n doubles, 2 GiB at the most)
+ *   merges             max(n - 3, 0) records.  Tips are the nodes 0..n-1; merge t joins the nodes a and b (the smaller
+ *                      slot's first) into the node n + t.  n_active is the number of live nodes before the merge, d their
+ *                      distance and ra, rb their row sums then: the branch lengths follow on the host,
+ *                      la = d / 2 + (ra - rb) / (2 (n_active - 2)), lb = d - la
+ *   last / last_d      the three nodes that remain and their distances d01, d02, d12.  n <= 3 launches nothing: last is
+ *                      0..n-1 and last_d the given distances, the entries without a node or a pair zeroed
+ * Every refusal comes before anything is launched.  kernel_ms (may be NULL) receives the device time of the kernels
+ * (HIP events).
+ */
+#define SMX_NJ_MAX_N 16384
+
+typedef struct smx_nj_merge {
+    uint32_t a, b, n_active, pad;   /* pad = 0 */
+    double d, ra, rb;
+} smx_nj_merge;
+
+int smx_nj(const int32_t *tri, uint32_t n, smx_nj_merge *merges, uint32_t last[3], double last_d[3], float *kernel_ms);
 
 /*
  * Match statistics (specimux-stats; reference trace_stats.py): the "pool -> primer pair -> outcome" tables counted on the

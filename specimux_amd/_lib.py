@@ -43,6 +43,10 @@ assert HITS_JOB_DTYPE.itemsize == 16
 REACH_JOB_DTYPE = np.dtype([("q0", "<u4"), ("nq", "<u4"), ("t0", "<u4"), ("nt", "<u4")])
 REACH_MAX_E = 15
 assert REACH_JOB_DTYPE.itemsize == 16
+NJ_MERGE_DTYPE = np.dtype([("a", "<u4"), ("b", "<u4"), ("n_active", "<u4"), ("pad", "<u4"), ("d", "<f8"), ("ra", "<f8"),
+                           ("rb", "<f8")])
+NJ_MAX_N = 16384
+assert NJ_MERGE_DTYPE.itemsize == 40
 
 
 class PanelDesc(C.Structure):
@@ -122,6 +126,7 @@ SYMBOLS = [
     ("smx_prefix_reach", C.c_int, [C.c_char_p, _P, C.c_uint32, _P, _P, _P, C.c_uint32, C.c_uint32, _P, C.POINTER(C.c_float)]),
     ("smx_prefix_reach_matrix", C.c_int, [C.c_char_p, _P, C.c_uint32, _P, _P, _P, C.c_uint32, C.c_uint32, _P,
                                           C.POINTER(C.c_float)]),
+    ("smx_nj", C.c_int, [_P, C.c_uint32, _P, _P, _P, C.POINTER(C.c_float)]),
     ("smx_cons_pileup", C.c_int, [C.c_char_p, _P, C.c_uint32, _P, _P, C.c_uint32, _P, _P, C.POINTER(C.c_float)]),
     ("smx_cons_votes", C.c_int, [C.c_char_p, _P, C.c_uint32, _P, _P, C.c_uint32, _P, _P, C.POINTER(C.c_float)]),
     ("smx_cons_phase", C.c_int, [C.c_char_p, _P, C.c_uint32, _P, _P, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,

@@ -290,6 +290,25 @@ def prefix_reach_matrix(seqs: Sequence[bytes], weights: Sequence[int], needs: Se
     return split(vals, shapes)
 
 
+# ------------------------------------------------------------------------------------------------ tree
+def nj(tri, n: int, kernel_ms: Optional[list] = None) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """One smx_nj call: the neighbour-joining tree of n tips from their packed upper triangle of distances (n (n - 1) / 2
+    int32 >= 0, row-major over i < j, what pairs_distances returns for a job).  Returns the max(n - 3, 0) merge records
+    (NJ_MERGE_DTYPE: merge t joins the nodes a and b into the node n + t), the three nodes left (uint32; 0..n-1 for
+    n <= 3, the rest 0) and their distances d01, d02, d12 (float64)."""
+    n = int(n)
+    tri = np.ascontiguousarray(tri, dtype=np.int32).reshape(-1)
+    if n < 0 or tri.size != n * (n - 1) // 2:
+        raise ValueError("tri must hold the n (n - 1) / 2 entries of the upper triangle")
+    n_merges = max(n - 3, 0)
+    merges = _filled(max(n_merges, 1) * (_lib.NJ_MERGE_DTYPE.itemsize // 8), KEY_SENTINEL, np.uint64).view(_lib.NJ_MERGE_DTYPE)
+    last = _filled(3, WORD_SENTINEL, np.uint32)
+    last_d = _filled(3, KEY_SENTINEL, np.uint64).view(np.float64)
+    padded = tri if tri.size else np.zeros(1, dtype=np.int32)      # never a null pointer
+    invoke("smx_nj", _lib.ptr(padded), n, _lib.ptr(merges), _lib.ptr(last), _lib.ptr(last_d), kernel_ms=kernel_ms)
+    return merges[:n_merges], last, last_d
+
+
 # ------------------------------------------------------------------------------------------------ chimera
 def _scan(name, head, patterns, k, n, tail, max_hits, kernel_ms):
     """Both inner scans: `head` and `tail` are the arguments before and after (patterns, poff, n_patterns, k)."""

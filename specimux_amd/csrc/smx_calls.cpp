@@ -1,5 +1,5 @@
 // smx_calls.cpp -- the one-shot calls of libsmx.so over host buffers: alignments (smx_align, smx_align_batch), specimine
-// (smx_mine.hip), clusters (smx_pairs.hip), consensus (smx_cons.hip), crosstalk (smx_nearest.hip), identify (smx_hits.hip), bimera (smx_reach.hip) and the inner scan (smx_inner.hip).  Each keeps one grow-only device workspace; its calls are serialised.
+// (smx_mine.hip), clusters (smx_pairs.hip), consensus (smx_cons.hip), crosstalk (smx_nearest.hip), identify (smx_hits.hip), bimera (smx_reach.hip), tree (smx_nj.hip) and the inner scan (smx_inner.hip).  Each keeps one grow-only device workspace; its calls are serialised.
 // Every *_call below runs in one order: null checks, the plan (a bad call is refused here, without a
 // device), the workspace's lock, require_device, *kernel_ms = 0, the early returns of a call without work, the uploads,
 // the launches (timed_launches), the copy-out.  Consensus alone zeroes *kernel_ms and answers a call without jobs
@@ -12,6 +12,7 @@
 #include "smx_nearest_plan.h"
 #include "smx_hits_plan.h"
 #include "smx_reach_plan.h"
+#include "smx_nj_plan.h"
 #include "smx_mine_plan.h"
 #include "smx_pairs_plan.h"
 #include "smx_inner_plan.h"
@@ -494,6 +495,54 @@ int smx_prefix_reach_matrix(const char *seqs, const uint64_t *off, uint32_t n_se
                             const uint32_t *need, const smx_reach_job *jobs, uint32_t n_jobs, uint32_t E, uint32_t *reach,
                             float *kernel_ms) {
     return reach_call(true, seqs, off, n_seqs, weight, need, jobs, n_jobs, E, nullptr, reach, kernel_ms);
+}
+
+// ---- tree: the neighbour-joining merges of n tips from their packed distance triangle (smx_nj.hip); a workspace of its
+// own.  Every buffer entry a launch reads was written by an earlier launch of the same call, so nothing an earlier,
+// larger call left in the workspace is ever seen
+namespace {
+struct {
+    std::mutex mutex;
+    DevBuf tri, d, r, node, best_q, best_hi, merges;
+} g_nj;
+
+int nj_call(const int32_t *tri, uint32_t n, smx_nj_merge *merges, uint32_t *last, double *last_d, float *kernel_ms) {
+    // the checks, the buffer sizes and the launch counts: smx_nj_plan.h
+    smx::NjPlan P;
+    std::string why;
+    SMX_TRY(refused(smx::nj_plan(tri, n, merges, last, last_d, &P, &why), why));
+    std::lock_guard<std::mutex> guard(g_nj.mutex);
+    SMX_TRY(require_device());
+    if (kernel_ms) *kernel_ms = 0.0f;
+    if (P.iterations == 0) {                      // n <= 3: nothing to join
+        smx::nj_small(tri, n, last, last_d);
+        return SMX_OK;
+    }
+    auto &W = g_nj;
+    HIP_TRY(W.tri.upload(tri, (size_t)P.tri_bytes));
+    HIP_TRY(W.d.ensure((size_t)P.d_bytes));
+    HIP_TRY(W.r.ensure((size_t)P.r_bytes));
+    HIP_TRY(W.node.ensure((size_t)P.node_bytes));
+    HIP_TRY(W.best_q.ensure((size_t)P.best_q_bytes));
+    HIP_TRY(W.best_hi.ensure((size_t)P.best_hi_bytes));
+    HIP_TRY(W.merges.ensure((size_t)P.merges_bytes));
+    SMX_TRY(timed_launches(kernel_ms, "tree kernel launch", [&] {
+        return smx_launch_nj(nullptr, W.tri.as<int32_t>(), n, W.d.as<double>(), W.r.as<double>(), W.node.as<uint32_t>(),
+                             W.best_q.as<double>(), W.best_hi.as<uint32_t>(), W.merges.p);
+    }));
+    HIP_TRY(hipMemcpy(merges, W.merges.p, (size_t)P.merges_bytes, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(last, W.node.p, 3 * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    double d3[3][3];                              // the slots 0, 1, 2 of the matrix
+    HIP_TRY(hipMemcpy2D(d3, sizeof d3[0], W.d.p, (size_t)n * sizeof(double), sizeof d3[0], 3, hipMemcpyDeviceToHost));
+    last_d[0] = d3[0][1];
+    last_d[1] = d3[0][2];
+    last_d[2] = d3[1][2];
+    return SMX_OK;
+}
+}  // namespace
+
+int smx_nj(const int32_t *tri, uint32_t n, smx_nj_merge *merges, uint32_t last[3], double last_d[3], float *kernel_ms) {
+    return nj_call(tri, n, merges, last, last_d, kernel_ms);
 }
 
 // ---- consensus: every member read of a job aligned to the job's draft with traceback, the rows reduced to votes

@@ -233,6 +233,12 @@ int smx_launch_reach(void *stream, int matrix, const unsigned char *d_bytes, con
                      const uint32_t *d_weight, const uint32_t *d_need, const void *d_recs, const uint64_t *d_chunk_start,
                      uint32_t n_recs, const void *d_jobs, int grid, uint64_t per_block, int E, uint32_t n_seqs,
                      unsigned long long *d_keys, uint32_t *d_values);
+// tree (smx_nj.hip): every launch of one call, 3 < n <= SMX_NJ_MAX_N, enqueued without a wait in between: the init launch
+// over the n (n - 1) / 2 entries of d_tri, then for each merge t = 0 .. n - 4 the row minima and the join.  d_d: n x n
+// doubles; d_r, d_best_q: n doubles; d_node, d_best_hi: n uint32; d_merges: n - 3 smx_nj_merge.  Every entry a launch
+// reads was written by an earlier launch of the same call.  Afterwards the slots 0, 1, 2 of d_d and d_node are the last three
+int smx_launch_nj(void *stream, const int32_t *d_tri, uint32_t n, double *d_d, double *d_r, uint32_t *d_node,
+                  double *d_best_q, uint32_t *d_best_hi, void *d_merges);
 // inner scan (smx_inner.hip): the scan over A->n_units units x npass passes of G (4 or 8) patterns, w64 = 64-bit words;
 // then one merge launch over n_reads x A->Q (read, pattern) pairs once every class has left its records
 int smx_launch_inner_scan(void *stream, int w64, int G, int npass, const smx::InnerArgs *A);
