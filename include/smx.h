@@ -33,6 +33,7 @@
  *           a called sequence can be trusted (smx_cons_resample, section 20), or how noisy the reads themselves are
  *           (smx_cons_profile, section 21).
  *   smx_nj            <- nothing: the reference builds no tree of a run's sequences.
+ *   smx_msa           <- nothing: the reference aligns no run's sequences to one another.
  *   smx_inner_scan    <- nothing: the reference never looks between the two end windows.
  *   smx_counts_*      <- the parent summing (batch_total, batch_matched) (orchestration.py:203-207).
  *
@@ -665,6 +666,45 @@ typedef struct smx_nj_merge {
 } smx_nj_merge;
 
 int smx_nj(const int32_t *tri, uint32_t n, smx_nj_merge *merges, uint32_t last[3], double last_d[3], float *kernel_ms);
+
+/*
+ * msa: the progressive multiple alignment of n sequences along a guide tree -- what specimux-msa writes; nothing in the
+ * reference does this.  Every merge of the tree aligns the profiles of its two children by an
+ * integer-weighted dynamic programme with traceback; everything is integer and fixed to the last tie-break
+ * (smx_msa_core.h), so the rows, lengths and costs are the same bytes from run to run and equal to a host loop's.
+ *   seqs, off          n sequences back to back, n + 1 offsets; none is empty (SMX_ERR_ARG) or longer than
+ *                      SMX_MSA_MAX_COLS (SMX_ERR_UNSUPPORTED).  A C G T (upper case) are four symbols, every other byte
+ *                      is a fifth one that equals itself
+ *   n                  0..SMX_MSA_MAX_N (SMX_ERR_UNSUPPORTED above)
+ *   merges             n - 1 records: merge t joins the nodes a != b, both < n + t, into the node n + t; the tips are the
+ *                      nodes 0..n-1 and every node is a child at most once (SMX_ERR_ARG otherwise)
+ *   mismatch, gap      the weights X and G, 1..1000 each (SMX_ERR_ARG)
+ *   cap_cols           the columns a row of `rows` has room for
+ *   rows               n x cap_cols bytes; receives n rows of stride *n_cols: tip i's bytes at its columns, '-' elsewhere
+ *   n_cols             the columns of the alignment.  If it exceeds cap_cols the call returns SMX_ERR_OVERFLOW with
+ *                      *n_cols set, lens and costs filled and rows untouched: call again with that many
+ *   lens, costs        n - 1 entries: the columns of node n + t, and the cost of merge t -- the sum over the tips x under
+ *                      a and y under b of the pairwise cost of their rows (both gaps 0, one gap G, different symbols X)
+ * A node of more than SMX_MSA_MAX_COLS columns ends the call with SMX_ERR_UNSUPPORTED.  Every other refusal comes before
+ * anything is launched.  n = 0 writes nothing but *n_cols = 0; n = 1 returns the sequence.  kernel_ms (may be NULL)
+ * receives the device time of the kernels (HIP events), level after level.
+ */
+#define SMX_MSA_MAX_N    4096
+#define SMX_MSA_MAX_COLS 8192
+
+typedef struct smx_msa_merge { uint32_t a, b; } smx_msa_merge;
+
+int smx_msa(const char *seqs, const uint64_t *off, uint32_t n, const smx_msa_merge *merges, uint32_t mismatch, uint32_t gap,
+            uint32_t cap_cols, uint8_t *rows, uint32_t *n_cols, uint32_t *lens, uint64_t *costs, float *kernel_ms);
+
+/*
+ * Diagnostic (tools/msa_bench.py): where the last smx_msa call of this process that asked for kernel_ms spent its device
+ * time.  level_ms receives the time of the tree's levels in order, min(*n_levels, cap_levels) of them; tips_rows_ms the
+ * time of the tips launch and of the rows launch; phase_us the time of the merge kernel's three phases (forward, walk
+ * back, build), summed over the call's merges as thread 0 of each workgroup saw it on the device's wall clock -- zeros
+ * unless the call ran with SMX_MSA_PHASE_TIMING set in the environment.
+ */
+int smx_msa_debug_times(float *level_ms, uint32_t cap_levels, uint32_t *n_levels, float tips_rows_ms[2], double phase_us[3]);
 
 /*
  * Match statistics (specimux-stats; reference trace_stats.py): the "pool -> primer pair -> outcome" tables counted on the

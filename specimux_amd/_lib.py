@@ -47,6 +47,9 @@ NJ_MERGE_DTYPE = np.dtype([("a", "<u4"), ("b", "<u4"), ("n_active", "<u4"), ("pa
                            ("rb", "<f8")])
 NJ_MAX_N = 16384
 assert NJ_MERGE_DTYPE.itemsize == 40
+MSA_MERGE_DTYPE = np.dtype([("a", "<u4"), ("b", "<u4")])
+MSA_MAX_N, MSA_MAX_COLS = 4096, 8192
+assert MSA_MERGE_DTYPE.itemsize == 8
 
 
 class PanelDesc(C.Structure):
@@ -127,6 +130,8 @@ SYMBOLS = [
     ("smx_prefix_reach_matrix", C.c_int, [C.c_char_p, _P, C.c_uint32, _P, _P, _P, C.c_uint32, C.c_uint32, _P,
                                           C.POINTER(C.c_float)]),
     ("smx_nj", C.c_int, [_P, C.c_uint32, _P, _P, _P, C.POINTER(C.c_float)]),
+    ("smx_msa", C.c_int, [C.c_char_p, _P, C.c_uint32, _P, C.c_uint32, C.c_uint32, C.c_uint32, _P, _P, _P, _P, C.POINTER(C.c_float)]),
+    ("smx_msa_debug_times", C.c_int, [_P, C.c_uint32, _P, _P, _P]),
     ("smx_cons_pileup", C.c_int, [C.c_char_p, _P, C.c_uint32, _P, _P, C.c_uint32, _P, _P, C.POINTER(C.c_float)]),
     ("smx_cons_votes", C.c_int, [C.c_char_p, _P, C.c_uint32, _P, _P, C.c_uint32, _P, _P, C.POINTER(C.c_float)]),
     ("smx_cons_phase", C.c_int, [C.c_char_p, _P, C.c_uint32, _P, _P, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,

@@ -14,6 +14,7 @@ from . import _lib
 
 KEY_SENTINEL = 0x5A5A5A5A5A5A5A5A          # never a key the library leaves: it writes every entry
 WORD_SENTINEL = 0x5A5A5A5A
+ROW_SENTINEL = 0x5A                        # never a byte smx_msa leaves where it promises a row
 DIST_SENTINEL = -7                         # never a distance: those are >= -1
 ALWAYS = 2**32 - 1                         # the largest weight / need smx_prefix_reach takes
 REACH_SLOTS = 2                            # its keys per (query, side, e)
@@ -307,6 +308,39 @@ def nj(tri, n: int, kernel_ms: Optional[list] = None) -> Tuple[np.ndarray, np.nd
     padded = tri if tri.size else np.zeros(1, dtype=np.int32)      # never a null pointer
     invoke("smx_nj", _lib.ptr(padded), n, _lib.ptr(merges), _lib.ptr(last), _lib.ptr(last_d), kernel_ms=kernel_ms)
     return merges[:n_merges], last, last_d
+
+
+# ------------------------------------------------------------------------------------------------ msa
+def msa(seqs: Sequence[bytes], merges, mismatch: int = 1, gap: int = 1, cap_cols: Optional[int] = None,
+        kernel_ms: Optional[list] = None) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """One smx_msa call: the n sequences aligned along the guide tree `merges` (n - 1 pairs (a, b): merge t joins the nodes
+    a and b into the node n + t; the tips are 0..n-1).  Returns the rows [n, n_cols] uint8 ('-' where a row has a gap),
+    the columns of every new node (uint32) and the cost of every merge (uint64).  cap_cols, the room of a row, defaults to
+    min(MSA_MAX_COLS, 2 x the longest + 64); if the library reports more columns (SMX_ERR_OVERFLOW) the call is made once
+    more with the reported number, and kernel_ms receives both device times."""
+    n = len(seqs)
+    pairs = [(int(a), int(b)) for a, b in merges]
+    if len(pairs) != max(n - 1, 0):
+        raise ValueError("merges must hold n - 1 pairs")
+    marr = job_array(pairs, _lib.MSA_MERGE_DTYPE) if pairs else np.zeros(1, dtype=_lib.MSA_MERGE_DTYPE)   # never a null pointer
+    cap = min(_lib.MSA_MAX_COLS, 2 * max((len(s) for s in seqs), default=0) + 64) if cap_cols is None else int(cap_cols)
+    times: list = []
+    for attempt in (0, 1):
+        rows = _filled(n * cap, ROW_SENTINEL, np.uint8)
+        n_cols = _filled(1, WORD_SENTINEL, np.uint32)
+        lens = _filled(n - 1, WORD_SENTINEL, np.uint32)
+        costs = _filled(n - 1, KEY_SENTINEL, np.uint64)
+        status = invoke("smx_msa", b"".join(seqs), _lib.ptr(offsets(seqs)), n, _lib.ptr(marr), int(mismatch), int(gap), cap,
+                        _lib.ptr(rows), _lib.ptr(n_cols), _lib.ptr(lens), _lib.ptr(costs), kernel_ms=times, check=False)
+        if status == _lib.ERR_OVERFLOW and attempt == 0 and cap < int(n_cols[0]) <= _lib.MSA_MAX_COLS:
+            cap = int(n_cols[0])
+            continue
+        _lib.check(status)
+        break
+    if kernel_ms is not None:
+        kernel_ms.extend(times)
+    nc = int(n_cols[0])
+    return rows[:n * nc].reshape(n, nc), lens[:max(n - 1, 0)], costs[:max(n - 1, 0)]
 
 
 # ------------------------------------------------------------------------------------------------ chimera

@@ -1,5 +1,5 @@
 // smx_calls.cpp -- the one-shot calls of libsmx.so over host buffers: alignments (smx_align, smx_align_batch), specimine
-// (smx_mine.hip), clusters (smx_pairs.hip), consensus (smx_cons.hip), crosstalk (smx_nearest.hip), identify (smx_hits.hip), bimera (smx_reach.hip), tree (smx_nj.hip) and the inner scan (smx_inner.hip).  Each keeps one grow-only device workspace; its calls are serialised.
+// (smx_mine.hip), clusters (smx_pairs.hip), consensus (smx_cons.hip), crosstalk (smx_nearest.hip), identify (smx_hits.hip), bimera (smx_reach.hip), tree (smx_nj.hip), msa (smx_msa.hip) and the inner scan (smx_inner.hip).  Each keeps one grow-only device workspace; its calls are serialised.
 // Every *_call below runs in one order: null checks, the plan (a bad call is refused here, without a
 // device), the workspace's lock, require_device, *kernel_ms = 0, the early returns of a call without work, the uploads,
 // the launches (timed_launches), the copy-out.  Consensus alone zeroes *kernel_ms and answers a call without jobs
@@ -13,6 +13,7 @@
 #include "smx_hits_plan.h"
 #include "smx_reach_plan.h"
 #include "smx_nj_plan.h"
+#include "smx_msa_plan.h"
 #include "smx_mine_plan.h"
 #include "smx_pairs_plan.h"
 #include "smx_inner_plan.h"
@@ -543,6 +544,160 @@ int nj_call(const int32_t *tri, uint32_t n, smx_nj_merge *merges, uint32_t *last
 
 int smx_nj(const int32_t *tri, uint32_t n, smx_nj_merge *merges, uint32_t last[3], double last_d[3], float *kernel_ms) {
     return nj_call(tri, n, merges, last, last_d, kernel_ms);
+}
+
+// ---- msa: the progressive alignment of n sequences along a guide tree (smx_msa.hip); a workspace of its own.  The host
+// waits once per level of the tree, reads that level's lengths (one small copy) and sizes the next level's launches by
+// them.  Every buffer entry a launch reads was written by an earlier launch of the same call
+namespace {
+struct {
+    std::mutex mutex;
+    DevBuf bytes, doff, prof_off, prof, maps, recs, tb, ops, row, lens, costs, parent, map_off, rows, phase;
+    // what smx_msa_debug_times hands out: of the last call that asked for kernel_ms, the device time of every level and of
+    // the tips and rows launches; with SMX_MSA_PHASE_TIMING, the wall-clock ticks of the merge kernel's three phases,
+    // summed over the call's merges
+    std::vector<float> level_ms;
+    float tips_ms = 0.0f, rows_ms = 0.0f;
+    uint64_t phase_ticks[3] = {0, 0, 0};
+    int clock_khz = 0;
+} g_msa;
+
+// a buffer that keeps its first `used` bytes when it grows: the profiles and maps of the levels that have run
+hipError_t grow_keeping(DevBuf *b, size_t need, size_t used) {
+    if (need <= b->cap) return hipSuccess;
+    DevBuf bigger;
+    hipError_t e = bigger.ensure(need + need / 2);
+    if (e == hipSuccess && used) e = hipMemcpy(bigger.p, b->p, used, hipMemcpyDeviceToDevice);
+    if (e != hipSuccess) {
+        bigger.release();
+        return e;
+    }
+    b->release();
+    *b = bigger;
+    return hipSuccess;
+}
+
+int msa_call(const char *seqs, const uint64_t *off, uint32_t n, const smx_msa_merge *merges, uint32_t X, uint32_t G,
+             uint32_t cap_cols, uint8_t *rows, uint32_t *n_cols, uint32_t *lens, uint64_t *costs, float *kernel_ms) {
+    // the checks, the levels and the sizes: smx_msa_plan.h
+    smx::MsaPlan P;
+    std::string why;
+    SMX_TRY(refused(smx::msa_plan(seqs, off, n, merges, X, G, rows, n_cols, lens, costs, &P, &why), why));
+    // clusters.budget_bytes(): SMX_CLUSTERS_BUDGET_BYTES, else SMX_MINE_BUDGET_BYTES, else the default; empty or 0 is unset
+    uint64_t budget = 0;
+    for (const char *name : {"SMX_CLUSTERS_BUDGET_BYTES", "SMX_MINE_BUDGET_BYTES"})
+        if (const char *env = budget ? nullptr : getenv(name)) budget = strtoull(env, nullptr, 10);
+    if (!budget) budget = smx::MSA_DEFAULT_BUDGET;
+    const bool phases = getenv("SMX_MSA_PHASE_TIMING") != nullptr;   // diagnostic: smx_msa_debug_times
+    std::lock_guard<std::mutex> guard(g_msa.mutex);
+    SMX_TRY(require_device());
+    if (kernel_ms) *kernel_ms = 0.0f;
+    *n_cols = 0;
+    if (n == 0) return SMX_OK;
+    if (n == 1) {                                 // nothing to align: the sequence is the row
+        *n_cols = (uint32_t)(off[1] - off[0]);
+        if (*n_cols > cap_cols) return fail(SMX_ERR_OVERFLOW, "%u columns, room for %u", *n_cols, cap_cols);
+        memcpy(rows, seqs + off[0], *n_cols);
+        return SMX_OK;
+    }
+    auto &W = g_msa;
+    smx::MsaState S;
+    smx::msa_state_init(P, off, &S);
+    std::vector<uint64_t> doff(n + 1);
+    for (uint32_t i = 0; i <= n; i++) doff[i] = off[i] - off[0];
+    HIP_TRY(W.bytes.upload(seqs + off[0], (size_t)P.seq_bytes));
+    HIP_TRY(W.doff.upload(doff));
+    HIP_TRY(W.prof_off.upload(S.prof_off.data(), (size_t)n * sizeof(uint64_t)));
+    HIP_TRY(W.prof.ensure((size_t)S.prof_used * 4 * sizeof(smx::MsaCol)));   // a guess; grow_keeping has the last word
+    HIP_TRY(W.lens.ensure((size_t)P.n_merges * sizeof(uint32_t)));
+    HIP_TRY(W.costs.ensure((size_t)P.n_merges * sizeof(uint64_t)));
+    float total = 0.0f, ms = 0.0f;
+    float *part = kernel_ms ? &ms : nullptr;
+    W.level_ms.clear();
+    W.tips_ms = W.rows_ms = 0.0f;
+    W.phase_ticks[0] = W.phase_ticks[1] = W.phase_ticks[2] = 0;
+    std::vector<unsigned long long> h_phase;
+    SMX_TRY(timed_launches(part, "msa tips launch", [&] {
+        return smx_launch_msa_tips(nullptr, W.bytes.as<unsigned char>(), W.doff.as<uint64_t>(), n, W.prof_off.as<uint64_t>(), W.prof.p);
+    }));
+    total += ms;
+    W.tips_ms = ms;
+    std::vector<uint32_t> h_lens(P.n_merges);
+    std::vector<smx::MsaLaunch> launches;
+    std::vector<smx::MsaMergeDev> recs;
+    for (uint32_t v = 1; v <= P.n_levels; v++) {
+        smx::msa_level_launches(P, merges, S, v, budget, &launches);
+        float level = 0.0f;
+        for (const smx::MsaLaunch &L : launches) {
+            const uint64_t prof_before = S.prof_used, map_before = S.map_used;
+            smx::msa_launch_records(P, merges, L, &S, &recs);
+            HIP_TRY(grow_keeping(&W.prof, (size_t)S.prof_used * sizeof(smx::MsaCol), (size_t)prof_before * sizeof(smx::MsaCol)));
+            HIP_TRY(grow_keeping(&W.maps, (size_t)S.map_used * sizeof(uint16_t), (size_t)map_before * sizeof(uint16_t)));
+            HIP_TRY(W.recs.upload(recs));
+            HIP_TRY(W.tb.ensure((size_t)L.tb_words * sizeof(uint32_t)));
+            HIP_TRY(W.ops.ensure((size_t)L.ops_bytes));
+            HIP_TRY(W.row.ensure((size_t)L.row_entries * sizeof(uint64_t)));
+            if (phases) HIP_TRY(W.phase.ensure((size_t)L.count * 4 * sizeof(unsigned long long)));
+            SMX_TRY(timed_launches(part, "msa merge launch", [&] {
+                return smx_launch_msa_merge(nullptr, W.recs.p, L.count, X, G, W.prof.p, W.maps.as<uint16_t>(), W.tb.as<uint32_t>(),
+                                            W.ops.as<uint8_t>(), W.row.as<uint64_t>(), W.lens.as<uint32_t>(), W.costs.as<uint64_t>(),
+                                            phases ? W.phase.as<unsigned long long>() : nullptr);
+            }));
+            total += ms;
+            level += ms;
+            if (phases) {
+                h_phase.resize((size_t)L.count * 4);
+                HIP_TRY(hipMemcpy(h_phase.data(), W.phase.p, h_phase.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+                for (uint32_t x = 0; x < L.count; x++)
+                    for (int k = 0; k < 3; k++) W.phase_ticks[k] += h_phase[4 * x + k + 1] - h_phase[4 * x + k];
+            }
+        }
+        if (kernel_ms) W.level_ms.push_back(level);
+        // the level's lengths: the next level is sized by them (entries of later levels are not looked at)
+        HIP_TRY(hipMemcpy(h_lens.data(), W.lens.p, (size_t)P.n_merges * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        for (const smx::MsaLaunch &L : launches) SMX_TRY(refused(smx::msa_launch_done(P, L, h_lens.data(), &S, &why), why));
+    }
+    const uint32_t root_cols = S.len[P.n_nodes - 1];
+    *n_cols = root_cols;
+    memcpy(lens, h_lens.data(), (size_t)P.n_merges * sizeof(uint32_t));
+    HIP_TRY(hipMemcpy(costs, W.costs.p, (size_t)P.n_merges * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    if (kernel_ms) *kernel_ms = total;
+    if (root_cols > cap_cols) return fail(SMX_ERR_OVERFLOW, "%u columns, room for %u", root_cols, cap_cols);
+    HIP_TRY(W.parent.upload(P.parent));
+    HIP_TRY(W.map_off.upload(S.map_off));
+    HIP_TRY(W.rows.ensure((size_t)n * root_cols));
+    SMX_TRY(timed_launches(part, "msa rows launch", [&] {
+        return smx_launch_msa_rows(nullptr, W.bytes.as<unsigned char>(), W.doff.as<uint64_t>(), n, W.parent.as<uint32_t>(),
+                                   W.map_off.as<uint64_t>(), W.maps.as<uint16_t>(), root_cols, W.rows.as<uint8_t>());
+    }));
+    total += ms;
+    W.rows_ms = ms;
+    if (kernel_ms) *kernel_ms = total;
+    HIP_TRY(hipMemcpy(rows, W.rows.p, (size_t)n * root_cols, hipMemcpyDeviceToHost));
+    return SMX_OK;
+}
+}  // namespace
+
+int smx_msa_debug_times(float *level_ms, uint32_t cap_levels, uint32_t *n_levels, float tips_rows_ms[2], double phase_us[3]) {
+    if (!n_levels || !tips_rows_ms || !phase_us || (cap_levels && !level_ms)) return fail(SMX_ERR_ARG, "null argument");
+    std::lock_guard<std::mutex> guard(g_msa.mutex);
+    auto &W = g_msa;
+    if (!W.clock_khz) {
+        SMX_TRY(require_device());
+        if (hipDeviceGetAttribute(&W.clock_khz, hipDeviceAttributeWallClockRate, 0) != hipSuccess || W.clock_khz <= 0)
+            W.clock_khz = 100000;                 // gfx9's constant 100 MHz
+    }
+    *n_levels = (uint32_t)W.level_ms.size();
+    for (uint32_t v = 0; v < *n_levels && v < cap_levels; v++) level_ms[v] = W.level_ms[v];
+    tips_rows_ms[0] = W.tips_ms;
+    tips_rows_ms[1] = W.rows_ms;
+    for (int k = 0; k < 3; k++) phase_us[k] = (double)W.phase_ticks[k] * 1000.0 / (double)W.clock_khz;
+    return SMX_OK;
+}
+
+int smx_msa(const char *seqs, const uint64_t *off, uint32_t n, const smx_msa_merge *merges, uint32_t mismatch, uint32_t gap,
+            uint32_t cap_cols, uint8_t *rows, uint32_t *n_cols, uint32_t *lens, uint64_t *costs, float *kernel_ms) {
+    return msa_call(seqs, off, n, merges, mismatch, gap, cap_cols, rows, n_cols, lens, costs, kernel_ms);
 }
 
 // ---- consensus: every member read of a job aligned to the job's draft with traceback, the rows reduced to votes

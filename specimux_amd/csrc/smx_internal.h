@@ -239,6 +239,20 @@ int smx_launch_reach(void *stream, int matrix, const unsigned char *d_bytes, con
 // reads was written by an earlier launch of the same call.  Afterwards the slots 0, 1, 2 of d_d and d_node are the last three
 int smx_launch_nj(void *stream, const int32_t *d_tri, uint32_t n, double *d_d, double *d_r, uint32_t *d_node,
                   double *d_best_q, uint32_t *d_best_hi, void *d_merges);
+// msa (smx_msa.hip).  d_bytes / d_doff: the n sequences back to back and their n + 1 offsets from 0.  tips: the one-hot
+// profiles of the tips, tip i's at the column d_prof_off[i] of d_prof (16 bytes a column).  merge: the `count` merges of one
+// launch (MsaMergeDev, smx_msa_core.h, offsets into d_prof, d_maps and the launch's scratch d_tb / d_ops / d_row), all of one
+// level of the tree: each reads its children's profiles, which earlier launches wrote, and writes the new node's profile,
+// its children's maps, lens[t] and costs[t].  rows: n rows of n_cols bytes from the maps, d_parent (MSA_NONE: the root)
+// and d_map_off per node.  d_phase (may be null): 4 wall-clock reads per merge of the launch, thread 0's, at the start, after
+// the forward phase, after the walk and at the end (SMX_MSA_PHASE_TIMING)
+int smx_launch_msa_tips(void *stream, const unsigned char *d_bytes, const uint64_t *d_doff, uint32_t n,
+                        const uint64_t *d_prof_off, void *d_prof);
+int smx_launch_msa_merge(void *stream, const void *d_recs, uint32_t count, uint32_t X, uint32_t G, void *d_prof, uint16_t *d_maps,
+                         uint32_t *d_tb, uint8_t *d_ops, uint64_t *d_row, uint32_t *d_lens, uint64_t *d_costs,
+                         unsigned long long *d_phase);
+int smx_launch_msa_rows(void *stream, const unsigned char *d_bytes, const uint64_t *d_doff, uint32_t n, const uint32_t *d_parent,
+                        const uint64_t *d_map_off, const uint16_t *d_maps, uint32_t n_cols, uint8_t *d_rows);
 // inner scan (smx_inner.hip): the scan over A->n_units units x npass passes of G (4 or 8) patterns, w64 = 64-bit words;
 // then one merge launch over n_reads x A->Q (read, pattern) pairs once every class has left its records
 int smx_launch_inner_scan(void *stream, int w64, int G, int npass, const smx::InnerArgs *A);
